@@ -11,12 +11,20 @@ With N GPUs the ladder is sharded in contiguous rung blocks (1024/N rungs per GP
 with N so that per-GPU work is fixed (weak scaling); accepted exchanges across a shard boundary travel as
 point-to-point messages between neighbouring ranks.
 
-Prints ONE JSON line (rank 0).  roofline.achieved = algorithmic bytes per launch (16*D+44 B per MH step, SURVEY.md
+Prints ONE JSON line (rank 0).  A plain run measures the headline figure only: set-up, warm-up, the timed steps and the line
+(value, ms_per_step, the roofline of the timed sweep launches).  --full adds everything that takes runs of its own: the device
+calibration, the latency companions (w1, w1_sampler_defaults), the evolving ladders and the CPU baselines.
+--dump-outputs DIR writes, after the timed steps, a fixed sample of what the last step left the caller (states, log
+likelihoods / priors / posteriors, counters, temperatures, swap counts) as DIR/<name>.npy; the inputs and the number of steps
+before the dump depend on the arguments alone, so two builds can be compared output for output.
+
+roofline.achieved = algorithmic bytes per launch (16*D+44 B per MH step, SURVEY.md
 section 8(d), x the chains the sweep kernel works on in that launch -- the compacted sweep skips the rungs an exchange
 attempt touched; counted from MH_chain::Ntries) / mean duration of that kernel from HIP events recorded around each of
 its launches on the engine's stream inside the timed region (roofline_record() has the definitions of frac, step_frac,
-traffic_frac).  cpu_baseline = the real reference's own parallel_tempering_chains::step
-(oracle/_ref/ptm_ref_driver, built from /root/reference) on this host, 1 thread, bounded sample.
+traffic_frac).  cpu_baseline (--full) = the real reference's own parallel_tempering_chains::step
+(oracle/_ref/ptm_ref_driver, built by `make -C oracle ref` where the reference sources are present) on this host, 1 thread,
+bounded sample; without that binary, the C port on all usable host cores.
 """
 import argparse
 import json
@@ -176,14 +184,42 @@ def cpu_port(problem, budget_s=8.0):
 DEFAULT_WALKERS = 16384
 
 
-def settle(eng, seconds=0.25):
-    """set-up, before the W warm-up steps: run the ladder for a quarter of a second so that the GPU's clocks have ramped
-    and the chains have left their prior draws (the acceptance pattern, and with it the row traffic, is then the
-    stationary one).  Not timed, not counted."""
-    t0 = time.perf_counter()
-    while time.perf_counter() - t0 < seconds:
+def settle_steps(n_chains, seconds=0.25, rate=9e9, min_step_s=2e-5):
+    """how many set-up steps make about `seconds` of work for a population of n_chains at the headline rate (MH steps/s; a
+    step takes at least min_step_s however small the population): a count fixed by the arguments, not by a clock, so that
+    every run with the same arguments leaves the same chains behind (--dump-outputs)"""
+    per_step = max(min_step_s, n_chains / rate)
+    return 20 * max(1, int(round(seconds / per_step / 20)))
+
+
+def settle(eng, steps):
+    """set-up, before the W warm-up steps: run the ladder for about a quarter of a second (settle_steps) so that the GPU's
+    clocks have ramped and the chains have left their prior draws (the acceptance pattern, and with it the row traffic, is
+    then the stationary one).  Not timed, not counted."""
+    for _ in range(steps // 20):
         eng.step(20)
         eng.sync()
+
+
+DUMP_CHAINS = 1 << 16    # chains in the --dump-outputs sample: 16 MB of f64 states at D = 32
+DUMP_LADDERS = 256       # walkers (whole ladders) whose temperatures and swap counters are dumped
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as float64 .npy files -- the states and
+    per-chain arrays of a fixed, seeded sample of the chains (rung-major chain index rung * W + walker, in chain_index.npy),
+    the inverse temperatures and swap counters of a fixed sample of the ladders (walker_index.npy).  About 25 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    chains = np.sort(rng.choice(eng.Nc, size=min(eng.Nc, DUMP_CHAINS), replace=False))
+    walkers = np.sort(rng.choice(eng.W, size=min(eng.W, DUMP_LADDERS), replace=False))
+    t, a = eng.swap_counts()
+    out = {"chain_index": chains, "states": eng.states()[chains], "walker_index": walkers,
+           "invtemps": eng.invtemps()[walkers], "swap_tries": t[walkers], "swap_accepts": a[walkers]}
+    for name in ("llike", "lprior", "lpost", "ntries", "naccept", "last_type"):
+        out[name] = getattr(eng, name)[chains]
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def run_single(args):
@@ -196,8 +232,9 @@ def run_single(args):
     eng = E.Engine(D, NT, W, seed=SEED, swap_rate=SWAP_RATE, add_every_n=100, time_kernels=True)
     pr.configure(eng, E.PROP_LOWER)
     eng.init_from_prior()
-    settle(eng)
-    # what THIS device gives a streaming copy and an f64 fma loop right now (a few hundred ms, before anything is timed): boxes of
+    n_settle = settle_steps(NT * W)
+    settle(eng, n_settle)
+    # (--full) what THIS device gives a streaming copy and an f64 fma loop right now (a few hundred ms, before anything is timed): boxes of
     # the pool differ by several per cent in the clock they hold under an f64 load, and the sweep kernel is bound by f64 issue
     calibration = None if args.no_calibration else eng.calibrate()
     # The GPU must not idle between the warm-up and the timed steps: after ~20 ms without work the device drops its clocks and the
@@ -205,7 +242,7 @@ def run_single(args):
     # after every gap).  Round 3's line read 67 MB of counters back right here and so timed exactly that ramp.  So: everything the
     # host wants to know first (two sums reduced on the device: 16 bytes), then clocks up again, warm-up, and straight into the
     # timed steps with nothing but the contract's synchronisation in between.
-    settle(eng, 0.25)
+    settle(eng, n_settle)
     eng.step(args.warmup)            # (queued behind the settling steps: the device never idles from here to the end of the timed steps)
     tries0 = eng.counter_sums()[0]   # MH_chain::Ntries counts the Metropolis moves made (chain.cc:1005); exchanged rungs make none
     eng.kernel_times(drop=True)      # forget the records so far, unread (a few hundred event queries would be a gap of their own)
@@ -224,6 +261,8 @@ def run_single(args):
                            measured_traffic(eng.sweep_kernel_name) if W == DEFAULT_WALKERS else None, kt=kt, calibration=calibration)
     acc = float((eng.naccept.sum() - eng.Nc)) / max(1, float((eng.ntries.sum() - eng.Nc)))
     t, a = eng.swap_counts()
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
     # latency-bound companion: the bare 1024-chain ladder (W = 1, the reference's own shape and BASELINE's literal one)
     w1 = None
     if not args.no_w1:
@@ -319,9 +358,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--walkers", type=int, default=DEFAULT_WALKERS, help="independent ladders batched per GPU")
     ap.add_argument("--halo", type=int, default=None, help="llike halo depth (rungs) between shards (default: ptmcmc_amd.parallel.DEFAULT_HALO)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-w1", action="store_true", help="skip the 1024-chain latency companion")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the copy / f64-fma calibration of the device (ptm_calibrate)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the device calibration, the 1024-chain latency companions, the "
+                         "evolving ladders and the CPU baselines (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of what the last step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-w1", action="store_true", help="with --full: skip the 1024-chain latency companions and the evolving ladders")
+    ap.add_argument("--no-calibration", action="store_true", help="with --full: skip the copy / f64-fma calibration of the device (ptm_calibrate)")
     ap.add_argument("--shard", choices=("rungs", "walkers"), default="rungs",
                     help="N > 1: how the population is spread -- contiguous rung blocks with neighbour exchanges over RCCL (BASELINE's "
                          "configuration, the default), or whole ladders per GPU (no message at all; the form evolving ladders need)")
@@ -331,7 +375,13 @@ def main():
                          "ptmcmc_amd.parallel.ShardedLadder over torch.distributed")
     ap.add_argument("--force-dist", action="store_true", help="take the torch.distributed path even with one rank (smoke test)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu = args.no_w1 = args.no_calibration = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or args.force_dist):
+        ap.error("--dump-outputs is available on the single-GPU path only (--gpus 1 without --force-dist)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started by hand without the launcher: run the ranks as child processes (nothing has touched the GPU yet)
         import subprocess

@@ -3,12 +3,10 @@ import os
 import sys
 
 import numpy as np
-import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle_lib as O
-from oracle_shard import OracleShard
 from ptmcmc_amd.parallel import ShardedLadder, shard_bounds
 from ptmcmc_amd.problems import GaussianProblem
 
@@ -30,6 +28,10 @@ def make_ladder(D, Nt, W, sr, seed, evolve=0.0, cut=-1.0):
 
 
 if __name__ == "__main__":
+    # torch only in the rank processes: the tests import this module for make_ladder, and torch brought into the pytest process
+    # after the engine library would hold a second HIP runtime beside the one the engine's GPU tests use there
+    import torch.distributed as dist
+    from oracle_shard import OracleShard
     D, Nt, W, nsteps, halo = (int(v) for v in sys.argv[1:6])
     sr, out = float(sys.argv[6]), sys.argv[7]
     evolve, cut = (float(sys.argv[8]), float(sys.argv[9])) if len(sys.argv) > 9 else (0.0, -1.0)

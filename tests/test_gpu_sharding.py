@@ -200,7 +200,8 @@ def test_bench_with_two_ranks_rehearsed_on_one_gpu(sabotage, expect):
     s_ = socket.socket(); s_.bind(("127.0.0.1", 0)); port = s_.getsockname()[1]; s_.close()
     env = dict(os.environ, PTM_BENCH_REHEARSAL="1", PTM_PREFLIGHT_SABOTAGE=sabotage, OMP_NUM_THREADS="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--walkers", "1024", "--steps", "6", "--warmup", "2"],
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--walkers", "1024", "--steps", "6", "--warmup", "2",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     recs = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]

@@ -6,4 +6,4 @@ for C in 0 1; do
 done
 unset PTM_COMPACT
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_sharding.py -x -q -m gpu -k "full_size or sharded or bench or 1024 or exchange_decide" 2>&1 | tail -3
-python bench.py --steps 20 --warmup 5 --no-cpu 2>&1 | tail -1 | cut -c1-1400
+python bench.py --steps 20 --warmup 5 --full --no-cpu 2>&1 | tail -1 | cut -c1-1400

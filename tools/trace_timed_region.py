@@ -22,7 +22,7 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]
 summ = lambda d: {"launches": len(d), "avg_ms": sum(d) / len(d), "min_ms": min(d), "max_ms": max(d)}
 out = {
-    "note": "rocprofv3 --kernel-trace of `bench.py --steps %d --warmup 5 --no-cpu --no-w1`: durations of the sweep kernel's launches from the trace; "
+    "note": "rocprofv3 --kernel-trace of `bench.py --steps %d --warmup 5 --full --no-cpu --no-w1`: durations of the sweep kernel's launches from the trace; "
             "`all` = what profiles/%s_kernel_stats.csv averages (settling steps and the launches behind the calibration's idle gap included), "
             "`timed_region` = the last %d launches = the bench's timed steps, to be compared with the line's own HIP-event figures" % (steps, tag, steps),
     "kernel": rows[0]["Kernel_Name"],
