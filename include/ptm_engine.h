@@ -133,6 +133,24 @@ int ptm_set_target_callback(ptm_engine* e, ptm_loglike_batch_fn fn, void* user);
  * states with the prior's own drawSample and hand them over with ptm_set_states.  fn = NULL removes it. */
 typedef void (*ptm_logprior_batch_fn)(void* user, const double* X, int n, int dim, double* out_lprior);
 int ptm_set_prior_callback(ptm_engine* e, ptm_logprior_batch_fn fn, void* user);
+/* A user likelihood evaluated ON THE DEVICE: called on the HOST once per sweep (and by the state set-up calls), in stream order;
+ * it enqueues its work on `stream` (a hipStream_t) and may return before that work has run.  X_dev [n_rows][dim] row-major,
+ * natural dimension order; rows [0, *count_dev) are the proposals MH_chain::step would evaluate, in local-chain order; rows past
+ * the count hold states inside the prior's support (so a fixed-shape evaluation of all n_rows rows is safe); out_llike_dev
+ * [n_rows].  The step is then exchange kernel -> propose pass -> pack -> the user's work -> scatter -> accept pass, all queued:
+ * ptm_step(n) returns without waiting, as it does for the Gaussian target.
+ * x_batch_dev [n_rows * dim] / llike_batch_dev [n_rows] are device buffers the engine hands to fn (NULL: the engine allocates
+ * them).  n_rows is ptm_target_device_rows.  The last of ptm_set_target_gaussian / _callback / _device called wins.  Refused
+ * (PTM_ERR_UNSUPPORTED) with a prior callback, host-side proposals, rung-sharded steps and partial sweeps. */
+typedef void (*ptm_loglike_device_fn)(void* user, void* stream, int n_rows, int dim, const double* X_dev, const int32_t* count_dev,
+                                      double* out_llike_dev);
+int ptm_set_target_device(ptm_engine* e, ptm_loglike_device_fn fn, void* user, double* x_batch_dev, double* llike_batch_dev);
+/* n_rows of the device likelihood: this engine's local chain count */
+int ptm_target_device_rows(ptm_engine* e);
+/* the best log-posterior (lprior + llike) among the states the device likelihood evaluated since the last state set-up
+ * (ptm_set_states / ptm_init_from_prior_k), and that state x[dim]: bayes_likelihood::bestPost / bestState.  Ties go to the
+ * earliest (step, local chain), a NaN never becomes the best; before any evaluation -inf and the zero state. */
+int ptm_get_best_evaluated(ptm_engine* e, double* lpost, double* x);
 /* inverse temperatures of the GLOBAL ladder, beta[n_rungs] (chain.cc:1181-1183,1340) */
 int ptm_set_ladder(ptm_engine* e, const double* beta);
 /* parallel_tempering_chains::evolve_temps(rate, lpost_cut) (chain.hh:302-307; default-on in the sampler with rate 0.01,

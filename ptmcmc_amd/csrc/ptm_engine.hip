@@ -18,6 +18,7 @@
 
 #include "../../include/ptm_engine.h"
 #include "ptm_aux_kernels.hpp"
+#include "ptm_devlike_kernels.hpp"
 #include "ptm_launch.hpp"
 #include "ptm_shard_rccl.hpp"
 
@@ -108,6 +109,17 @@ struct ptm_engine {
   ptm_propose_batch_fn pcb = nullptr;
   ptm_proposal_result_fn pres = nullptr;
   void* pcb_user = nullptr;
+  // device likelihood (ptm_set_target_device): the user's function enqueues on the stream; its batch buffers (owned or the
+  // caller's), the count, the row -> chain index, the chunk totals of the pack, hand-over buffers in device memory whatever the
+  // population, and the best log-posterior seen with its state {lpost, x[D]}
+  ptm_loglike_device_fn dfn = nullptr;
+  void* dfn_user = nullptr;
+  double *dl_x = nullptr, *dl_ll = nullptr;
+  bool dl_own_x = false, dl_own_ll = false;
+  int32_t* dl_count = nullptr;
+  int *dl_rows = nullptr, *dl_chunks = nullptr;
+  double *dl_xprop = nullptr, *dl_lprior_new = nullptr, *dl_llike_new = nullptr, *dl_best = nullptr;
+  unsigned char* dl_gate = nullptr;
   // compacted sweep (partition_kernel): per-rung lists of the walkers that move, their counts; touched = an exchange phase
   // ran since the last sweep
   int *cidx = nullptr, *ccnt = nullptr;
@@ -462,7 +474,9 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
   void* ptrs[] = {e->x, e->ll, e->lp, e->ntries, e->naccept, e->last_type, e->arr_below, e->arr_above, e->mv_src, e->mv_dst, e->mv_n,
                   e->err, e->nhist, e->swap_cnt, e->touch, e->swap_log, e->hist.x, e->hist.ll, e->hist.lp, e->hist.meta, e->map.lpost, e->map.ll, e->map.lp, e->map.x, e->blo,
                   e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt,
-                  e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type};
+                  e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
+                  e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
+                  e->dl_lprior_new, e->dl_llike_new, e->dl_best};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (e->h_sums) (void)hipHostFree(e->h_sums);
@@ -612,6 +626,7 @@ extern "C" int ptm_set_target_gaussian(ptm_engine* e, const double* mean, const 
   e->like0 = like0;
   e->have_target = 1;
   e->cb = nullptr;  // a device target replaces a host callback
+  e->dfn = nullptr;  // ... and a device likelihood
   return PTM_OK;
 }
 
@@ -643,6 +658,7 @@ extern "C" int ptm_set_target_callback(ptm_engine* e, ptm_loglike_batch_fn fn, v
   int rc = alloc_proposal_buffers(e);
   if (rc) return rc;
   e->cb = fn; e->cb_user = user;
+  e->dfn = nullptr;   // (the last target setter wins)
   e->have_target = 1;
   return PTM_OK;
 }
@@ -650,6 +666,7 @@ extern "C" int ptm_set_target_callback(ptm_engine* e, ptm_loglike_batch_fn fn, v
 extern "C" int ptm_set_prior_callback(ptm_engine* e, ptm_logprior_batch_fn fn, void* user) {
   SETTLE(e);
   if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  if (fn && e->dfn) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior with a device likelihood is not built (ptm_set_target_device)");
   e->prior_cb = fn; e->prior_user = fn ? user : nullptr;
   e->lp_is_const = false;
   return PTM_OK;
@@ -663,6 +680,7 @@ extern "C" int ptm_set_proposal_callback(ptm_engine* e, ptm_propose_batch_fn pro
     e->have_prop = e->prop ? 1 : 0;
     return PTM_OK;
   }
+  if (e->dfn) return fail(PTM_ERR_UNSUPPORTED, "host-side proposals with a device likelihood are not built (ptm_set_target_device)");
   const size_t Nc = e->Nc, DP = e->DP;
   int rc = alloc_proposal_buffers(e);
   if (rc) return rc;
@@ -1052,17 +1070,20 @@ static Dev make_dev(ptm_engine* e) {
   return p;
 }
 
+// a user likelihood, on the host (ptm_set_target_callback) or on the device (ptm_set_target_device): the propose / accept passes
+static inline bool user_like(const ptm_engine* e) { return e->cb != nullptr || e->dfn != nullptr; }
+
 static SweepSel sweep_sel(const ptm_engine* e) {
   SweepSel s;
   s.kind = e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : (e->prop_kind == PTM_PROP_LOWER ? KIND_LOWER : KIND_DENSE);
   s.uni = (e->W % 64) == 0;
   s.host_prop = e->pcb != nullptr;
   if (s.host_prop) s.kind = KIND_DIAG;   // (no factor is read: any instantiation serves)
-  s.plain = !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !e->cb && e->mix_K == 0 && !e->betaC && !s.host_prop;
+  s.plain = !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !e->betaC && !s.host_prop;
   s.simple = s.uni && s.plain;
-  s.lean_ev = s.uni && e->betaC && !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !e->cb && e->mix_K == 0 && !s.host_prop &&
+  s.lean_ev = s.uni && e->betaC && !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !s.host_prop &&
               !e->hist.rungs && !e->map.rungs;
-  s.callback = e->cb != nullptr;
+  s.callback = user_like(e);
   s.de = e->de_on;
   return s;
 }
@@ -1128,12 +1149,127 @@ static int callback_host_part(ptm_engine* e) {
   return PTM_OK;
 }
 
+// ---- device likelihood (ptm_set_target_device) ----------------------------------------------------------------------------
+// pack the selected chains' rows ((gate & gmask) == gval; gate == nullptr: all) into the batch, call the user's function on the
+// stream, scatter its llikes into dst by chain (gate_out: the redraw loop's verdicts) and -- best -- fold lprior + llike of the
+// evaluated rows into the kept best.  Everything is queued; nothing waits.
+static int devlike_eval(ptm_engine* e, const unsigned char* gate, int gmask, int gval, const double* xsel, const double* xrest, double* dst,
+                        unsigned char* gate_out, const double* lprior, bool best) {
+  const int n = e->Nc, D = e->D;
+  const int nchunk = (n + DL_CHUNK - 1) / DL_CHUNK;
+  hipLaunchKernelGGL(devlike_count_kernel, dim3(nchunk), dim3(DL_CHUNK), 0, e->stream, n, gate, gmask, gval, e->dl_chunks);
+  HIPCHK(hipGetLastError());
+#define PTM_DL_PACK(N) case N: hipLaunchKernelGGL((devlike_pack_kernel<N>), dim3(nchunk), dim3(DL_CHUNK), 0, e->stream, n, D, nchunk, gate, gmask, gval, \
+                                                  (const int*)e->dl_chunks, xsel, xrest, e->dl_x, e->dl_rows, e->dl_count); break;
+  switch (e->DP) {
+    PTM_DL_PACK(4) PTM_DL_PACK(8) PTM_DL_PACK(16) PTM_DL_PACK(32) PTM_DL_PACK(64) PTM_DL_PACK(128) PTM_DL_PACK(256) PTM_DL_PACK(512) PTM_DL_PACK(1024)
+    default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  }
+#undef PTM_DL_PACK
+  HIPCHK(hipGetLastError());
+  if (!xrest) {
+    const size_t tot = (size_t)n * D;
+    hipLaunchKernelGGL(devlike_fill_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, n, D, (const int32_t*)e->dl_count, e->dl_x);
+    HIPCHK(hipGetLastError());
+  }
+  e->dfn(e->dfn_user, (void*)e->stream, n, D, e->dl_x, e->dl_count, e->dl_ll);
+  hipLaunchKernelGGL(devlike_scatter_kernel, dim3(1), dim3(DL_SCATTER_THREADS), 0, e->stream, D, (const int32_t*)e->dl_count, (const int*)e->dl_rows,
+                     (const double*)e->dl_ll, dst, gate_out, lprior, (const double*)e->dl_x, best ? e->dl_best : nullptr);
+  HIPCHK(hipGetLastError());
+  return PTM_OK;
+}
+
+// the best posterior seen: none yet (-inf, the zero state: bayes_likelihood::reset)
+static int devlike_reset_best(ptm_engine* e) {
+  if (!e->dl_best) return PTM_OK;
+  std::vector<double> b((size_t)e->D + 1, 0.0);
+  b[0] = -__builtin_inf();
+  return upload(e->dl_best, b.data(), b.size(), e->stream);
+}
+
+extern "C" int ptm_set_target_device(ptm_engine* e, ptm_loglike_device_fn fn, void* user, double* x_batch_dev, double* llike_batch_dev) {
+  if (!e || !fn) return fail(PTM_ERR_INVALID, "null argument");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_set_target_device");
+  if (e->prior_cb) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior with a device likelihood is not built (ptm_set_prior_callback)");
+  if (e->pcb) return fail(PTM_ERR_UNSUPPORTED, "host-side proposals with a device likelihood are not built (ptm_set_proposal_callback)");
+  if (e->nloc != e->Nt) return fail(PTM_ERR_UNSUPPORTED, "a device likelihood on a rung shard is not built: split such a population by walkers");
+  const size_t Nc = e->Nc, D = e->D, DP = e->DP;
+  int rc;
+  if (!e->dl_count &&
+      ((rc = dalloc(&e->dl_count, 1)) || (rc = dalloc(&e->dl_rows, Nc)) || (rc = dalloc(&e->dl_chunks, (Nc + DL_CHUNK - 1) / DL_CHUNK)) ||
+       (rc = dalloc(&e->dl_xprop, Nc * DP)) || (rc = dalloc(&e->dl_gate, Nc)) || (rc = dalloc(&e->dl_lprior_new, Nc)) ||
+       (rc = dalloc(&e->dl_llike_new, Nc)) || (rc = dalloc(&e->dl_best, D + 1))))
+    return rc;
+  // the batch buffers: the caller's, or the engine's own (kept across calls)
+  if (x_batch_dev) {
+    if (e->dl_own_x && e->dl_x) { HIPCHK(hipStreamSynchronize(e->stream)); (void)hipFree(e->dl_x); }
+    e->dl_x = x_batch_dev; e->dl_own_x = false;
+  } else if (!e->dl_own_x) {
+    e->dl_x = nullptr;
+    if ((rc = dalloc(&e->dl_x, Nc * D))) return rc;
+    e->dl_own_x = true;
+  }
+  if (llike_batch_dev) {
+    if (e->dl_own_ll && e->dl_ll) { HIPCHK(hipStreamSynchronize(e->stream)); (void)hipFree(e->dl_ll); }
+    e->dl_ll = llike_batch_dev; e->dl_own_ll = false;
+  } else if (!e->dl_own_ll) {
+    e->dl_ll = nullptr;
+    if ((rc = dalloc(&e->dl_ll, Nc))) return rc;
+    e->dl_own_ll = true;
+  }
+  HIPCHK(hipMemsetAsync(e->dl_gate, 0, Nc, e->stream));
+  if ((rc = devlike_reset_best(e))) return rc;
+  e->dfn = fn; e->dfn_user = user;
+  e->cb = nullptr;   // (the last target setter wins)
+  e->have_target = 1;
+  return PTM_OK;
+}
+
+extern "C" int ptm_target_device_rows(ptm_engine* e) {
+  if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  return e->Nc;
+}
+
+extern "C" int ptm_get_best_evaluated(ptm_engine* e, double* lpost, double* x) {
+  if (!e || !lpost) return fail(PTM_ERR_INVALID, "null argument");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_get_best_evaluated");
+  if (!e->dl_best) return fail(PTM_ERR_INVALID, "no device likelihood set (ptm_set_target_device)");
+  std::vector<double> b((size_t)e->D + 1);
+  HIPCHK(hipMemcpyAsync(b.data(), e->dl_best, b.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *lpost = b[0];
+  if (x) memcpy(x, b.data() + 1, (size_t)e->D * 8);
+  return PTM_OK;
+}
+
+// the device likelihood of ptm_debug_evaluate's rows (natural order, enforced), in batches of the engine's n_rows
+static int devlike_debug(ptm_engine* e, const double* X, int n, double* llike) {
+  const size_t Nc = e->Nc, D = e->D;
+  std::vector<double> rows(Nc * D);
+  for (size_t k0 = 0; k0 < (size_t)n; k0 += Nc) {
+    const size_t m = std::min(Nc, (size_t)n - k0);
+    for (size_t k = 0; k < Nc; ++k) memcpy(&rows[k * D], X + (k0 + (k < m ? k : 0)) * D, D * 8);   // (rows past the count: row 0)
+    const int32_t cnt = (int32_t)m;
+    HIPCHK(hipMemcpyAsync(e->dl_x, rows.data(), Nc * D * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->dl_count, &cnt, 4, hipMemcpyHostToDevice, e->stream));
+    e->dfn(e->dfn_user, (void*)e->stream, (int)Nc, (int)D, e->dl_x, e->dl_count, e->dl_ll);
+    HIPCHK(hipMemcpyAsync(llike + k0, e->dl_ll, m * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (rows and cnt are reused)
+  }
+  return PTM_OK;
+}
+
+// a shard's exchange phases and partial sweeps: not with a device likelihood
+#define NO_DEVLIKE(e, name) do { if ((e) && (e)->dfn) return fail(PTM_ERR_UNSUPPORTED, name " with a device likelihood is not built (rung-sharded steps)"); } while (0)
+
 static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = true) {
   Dev p = make_dev(e);
   if (nr < 0) nr = e->nloc - rung0;
   if (rung0 < 0 || nr < 0 || rung0 + nr > e->nloc) return fail(PTM_ERR_INVALID, "rung range out of the shard");
   p.c_begin = rung0 * e->W; p.c_end = (rung0 + nr) * e->W;
-  if ((e->cb || e->pcb) && (rung0 != 0 || nr != e->nloc)) return fail(PTM_ERR_UNSUPPORTED, "partial sweeps with a host-callback likelihood or host-side proposals are not built");
+  if ((user_like(e) || e->pcb) && (rung0 != 0 || nr != e->nloc)) return fail(PTM_ERR_UNSUPPORTED, "partial sweeps with a user likelihood (host or device) or host-side proposals are not built");
   auto close_step = [&]() {
     e->step += 1; e->touched = false;
     if (e->compact_step) { e->nhist_pending += 1; e->compact_step = false; }
@@ -1220,7 +1356,15 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     HIPCHK(copy_unless_shared(e->hvalid, e->h_valid.data(), Nc, hipMemcpyHostToDevice, e->stream));
     p.xprop = e->xprop; p.lprior_new = e->lprior_new; p.gate = e->gate; p.llike_new = e->llike_new;
   }
-  if (!e->cb) {
+  if (e->dfn) {
+    // device likelihood: propose pass -> pack -> the user's work -> scatter (+ best) -> accept pass, all queued on the stream
+    p.xprop = e->dl_xprop; p.lprior_new = e->dl_lprior_new; p.gate = e->dl_gate; p.llike_new = e->dl_llike_new;
+    p.mode = 1;
+    HIPCHK(launch(p));
+    { const int rc = devlike_eval(e, e->dl_gate, 2, 2, e->dl_xprop, e->x, e->dl_llike_new, nullptr, e->dl_lprior_new, true); if (rc) return rc; }
+    p.mode = 2;
+    HIPCHK(launch(p));
+  } else if (!e->cb) {
     HIPCHK(launch(p));
   } else {
     // host-callback likelihood: propose kernel -> user function on the gated proposals -> accept kernel
@@ -1472,7 +1616,12 @@ extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llik
   int rc;
   if ((rc = upload(e->x, rows.data(), Nc * DP, e->stream))) return rc;
   if (llike && (rc = upload(e->ll, llike, Nc, e->stream))) return rc;
-  if ((rc = run_eval(e, (int)Nc, e->x, nullptr, e->lp, e->ll, (llike || e->cb) ? 0 : 1))) return rc;
+  if ((rc = run_eval(e, (int)Nc, e->x, nullptr, e->lp, e->ll, (llike || user_like(e)) ? 0 : 1))) return rc;
+  if (e->dfn) {
+    // the device likelihood evaluates the (enforced) start states; the best posterior starts over with them
+    if ((rc = devlike_reset_best(e))) return rc;
+    if (!llike && (rc = devlike_eval(e, nullptr, 0, 0, e->x, e->x, e->ll, nullptr, e->lp, true))) return rc;
+  }
   if (e->cb && !llike) {
     // MH_chain::add_state(s) with the 999 sentinel: the likelihood plug-in evaluates the (enforced) start states (chain.cc:925)
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -1542,8 +1691,25 @@ extern "C" int ptm_init_from_prior_k(ptm_engine* e, int kdraw) {
   p.init_base = (uint64_t)kdraw << 17;   // attempts of draw k count from k * 2^17 (a draw gives up after 100000 < 2^17 attempts)
   HIPCHK(hipMemsetAsync(e->err + 1, 0, 4, e->stream));
   int rc;
-  if (!e->cb) {
+  if (e->dfn && (rc = devlike_reset_best(e))) return rc;
+  if (!user_like(e)) {
     if ((rc = launch_init(e, p, -1, nullptr))) return rc;
+  } else if (e->dfn) {
+    // the redraw loop with the device likelihood: one attempt per launch for the chains still pending (dl_gate), the device's
+    // verdicts (dl_gate 0: draw again, 2: done), the pending count looked at once per attempt
+    const size_t Nc = e->Nc;
+    HIPCHK(hipMemsetAsync(e->dl_gate, 0, Nc, e->stream));
+    std::vector<unsigned char> hg(Nc);
+    size_t left = Nc;
+    for (long long a = 0; left && a < 100000; ++a) {
+      if ((rc = launch_init(e, p, a, e->dl_gate))) return rc;
+      if ((rc = devlike_eval(e, e->dl_gate, 3, 1, e->x, nullptr, e->dl_llike_new, e->dl_gate, e->lp, true))) return rc;
+      HIPCHK(hipMemcpyAsync(hg.data(), e->dl_gate, Nc, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+      left = (size_t)std::count_if(hg.begin(), hg.end(), [](unsigned char g) { return g != 2; });
+    }
+    if (left) return fail(PTM_ERR_INVALID, "could not draw a valid start state from the prior for some chain");
+    HIPCHK(hipMemcpyAsync(e->ll, e->dl_llike_new, Nc * 8, hipMemcpyDeviceToDevice, e->stream));
   } else {
     // MH_chain::initialize's redraw loop (chain.cc:856-869) with the plug-in likelihood on the host: one attempt per
     // launch for the chains still pending; `gate` doubles as the pending flag array
@@ -1602,7 +1768,7 @@ extern "C" int ptm_draw_prior_rows(ptm_engine* e, int k_begin, int n, double* x_
   size_t G = per ? (size_t)(256u << 20) / per : 1;
   if (G < 1) G = 1;
   if (G > (size_t)n) G = (size_t)n;
-  if (e->cb) G = 1;
+  if (user_like(e)) G = 1;
   double *xs = nullptr, *ls = nullptr, *ps = nullptr;
   int rc = PTM_OK;
   if ((rc = dalloc(&xs, G * Nc * DP)) || (rc = dalloc(&ls, G * Nc)) || (rc = dalloc(&ps, G * Nc))) { hipFree(xs); hipFree(ls); hipFree(ps); return rc; }
@@ -1616,8 +1782,22 @@ extern "C" int ptm_draw_prior_rows(ptm_engine* e, int k_begin, int n, double* x_
       Dev p = make_dev(e);
       p.init_base = (uint64_t)(k_begin + k0 + j) << 17;
       double *xj = xs + (size_t)j * Nc * DP, *lj = ls + (size_t)j * Nc, *pj = ps + (size_t)j * Nc;
-      if (!e->cb) {
+      if (!user_like(e)) {
         if ((rc = launch_init(e, p, -1, nullptr, xj, lj, pj))) return done(rc);
+      } else if (e->dfn) {
+        // the redraw loop of ptm_init_from_prior_k with the device likelihood, on the staging row
+        PTM_DRAW_CHK(hipMemsetAsync(e->dl_gate, 0, Nc, e->stream));
+        std::vector<unsigned char> hg(Nc);
+        size_t left = Nc;
+        for (long long a = 0; left && a < 100000; ++a) {
+          if ((rc = launch_init(e, p, a, e->dl_gate, xj, lj, pj))) return done(rc);
+          if ((rc = devlike_eval(e, e->dl_gate, 3, 1, xj, nullptr, e->dl_llike_new, e->dl_gate, pj, true))) return done(rc);
+          PTM_DRAW_CHK(hipMemcpyAsync(hg.data(), e->dl_gate, Nc, hipMemcpyDeviceToHost, e->stream));
+          PTM_DRAW_CHK(hipStreamSynchronize(e->stream));
+          left = (size_t)std::count_if(hg.begin(), hg.end(), [](unsigned char g) { return g != 2; });
+        }
+        if (left) return done(fail(PTM_ERR_INVALID, "could not draw a valid state from the prior for some chain"));
+        PTM_DRAW_CHK(hipMemcpyAsync(lj, e->dl_llike_new, Nc * 8, hipMemcpyDeviceToDevice, e->stream));
       } else {
         // the redraw loop of ptm_init_from_prior_k (chain.cc:856-869) on the staging row
         PTM_DRAW_CHK(hipMemsetAsync(e->gate, 0, Nc, e->stream));
@@ -1682,7 +1862,7 @@ extern "C" int ptm_sweep(ptm_engine* e, int n) {
 // two-launch path.  Returns the steps taken (0: not this engine's case), or a negative status.
 static int fused_steps(ptm_engine* e, int n) {
   static const bool fused_ok = [] { const char* v = getenv("PTM_FUSED"); return !(v && *v == '0'); }();
-  if (!fused_ok || e->DP > 16 || (long long)e->Nt * e->DP > 256 || e->cb || e->pcb || e->cfg.time_kernels) return 0;
+  if (!fused_ok || e->DP > 16 || (long long)e->Nt * e->DP > 256 || user_like(e) || e->pcb || e->cfg.time_kernels) return 0;
   if (e->evolve_rate > 0 && (e->W > 64 || e->evolve_cut >= 0)) return 0;   // (the new temperatures' chain-indexed image is then a separate launch)
   const bool evb = e->evolve_rate > 0 && e->beta_add;
   const size_t dlds = decide_lds_bytes(e->Nt, e->ms, e->Nt, e->evolve_rate > 0, evb);
@@ -1739,7 +1919,7 @@ static bool ladder_applies(ptm_engine* e, long long* grid_out = nullptr, size_t*
   // mixtures, history and MAP tracking have their builds: ladder_flavour); ANY population whose grid is resident at once (below): where
   // it fits, a step costs this kernel its ~6 us of latency whatever the walkers' number (64 walkers x 64 rungs of 12 dimensions with the
   // sampler's defaults: 14 us against 40 on two launches)
-  if (e->cb || e->prior_cb || e->pcb) return false;
+  if (user_like(e) || e->prior_cb || e->pcb) return false;
   const int R = 256 / e->DP, NB = (e->Nt + R - 1) / R;
   const long long grid = (long long)e->W * NB;
   const bool diag = e->prop_kind == PTM_PROP_DIAG;
@@ -1980,6 +2160,7 @@ extern "C" int ptm_exchange_decide(ptm_engine* e, const void* ll_below, const vo
                                    void* send_down) {
   SETTLE(e);
   NO_BATCH(e, "ptm_exchange_decide");
+  NO_DEVLIKE(e, "ptm_exchange_decide");
   int rc = ready(e);
   if (rc) return rc;
   if (e->evolve_rate > 0 && e->nloc != e->Nt)
@@ -1997,6 +2178,7 @@ extern "C" int ptm_exchange_decide(ptm_engine* e, const void* ll_below, const vo
 extern "C" int ptm_exchange_decide_gathered(ptm_engine* e, const void* ll_all, const void* lp_all, void* send_up, void* send_down) {
   SETTLE(e);
   NO_BATCH(e, "ptm_exchange_decide_gathered");
+  NO_DEVLIKE(e, "ptm_exchange_decide_gathered");
   int rc = ready(e);
   if (rc) return rc;
   if (!ll_all) return fail(PTM_ERR_INVALID, "null argument");
@@ -2046,6 +2228,7 @@ extern "C" int ptm_exchange_redo_count(ptm_engine* e, int* n) {
 extern "C" int ptm_exchange_redo(ptm_engine* e, const void* ll_all, const void* lp_all, void* send_up, void* send_down) {
   SETTLE(e);
   NO_BATCH(e, "ptm_exchange_redo");
+  NO_DEVLIKE(e, "ptm_exchange_redo");
   int rc = ready(e);
   if (rc) return rc;
   if (!e->redo_flag) return fail(PTM_ERR_INVALID, "ptm_set_shard_map first");
@@ -2098,6 +2281,7 @@ extern "C" int ptm_dev_copy(void* dst, const void* src, size_t bytes) {
 extern "C" int ptm_exchange_install(ptm_engine* e, const void* recv_below, const void* recv_above) {
   SETTLE(e);
   NO_BATCH(e, "ptm_exchange_install");
+  NO_DEVLIKE(e, "ptm_exchange_install");
   int rc = ready(e);
   if (rc) return rc;
   const bool first = e->r0 == 0, last = e->r0 + e->nloc == e->Nt;
@@ -2107,6 +2291,7 @@ extern "C" int ptm_exchange_install(ptm_engine* e, const void* recv_below, const
 extern "C" int ptm_sweep_rungs(ptm_engine* e, int first_local_rung, int n_rungs, int closes_step) {
   SETTLE(e);
   NO_BATCH(e, "ptm_sweep_rungs");
+  NO_DEVLIKE(e, "ptm_sweep_rungs");
   int rc = ready(e);
   if (rc) return rc;
   return launch_sweep(e, first_local_rung, n_rungs, closes_step != 0);
@@ -2118,6 +2303,7 @@ extern "C" int ptm_exchange_row_capacity(ptm_engine* e) { return e ? e->row_cap 
 extern "C" int ptm_exchange_finish_and_sweep(ptm_engine* e, const void* recv_below, const void* recv_above) {
   SETTLE(e);
   NO_BATCH(e, "ptm_exchange_finish_and_sweep");
+  NO_DEVLIKE(e, "ptm_exchange_finish_and_sweep");
   int rc = ready(e);
   if (rc) return rc;
   const bool first = e->r0 == 0, last = e->r0 + e->nloc == e->Nt;
@@ -2286,7 +2472,7 @@ extern "C" int ptm_shard_step(ptm_engine* e, int n) {
   int rc = ready(e);
   if (rc) return rc;
   if (!e->shard) return fail(PTM_ERR_INVALID, "ptm_shard_init first");
-  if (e->cb || e->pcb) return fail(PTM_ERR_UNSUPPORTED, "sharded steps with a host-callback likelihood or host-side proposals are not built");
+  if (user_like(e) || e->pcb) return fail(PTM_ERR_UNSUPPORTED, "sharded steps with a user likelihood (host or device) or host-side proposals are not built");
   ShardComm* s = e->shard;
   if (e->evolve_rate > 0) {
     // Evolving ladders: every shard replays the whole ladder's trials from the whole ladder's llikes (and lpriors, with a
@@ -2697,6 +2883,7 @@ extern "C" const char* ptm_sweep_kernel_name(ptm_engine* e) {
     snprintf(b, sizeof b, "sweep_lanes_kernel<%d, %d, %s>", e->DP, s.kind, s.plain ? "false" : "true");
   else snprintf(b, sizeof b, "sweep_kernel<%d, %d, %s, %s>", e->DP, s.kind, s.uni ? "true" : "false", s.simple ? "true" : "false");
   e->kname = b;
+  if (e->dfn) e->kname += " + device likelihood";   // (propose pass, pack, the user's work, scatter, accept pass)
   return e->kname.c_str();
 }
 
@@ -2704,7 +2891,7 @@ extern "C" const char* ptm_step_kernel_name(ptm_engine* e) {
   if (!e) return "";
   static thread_local std::string name;
   char b[160];
-  const bool fused = e->DP <= 16 && (long long)e->Nt * e->DP <= 256 && !e->cb && !e->pcb && !e->cfg.time_kernels && !(getenv("PTM_FUSED") && *getenv("PTM_FUSED") == '0') &&
+  const bool fused = e->DP <= 16 && (long long)e->Nt * e->DP <= 256 && !user_like(e) && !e->pcb && !e->cfg.time_kernels && !(getenv("PTM_FUSED") && *getenv("PTM_FUSED") == '0') &&
                      !(e->evolve_rate > 0 && (e->W > 64 || e->evolve_cut >= 0));
   if (e->nloc != e->Nt) snprintf(b, sizeof b, "(sharded: ptm_exchange_* / ptm_shard_step) decide_kernel + %s", ptm_sweep_kernel_name(e));
   else if (ladder_applies(e)) snprintf(b, sizeof b, "ladder_persistent_kernel<%d, %d, %d>", e->DP, e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : KIND_DENSE, ladder_flavour(e));
@@ -2793,14 +2980,19 @@ extern "C" int ptm_debug_evaluate(ptm_engine* e, const double* X, int n, int32_t
   HIPCHK(hipMalloc((void**)&dll, (size_t)n * 8));
   HIPCHK(hipMalloc((void**)&dv, (size_t)n * 4));
   HIPCHK(hipMemcpy(dx, rows.data(), (size_t)n * DP * 8, hipMemcpyHostToDevice));
-  int rc = run_eval(e, n, dx, dv, dlp, dll, (e->have_target && !e->cb) ? 1 : 0);
+  int rc = run_eval(e, n, dx, dv, dlp, dll, (e->have_target && !user_like(e)) ? 1 : 0);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(rows.data(), dx, (size_t)n * DP * 8, hipMemcpyDeviceToHost));
   if (Xe) unpad_rows(rows, (size_t)n, D, DP, Xe);
   if (valid) HIPCHK(hipMemcpy(valid, dv, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (lprior) HIPCHK(hipMemcpy(lprior, dlp, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (llike && e->have_target && !e->cb) HIPCHK(hipMemcpy(llike, dll, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (llike && e->have_target && !user_like(e)) HIPCHK(hipMemcpy(llike, dll, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (llike && e->dfn) {   // the device likelihood's llikes of the enforced states
+    std::vector<double> xe((size_t)n * D);
+    unpad_rows(rows, (size_t)n, D, DP, xe.data());
+    if ((rc = devlike_debug(e, xe.data(), n, llike))) return rc;
+  }
   (void)hipFree(dx); (void)hipFree(dlp); (void)hipFree(dll); (void)hipFree(dv);
   return PTM_OK;
 }

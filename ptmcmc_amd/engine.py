@@ -30,6 +30,7 @@ EXPORTS = [
     "ptm_timer_start", "ptm_timer_stop", "ptm_get_kernel_times", "ptm_calibrate", "ptm_get_counter_sums", "ptm_get_ladder_stats", "ptm_sweep_kernel_name", "ptm_step_kernel_name", "ptm_debug_eval",
     "ptm_debug_philox", "ptm_debug_boxmuller", "ptm_debug_sqrt_scan", "ptm_debug_evaluate",
     "ptm_dev_alloc", "ptm_dev_free", "ptm_dev_copy",
+    "ptm_set_target_device", "ptm_target_device_rows", "ptm_get_best_evaluated",
 ]
 
 
@@ -64,6 +65,8 @@ LOGLIKE_BATCH_FN = C.CFUNCTYPE(None, C.c_void_p, _dp, C.c_int, C.c_int, _dp)
 # ptm_propose_batch_fn / ptm_proposal_result_fn (include/ptm_engine.h)
 PROPOSE_BATCH_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, _dp, _i32p, _i32p, C.c_uint64, _dp, _dp, _i32p, _i32p)
 PROPOSAL_RESULT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, _i32p, _i32p, _i32p)
+# ptm_loglike_device_fn (include/ptm_engine.h): user, stream, n_rows, dim, X_dev, count_dev, out_llike_dev (device pointers)
+LOGLIKE_DEVICE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 TORCH_LOADED_FIRST = None
@@ -160,8 +163,19 @@ def load():
                               C.POINTER(C.c_int64)]
     L.ptm_debug_sqrt_scan.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
     L.ptm_debug_evaluate.argtypes = [C.c_void_p, _dp, C.c_int, _i32p, _dp, _dp, _dp]
+    if hasattr(L, "ptm_set_target_device"):
+        L.ptm_set_target_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptm_target_device_rows.argtypes = [C.c_void_p]
+        L.ptm_get_best_evaluated.argtypes = [C.c_void_p, _dp, _dp]
     _lib = L
     return L
+
+
+def _wrap_int32_device(torch, ptr, dev):
+    """a 1-element int32 torch tensor over a device pointer (the engine's count), through the CUDA array interface"""
+    class _Arr:
+        __cuda_array_interface__ = {"shape": (1,), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(_Arr(), device=dev)
 
 
 def _chk(rc):
@@ -335,6 +349,56 @@ class Engine:
         cb = LOGLIKE_BATCH_FN(tramp)
         self._keep.append(cb)
         _chk(self.L.ptm_set_target_callback(self.h, C.cast(cb, C.c_void_p), None))
+
+    def set_target_device(self, fn):
+        """user likelihood on the DEVICE (ptm_set_target_device): fn(X, count, out) with torch views -- X (n_rows, D) float64,
+        count a 1-element int32 tensor (rows [0, count) are the proposals to evaluate, the rest in-support states), out (n_rows,)
+        float64 to fill.  It runs once per sweep with the engine's stream current and must only ENQUEUE its work (no .item(), no
+        copy to the host): step(n) queues n steps and returns.  Needs torch imported before the engine library (one HIP runtime)."""
+        import torch
+        if not TORCH_LOADED_FIRST:
+            raise PtmError("set_target_device needs torch imported BEFORE the engine library was loaded (one HIP runtime per process: "
+                           "see ptmcmc_amd.parallel.EngineShard)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n, D = self.Nc, self.D
+        X = torch.zeros((n, D), dtype=torch.float64, device=dev)
+        out = torch.zeros(n, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        state = {}
+
+        def tramp(user, stream, n_rows, dim, xp, cp, op):
+            cnt = state.get(cp)
+            if cnt is None:   # the engine's count buffer, wrapped once (torch has no public from-pointer constructor: a 1-element copy)
+                cnt = state[cp] = _wrap_int32_device(torch, cp, dev)
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                fn(X, cnt, out)
+        cb = LOGLIKE_DEVICE_FN(tramp)
+        self._keep += [cb, X, out, state]
+        _chk(self.L.ptm_set_target_device(self.h, C.cast(cb, C.c_void_p), None, C.c_void_p(X.data_ptr()), C.c_void_p(out.data_ptr())))
+
+    def set_target_device_c(self, fnptr, user=None, x_batch_dev=None, llike_batch_dev=None):
+        """user likelihood on the device through a raw C function pointer of the ptm_loglike_device_fn shape (e.g. from a hipcc-built
+        .so: ctypes.cast(lib.my_launcher, ctypes.c_void_p)); batch buffers: device pointers, or None for the engine's own"""
+        p = fnptr.value if isinstance(fnptr, C.c_void_p) else (C.cast(fnptr, C.c_void_p).value if isinstance(fnptr, C._CFuncPtr) else int(fnptr))
+        self._keep.append(fnptr)
+        _chk(self.L.ptm_set_target_device(self.h, C.c_void_p(p), C.c_void_p(user) if user is not None else None,
+                                          None if x_batch_dev is None else C.c_void_p(x_batch_dev),
+                                          None if llike_batch_dev is None else C.c_void_p(llike_batch_dev)))
+
+    @property
+    def target_device_rows(self):
+        """n_rows of the device likelihood: the local chain count (ptm_target_device_rows)"""
+        r = self.L.ptm_target_device_rows(self.h)
+        if r < 0:
+            _chk(r)
+        return r
+
+    def best_evaluated(self):
+        """(best lprior + llike the device likelihood evaluated since the last state set-up, its state [D]) (ptm_get_best_evaluated)"""
+        lp = C.c_double()
+        x = np.empty(self.D)
+        _chk(self.L.ptm_get_best_evaluated(self.h, C.byref(lp), x.ctypes.data_as(_dp)))
+        return lp.value, x
 
     def set_prior_callback(self, fn, batched=False):
         """a prior evaluated on the host (ptm_set_prior_callback): the C shape of probability_function::evaluate_log

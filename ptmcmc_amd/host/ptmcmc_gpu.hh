@@ -56,6 +56,22 @@ inline void ptm_check(int rc, const char* what) {
   }
 }
 
+// what must happen to an engine of the facade before it is destroyed: a device likelihood keeps the engine's best evaluated posterior
+// (the engine holds it on the device) -- the hooks are registered by device_likelihood and removed by its destructor
+inline std::map<ptm_engine*, std::function<void(ptm_engine*)>>& engine_release_hooks() { static std::map<ptm_engine*, std::function<void(ptm_engine*)>> m; return m; }
+inline std::mutex& engine_hooks_mutex() { static std::mutex m; return m; }
+inline void engine_gone(ptm_engine* e) {
+  std::function<void(ptm_engine*)> f;
+  {
+    std::lock_guard<std::mutex> lk(engine_hooks_mutex());
+    auto it = engine_release_hooks().find(e);
+    if (it == engine_release_hooks().end()) return;
+    f = it->second;
+    engine_release_hooks().erase(it);
+  }
+  f(e);
+}
+
 // ---- states.hh --------------------------------------------------------------------------------------------------
 class boundary {  // states.hh:29-48
   int lowertype, uppertype;
@@ -1786,6 +1802,77 @@ class bayes_likelihood : public probability_function, public Optioned {  // baye
  public:
 };
 
+// A likelihood evaluated ON THE DEVICE (ptm_set_target_device): the engine calls evaluate_log_device once per sweep on its own stream
+// with the batch of proposals in device memory (X_dev [n_rows][dim], rows [0, *count_dev) to evaluate, the rest in-support states);
+// it enqueues its work on `stream` (a hipStream_t) and returns.  The host evaluate_log (register_evaluate_log) stays required: with a
+// prior that is not a per-dimension product or with host-side proposals the ladder keeps the host path, and PTM_DEVICE_LIKE=0 in the
+// environment forces it.  bestPost / bestState: the best of what the host path saw and of every engine this likelihood served on the
+// device (replicas, walker ranges; ptm_get_best_evaluated -- an engine's is kept when the engine goes).
+class device_likelihood : public bayes_likelihood {
+ protected:
+  std::vector<ptm_engine*> dev_engines;   // live engines that evaluate through this likelihood
+  double dev_best_post = -INFINITY;       // the best of the engines already gone, and its state
+  std::vector<double> dev_best_x;
+  std::mutex dev_mutex;
+
+ public:
+  ~device_likelihood() {
+    std::lock_guard<std::mutex> lk(engine_hooks_mutex());
+    for (ptm_engine* e : dev_engines) engine_release_hooks().erase(e);
+  }
+  virtual void evaluate_log_device(void* stream, int n_rows, int dim, const double* X_dev, const int32_t* count_dev, double* out_dev) = 0;
+  static void device_trampoline(void* self, void* stream, int n_rows, int dim, const double* X_dev, const int32_t* count_dev, double* out_dev) {
+    ((device_likelihood*)self)->evaluate_log_device(stream, n_rows, dim, X_dev, count_dev, out_dev);
+  }
+  bool describe_device_target(ptm_engine* e) override {
+    const char* v = getenv("PTM_DEVICE_LIKE");
+    if (v && *v == '0') return false;
+    ptm_check(ptm_set_target_device(e, &device_likelihood::device_trampoline, this, nullptr, nullptr), "set_target_device");
+    {
+      std::lock_guard<std::mutex> lk(dev_mutex);
+      dev_engines.push_back(e);
+    }
+    std::lock_guard<std::mutex> lk(engine_hooks_mutex());
+    engine_release_hooks()[e] = [this](ptm_engine* g) { release(g); };
+    return true;
+  }
+  double bestPost() override {
+    std::vector<double> x;
+    return best_of_devices(x);
+  }
+  state bestState() override {
+    std::vector<double> x;
+    best_of_devices(x);
+    return x.empty() ? best : state::from_engine(getObjectStateSpace(), x.data(), (int)x.size());
+  }
+
+ private:
+  // an engine about to be destroyed: keep its best
+  void release(ptm_engine* e) {
+    std::vector<double> xe((size_t)nativeSpace.size() + 1);
+    double lp = -INFINITY;
+    const bool ok = ptm_get_best_evaluated(e, &lp, xe.data()) == PTM_OK;
+    std::lock_guard<std::mutex> lk(dev_mutex);
+    if (ok && lp > dev_best_post) { dev_best_post = lp; dev_best_x.assign(xe.begin(), xe.begin() + nativeSpace.size()); }
+    dev_engines.erase(std::remove(dev_engines.begin(), dev_engines.end(), e), dev_engines.end());
+  }
+  // the host path's best, replaced by a strictly greater one of the engines (x: that state; empty if the host's stands)
+  double best_of_devices(std::vector<double>& x) {
+    double b = best_post;
+    x.clear();
+    std::lock_guard<std::mutex> lk(dev_mutex);
+    if (dev_best_post > b) { b = dev_best_post; x = dev_best_x; }
+    const int D = (int)nativeSpace.size();
+    std::vector<double> xe(D > 0 ? D : 1);
+    for (ptm_engine* e : dev_engines) {
+      double lp = -INFINITY;
+      if (ptm_get_best_evaluated(e, &lp, xe.data()) != PTM_OK) continue;
+      if (lp > b) { b = lp; x.assign(xe.begin(), xe.begin() + D); }
+    }
+    return b;
+  }
+};
+
 // correlated Gaussian target evaluated ON the device: like0 - 1/2 (x-mean)^T P (x-mean) (cython/exampleGaussian.py:46-109)
 class gaussian_likelihood : public bayes_likelihood {
   std::vector<double> mean, precision;
@@ -2037,7 +2124,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     for (int i = 1; i < Ntemps; i++) temps[i] = temps[i - 1] * tratio;
   }
   ~parallel_tempering_chains() {
-    if (eng) ptm_engine_destroy(eng);
+    if (eng) { engine_gone(eng); ptm_engine_destroy(eng); }
     for (auto p : props) delete p;
   }
   // Keep what MH_chain::add_state saves (every add_every_N-th state of every rung, chain.cc:935-946) on the device, in a
@@ -2264,7 +2351,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
 
  private:
   void build_engine(bool host) {
-    if (eng) { ptm_engine_destroy(eng); eng = nullptr; }
+    if (eng) { engine_gone(eng); ptm_engine_destroy(eng); eng = nullptr; }
     bayes_likelihood* log_likelihood = init_like;
     const sampleable_probability_function* log_prior = init_prior;
     sp = log_prior->get_space();
@@ -2297,7 +2384,9 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     prior_on_host = !log_prior->describe(types, centers, halfwidths);
     if (!prior_on_host) {
       ptm_check(ptm_set_prior(eng, types.data(), centers.data(), halfwidths.data()), "set_prior");
-      if (!log_likelihood->describe_device_target(eng))
+      // (a device likelihood cannot serve host-side proposals, whose step waits on the host anyway: its host evaluate_log does)
+      const bool skip_device = host && dynamic_cast<device_likelihood*>(log_likelihood) != nullptr;
+      if (skip_device || !log_likelihood->describe_device_target(eng))
         ptm_check(ptm_set_target_callback(eng, &bayes_likelihood::batch_trampoline, log_likelihood), "set_target_callback");
     } else {
       // a prior that is not a per-dimension product: evaluated on the host between the propose and the accept kernel, and so
