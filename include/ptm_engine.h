@@ -184,9 +184,44 @@ int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double* factor, d
  * scales, oneDfracs.  offset = scale_k * (factor z); last_type = k + 10 * (1 if the move was one-dimensional).
  * K = 0 removes the mixture. */
 int ptm_set_proposal_mixture(ptm_engine* e, int K, const double* cum_shares, const double* scales, const double* one_d_fracs);
+/* ADAPTIVE proposal set: a proposal_distribution_set whose shares move with the members' outcomes (adapt_rate,
+ * proposal_distribution.cc:131-166) -- the sampler's recipe with --prop_adapt_rate (ptmcmc.cc:60-143): the top set {members ...}
+ * of which ONE member (`nested`) may itself be a set of K_inner Gaussians with its own rate.  Drawn and adapted on the device:
+ *   draw    a set of more than one member takes one uniform x and picks the first member that is ready with x < threshold
+ *           (differential evolution not ready yet: the next member); the top set's x is slot 3 of block 0 of the chain's
+ *           Metropolis stream, the nested set's slot 0 of block 0 of tag 3 (the same stream and step).  type = i + 10 t for
+ *           a top member i of type t, i + 10 (j + 10 t) for member j of the nested set.
+ *   update  after every Metropolis move of a rung the exchange phase left alone (rejections as invalid or by the prior cut
+ *           included), for a set of rate != 0: a member whose outcome repeats its last one has its weight multiplied by
+ *           1 - rate/4; its last outcome is stored and the set's outcome count goes up; from 10 x members outcomes on (the count
+ *           is never reset) the weights are renormalised and the thresholds rebuilt after EVERY outcome (reset_bins, Tpow = 0).
+ *           The outcome is then handed to the picked member: a picked nested set adapts the same way.
+ * Leaves [rung_count][K + K_inner]: top members 0..K-1, then the nested set's members; scale < 0 = differential evolution
+ * (ptm_set_proposal_de; top level only, at most one, not the last top member); the nested member's own top entry is not read.
+ * Initial state per LOCAL chain (chain c = r * n_walkers + w): weights and thresholds [Nc][K + K_inner] (thresholds non-decreasing,
+ * each set's last exactly 1: the engine derives none itself, so a host-side copy and the device start from the same bits),
+ * repeat bits [Nc][2] (bit i: member i's last outcome was an accept; top set, nested set) and outcome counts [Nc][2].
+ * Replaces the mixture of ptm_set_proposal_mixture; a later ptm_set_proposal_mixture (any K) switches adaptation off, a non-NULL
+ * ptm_set_proposal_callback takes over.  The state is per chain and is not part of ptm_restore: read it with
+ * ptm_get_proposal_adapt_state, put it back with ptm_set_proposal_adapt_state.  Every argument is checked before the current
+ * configuration is touched (PTM_ERR_INVALID: it keeps working); rung shards: PTM_ERR_UNSUPPORTED.  Steps of such an engine take
+ * the exchange kernel and the lanes or the general sweep kernel (never the matrix-core, fused small-ladder or persistent kernels: the
+ * persistent kernel is out of scope for adaptive sets). */
+typedef struct ptm_adaptive_set {
+  int K;              /* members of the top set, 1..8 */
+  int nested;         /* top member that is itself a set of K_inner Gaussians, or -1 */
+  int K_inner;        /* 0, or 1..8 when nested >= 0 */
+  double rate;        /* the top set's adapt_rate, in [0, 1) (0: its shares stay fixed) */
+  double rate_inner;  /* the nested set's, in [0, 1) */
+} ptm_adaptive_set;
+int ptm_set_proposal_adaptive(ptm_engine* e, const ptm_adaptive_set* set, const double* scales, const double* one_d_fracs, const double* weights,
+                              const double* thresholds, const int32_t* repeat_bits, const int32_t* outcomes);
+/* the per-chain state of the adaptive set, layouts as ptm_set_proposal_adaptive's initial state (queued inside ptm_batch_begin / _end) */
+int ptm_get_proposal_adapt_state(ptm_engine* e, double* weights, double* thresholds, int32_t* repeat_bits, int32_t* outcomes);
+int ptm_set_proposal_adapt_state(ptm_engine* e, const double* weights, const double* thresholds, const int32_t* repeat_bits, const int32_t* outcomes);
 
 /* Host-side proposals -- the "host fallback step" for everything that is not a Gaussian the device can draw itself
- * (differential evolution from the chain history, involutions, adaptive sets, user proposals with callbacks ...):
+ * (involutions, draws from the prior, temperature-dependent shares, user proposals with callbacks ...):
  * every sweep fetches the current states, calls `propose` once for all moving chains, and runs the rest of
  * MH_chain::step on the device.  `result` (may be NULL) is told the outcomes after the accept kernel.  Replaces the
  * proposals of ptm_set_proposals; propose == NULL goes back to them.  Whole-shard sweeps only (ptm_sweep, ptm_step,

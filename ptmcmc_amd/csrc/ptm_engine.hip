@@ -89,6 +89,12 @@ struct ptm_engine {
   int de_init_extra = 0;
   double *de_init = nullptr, *de_hast = nullptr;
   int* de_type = nullptr;
+  // adaptive proposal set (ptm_set_proposal_adaptive): the set's shape and rates; one device allocation each for the leaves
+  // [nloc][L][2], the per-chain doubles (weights | thresholds, [L][Nc] each) and ints (repeat bits | outcome counts, [2][Nc] each)
+  bool ada_on = false;
+  ptm_adaptive_set ada = {0, -1, 0, 0, 0};
+  double *ada_leaf = nullptr, *ada_dbl = nullptr;
+  int* ada_int = nullptr;
   // evolving ladders (ptm_set_evolve_temps): per-ladder inverse temperatures [W][Nt] and their chain-indexed image [Nc]
   double evolve_rate = 0, evolve_cut = -1;
   double *beta_w = nullptr, *betaC = nullptr, *beta_add = nullptr;
@@ -475,7 +481,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
                   e->err, e->nhist, e->swap_cnt, e->touch, e->swap_log, e->hist.x, e->hist.ll, e->hist.lp, e->hist.meta, e->map.lpost, e->map.ll, e->map.lp, e->map.x, e->blo,
                   e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
-                  e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
+                  e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
                   e->dl_lprior_new, e->dl_llike_new, e->dl_best};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -917,6 +923,19 @@ extern "C" int ptm_set_proposals(ptm_engine* e, int kind, const double* factors,
   return PTM_OK;
 }
 
+// the adaptive proposal set's device arrays go (ptm_set_proposal_mixture replaces it)
+static int ada_off(ptm_engine* e) {
+  e->ada_on = false;
+  if (!e->ada_leaf && !e->ada_dbl && !e->ada_int) return PTM_OK;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (e->ada_leaf) HIPCHK(hipFree(e->ada_leaf));
+  if (e->ada_dbl) HIPCHK(hipFree(e->ada_dbl));
+  if (e->ada_int) HIPCHK(hipFree(e->ada_int));
+  e->ada_leaf = e->ada_dbl = nullptr;
+  e->ada_int = nullptr;
+  return PTM_OK;
+}
+
 // A proposal_distribution_set of Gaussian members (proposal_distribution.cc:99-129) whose members are scalar multiples of
 // the rung's factor -- the sampler's default Gaussian recipe (six diagonal Gaussians a factor gauss_step_fac apart with
 // doubling shares, ptmcmc.cc:117-139).  Per local rung K members: cumulative shares (proposal_distribution_set's
@@ -928,6 +947,7 @@ extern "C" int ptm_set_proposal_mixture(ptm_engine* e, int K, const double* cum_
   if (K < 0 || K > 64) return fail(PTM_ERR_INVALID, "mixture size must be in 0..64");
   if (e->mix) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->mix)); e->mix = nullptr; }
   e->mix_K = 0;
+  { const int rc = ada_off(e); if (rc) return rc; }   // (a fixed mixture, or none, replaces an adaptive set)
   if (K == 0) return PTM_OK;
   if (!cum_shares || !scales || !one_d_fracs) return fail(PTM_ERR_INVALID, "null argument");
   const int nloc = e->nloc;
@@ -945,6 +965,142 @@ extern "C" int ptm_set_proposal_mixture(ptm_engine* e, int K, const double* cum_
   if ((rc = dalloc(&e->mix, t.size())) || (rc = upload(e->mix, t.data(), t.size(), e->stream))) return rc;
   e->mix_K = K;
   if (oned) e->any_oned = 1;
+  return PTM_OK;
+}
+
+// ---- adaptive proposal set (include/ptm_engine.h: ptm_set_proposal_adaptive) ------------------------------------------------
+// A per-chain state (host layout [Nc][L] and [Nc][2]) checked against the set's shape: finite non-negative weights with a positive sum per
+// set, thresholds non-decreasing in [0, 1] with each set's last exactly 1 (what reset_bins leaves), repeat bits of the set's members
+// only, outcome counts >= 0.  Nothing is touched.
+static int ada_check_state(const ptm_adaptive_set& a, size_t Nc, const double* w, const double* th, const int32_t* bits, const int32_t* cnt) {
+  if (!w || !th || !bits || !cnt) return fail(PTM_ERR_INVALID, "null argument");
+  const int L = a.K + a.K_inner;
+  for (size_t c = 0; c < Nc; ++c)
+    for (int b = 0; b < 2; ++b) {
+      const int first = b ? a.K : 0, n = b ? a.K_inner : a.K;
+      const int32_t bv = bits[c * 2 + b], cv = cnt[c * 2 + b];
+      if (bv < 0 || (n < 31 && bv >= (1 << n)) || cv < 0)
+        return fail(PTM_ERR_INVALID, "adaptive set: repeat bits name members of the set only and outcome counts are >= 0 (chain %zu)", c);
+      if (n == 0) continue;
+      double sum = 0.0, prev = 0.0;
+      for (int k = 0; k < n; ++k) {
+        const double wk = w[c * L + first + k], tk = th[c * L + first + k];
+        if (!std::isfinite(wk) || wk < 0) return fail(PTM_ERR_INVALID, "adaptive set: weights must be finite and >= 0 (chain %zu)", c);
+        if (!(tk >= prev && tk <= 1.0)) return fail(PTM_ERR_INVALID, "adaptive set: thresholds must not decrease and lie in [0, 1] (chain %zu)", c);
+        sum += wk;
+        prev = tk;
+      }
+      if (!(sum > 0)) return fail(PTM_ERR_INVALID, "adaptive set: the weights of a set must have a positive sum (chain %zu)", c);
+      if (prev != 1.0) return fail(PTM_ERR_INVALID, "adaptive set: the last threshold of a set must be exactly 1 (chain %zu)", c);
+    }
+  return PTM_OK;
+}
+// host layout -> the device's structure of arrays (or back)
+static void ada_to_soa(size_t Nc, int L, const double* w, const double* th, const int32_t* bits, const int32_t* cnt, std::vector<double>& dbl, std::vector<int>& in) {
+  dbl.assign(2 * (size_t)L * Nc, 0.0);
+  in.assign(4 * Nc, 0);
+  for (size_t c = 0; c < Nc; ++c) {
+    for (int k = 0; k < L; ++k) { dbl[(size_t)k * Nc + c] = w[c * L + k]; dbl[((size_t)L + k) * Nc + c] = th[c * L + k]; }
+    for (int b = 0; b < 2; ++b) { in[(size_t)b * Nc + c] = bits[c * 2 + b]; in[(size_t)(2 + b) * Nc + c] = cnt[c * 2 + b]; }
+  }
+}
+
+extern "C" int ptm_set_proposal_adaptive(ptm_engine* e, const ptm_adaptive_set* a, const double* scales, const double* one_d_fracs, const double* weights,
+                                         const double* thresholds, const int32_t* repeat_bits, const int32_t* outcomes) {
+  if (!e || !a || !scales || !one_d_fracs) return fail(PTM_ERR_INVALID, "null argument");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_set_proposal_adaptive");
+  // every check first: a refused call leaves the current proposals as they are
+  if (!e->have_prop) return fail(PTM_ERR_INVALID, "set the base proposals first (ptm_set_proposals)");
+  if (e->nloc != e->Nt)
+    return fail(PTM_ERR_UNSUPPORTED, "an adaptive proposal set on a rung shard is not built: split the population by walkers (walker_begin)");
+  if (a->K < 1 || a->K > 8) return fail(PTM_ERR_INVALID, "adaptive set: K must be in 1..8");
+  if (a->nested < -1 || a->nested >= a->K) return fail(PTM_ERR_INVALID, "adaptive set: nested must be -1 or a top member");
+  if (a->nested < 0 ? a->K_inner != 0 : (a->K_inner < 1 || a->K_inner > 8))
+    return fail(PTM_ERR_INVALID, "adaptive set: K_inner must be 1..8 with a nested set, 0 without");
+  if (!(a->rate >= 0 && a->rate < 1) || !(a->rate_inner >= 0 && a->rate_inner < 1)) return fail(PTM_ERR_INVALID, "adaptive set: rates must lie in [0, 1)");
+  const int L = a->K + a->K_inner, nloc = e->nloc;
+  const size_t Nc = e->Nc;
+  int oned = 0;
+  std::vector<double> leaf((size_t)nloc * L * 2);
+  for (int r = 0; r < nloc; ++r) {
+    int neg = 0;
+    for (int k = 0; k < L; ++k) {
+      const size_t i = (size_t)r * L + k;
+      if (k == a->nested) { leaf[2 * i] = 1.0; leaf[2 * i + 1] = 0.0; continue; }   // (the nested set's own entry is not read)
+      const double sc = scales[i], f = one_d_fracs[i];
+      if (!std::isfinite(sc)) return fail(PTM_ERR_INVALID, "adaptive set: scales must be finite (rung %d)", r);
+      if (!(f >= 0 && f <= 1)) return fail(PTM_ERR_INVALID, "oneDfrac must be in [0,1]");
+      if (sc < 0) {
+        if (k >= a->K) return fail(PTM_ERR_INVALID, "adaptive set: differential evolution (scale < 0) is a top member only (rung %d)", r);
+        if (k == a->K - 1) return fail(PTM_ERR_INVALID, "adaptive set: differential evolution must not be the last top member (rung %d)", r);
+        if (++neg > 1) return fail(PTM_ERR_INVALID, "adaptive set: at most one member with a negative scale (rung %d)", r);
+      }
+      leaf[2 * i] = sc; leaf[2 * i + 1] = f;
+      if (f > 0) oned = 1;
+    }
+  }
+  { const int rc = ada_check_state(*a, Nc, weights, thresholds, repeat_bits, outcomes); if (rc) return rc; }
+  std::vector<double> dbl;
+  std::vector<int> in;
+  ada_to_soa(Nc, L, weights, thresholds, repeat_bits, outcomes, dbl, in);
+  // the new arrays first, then the old configuration goes
+  double *nleaf = nullptr, *ndbl = nullptr;
+  int* nint = nullptr;
+  int rc;
+  if ((rc = dalloc(&nleaf, leaf.size())) || (rc = dalloc(&ndbl, dbl.size())) || (rc = dalloc(&nint, in.size()))) {
+    if (nleaf) (void)hipFree(nleaf);
+    if (ndbl) (void)hipFree(ndbl);
+    return rc;
+  }
+  if ((rc = upload(nleaf, leaf.data(), leaf.size(), e->stream)) || (rc = upload(ndbl, dbl.data(), dbl.size(), e->stream)) ||
+      (rc = upload(nint, in.data(), in.size(), e->stream))) {
+    (void)hipFree(nleaf); (void)hipFree(ndbl); (void)hipFree(nint);
+    return rc;
+  }
+  if ((rc = ada_off(e))) return rc;
+  if (e->mix) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->mix)); e->mix = nullptr; }
+  e->mix_K = 0;
+  e->ada_leaf = nleaf; e->ada_dbl = ndbl; e->ada_int = nint;
+  e->ada = *a;
+  e->ada_on = true;
+  if (oned) e->any_oned = 1;
+  return PTM_OK;
+}
+
+extern "C" int ptm_get_proposal_adapt_state(ptm_engine* e, double* weights, double* thresholds, int32_t* repeat_bits, int32_t* outcomes) {
+  if (!e || !weights || !thresholds || !repeat_bits || !outcomes) return fail(PTM_ERR_INVALID, "null argument");
+  SETTLE(e);
+  if (!e->ada_on) return fail(PTM_ERR_INVALID, "no adaptive proposal set (ptm_set_proposal_adaptive)");
+  const size_t Nc = e->Nc;
+  const int L = e->ada.K + e->ada.K_inner;
+  const unsigned char *sd, *si;
+  FETCH(sd, e->ada_dbl, 2 * (size_t)L * Nc * 8);
+  FETCH(si, e->ada_int, 4 * Nc * 4);
+  e->fetch_after.push_back([=] {
+    const double* d = (const double*)sd;
+    const int* q = (const int*)si;
+    for (size_t c = 0; c < Nc; ++c) {
+      for (int k = 0; k < L; ++k) { weights[c * L + k] = d[(size_t)k * Nc + c]; thresholds[c * L + k] = d[((size_t)L + k) * Nc + c]; }
+      for (int b = 0; b < 2; ++b) { repeat_bits[c * 2 + b] = q[(size_t)b * Nc + c]; outcomes[c * 2 + b] = q[(size_t)(2 + b) * Nc + c]; }
+    }
+  });
+  return fetch_done(e);
+}
+
+extern "C" int ptm_set_proposal_adapt_state(ptm_engine* e, const double* weights, const double* thresholds, const int32_t* repeat_bits, const int32_t* outcomes) {
+  if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_set_proposal_adapt_state");
+  if (!e->ada_on) return fail(PTM_ERR_INVALID, "no adaptive proposal set (ptm_set_proposal_adaptive)");
+  const size_t Nc = e->Nc;
+  const int L = e->ada.K + e->ada.K_inner;
+  { const int rc = ada_check_state(e->ada, Nc, weights, thresholds, repeat_bits, outcomes); if (rc) return rc; }
+  std::vector<double> dbl;
+  std::vector<int> in;
+  ada_to_soa(Nc, L, weights, thresholds, repeat_bits, outcomes, dbl, in);
+  int rc;
+  if ((rc = upload(e->ada_dbl, dbl.data(), dbl.size(), e->stream)) || (rc = upload(e->ada_int, in.data(), in.size(), e->stream))) return rc;
   return PTM_OK;
 }
 
@@ -1070,6 +1226,17 @@ static Dev make_dev(ptm_engine* e) {
   return p;
 }
 
+// the adaptive set's kernel argument (zero without one)
+static AdaArgs make_ada(const ptm_engine* e) {
+  AdaArgs a;
+  memset(&a, 0, sizeof a);
+  if (!e->ada_on) return a;
+  const size_t L = (size_t)e->ada.K + e->ada.K_inner, Nc = e->Nc;
+  a.K = e->ada.K; a.nested = e->ada.nested; a.Ki = e->ada.K_inner; a.rate = e->ada.rate; a.rate_in = e->ada.rate_inner;
+  a.leaf = e->ada_leaf; a.w = e->ada_dbl; a.th = e->ada_dbl + L * Nc; a.bits = e->ada_int; a.cnt = e->ada_int + 2 * Nc;
+  return a;
+}
+
 // a user likelihood, on the host (ptm_set_target_callback) or on the device (ptm_set_target_device): the propose / accept passes
 static inline bool user_like(const ptm_engine* e) { return e->cb != nullptr || e->dfn != nullptr; }
 
@@ -1079,9 +1246,10 @@ static SweepSel sweep_sel(const ptm_engine* e) {
   s.uni = (e->W % 64) == 0;
   s.host_prop = e->pcb != nullptr;
   if (s.host_prop) s.kind = KIND_DIAG;   // (no factor is read: any instantiation serves)
-  s.plain = !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !e->betaC && !s.host_prop;
+  s.ada = e->ada_on && !s.host_prop;   // (host-side proposals take over from an adaptive set)
+  s.plain = !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !s.ada && !e->betaC && !s.host_prop;
   s.simple = s.uni && s.plain;
-  s.lean_ev = s.uni && e->betaC && !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !s.host_prop &&
+  s.lean_ev = s.uni && e->betaC && !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !s.ada && !s.host_prop &&
               !e->hist.rungs && !e->map.rungs;
   s.callback = user_like(e);
   s.de = e->de_on;
@@ -1289,7 +1457,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   // population then visits the moving chains only (partition_kernel packs them per rung).  PTM_COMPACT=0 switches it off.
   static const bool compact_ok = [] { const char* v = getenv("PTM_COMPACT"); return !(v && *v == '0'); }();
   // ... and the box-bounds build (uniform priors, open / limit bounds, a mean, one-dimensional moves, scale mixtures, evolving ladders)
-  const bool gen1 = sel.uni && !sel.callback && !sel.host_prop && !sel.de && e->all_uniform && (!e->has_bounds || e->bounds_box);
+  const bool gen1 = sel.uni && !sel.callback && !sel.host_prop && !sel.de && !sel.ada && e->all_uniform && (!e->has_bounds || e->bounds_box);
   const bool compact = compact_ok && e->touched && e->DP == 32 && (sel.simple || gen1) && !e->hist.rungs && !e->map.rungs && !getenv("PTM_FORCE_VALU") &&
                        e->W >= 1024 && e->nloc <= 4096;   // (the same answer for every partial sweep of a step)
   if (!compact) { int rc = flush_nhist(e); if (rc) return rc; }
@@ -1306,17 +1474,18 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   // the timed bracket holds the sweep kernel alone (its name: ptm_sweep_kernel_name): the list fill and partition_kernel of a
   // compacted sweep stay outside, so that the events' mean is what rocprofv3 reports for that kernel
   if (ev0) HIPCHK(hipEventRecord(ev0, e->stream));
+  const AdaArgs ada = make_ada(e);
   auto launch = [&](const Dev& q) -> hipError_t {
     switch (e->DP) {
-      case 4: return launch_sweep_4(q, sel, e->stream);
-      case 8: return launch_sweep_8(q, sel, e->stream);
-      case 16: return launch_sweep_16(q, sel, e->stream);
-      case 32: return launch_sweep_32(q, sel, e->stream);
-      case 64: return launch_sweep_64(q, sel, e->stream);
-      case 128: return launch_sweep_128(q, sel, e->stream);
-      case 256: return launch_sweep_256(q, sel, e->stream);
-      case 512: return launch_sweep_512(q, sel, e->stream);
-      case 1024: return launch_sweep_1024(q, sel, e->stream);
+      case 4: return launch_sweep_4(q, sel, e->stream, ada);
+      case 8: return launch_sweep_8(q, sel, e->stream, ada);
+      case 16: return launch_sweep_16(q, sel, e->stream, ada);
+      case 32: return launch_sweep_32(q, sel, e->stream, ada);
+      case 64: return launch_sweep_64(q, sel, e->stream, ada);
+      case 128: return launch_sweep_128(q, sel, e->stream, ada);
+      case 256: return launch_sweep_256(q, sel, e->stream, ada);
+      case 512: return launch_sweep_512(q, sel, e->stream, ada);
+      case 1024: return launch_sweep_1024(q, sel, e->stream, ada);
     }
     return hipErrorInvalidValue;
   };
@@ -1862,7 +2031,7 @@ extern "C" int ptm_sweep(ptm_engine* e, int n) {
 // two-launch path.  Returns the steps taken (0: not this engine's case), or a negative status.
 static int fused_steps(ptm_engine* e, int n) {
   static const bool fused_ok = [] { const char* v = getenv("PTM_FUSED"); return !(v && *v == '0'); }();
-  if (!fused_ok || e->DP > 16 || (long long)e->Nt * e->DP > 256 || user_like(e) || e->pcb || e->cfg.time_kernels) return 0;
+  if (!fused_ok || e->DP > 16 || (long long)e->Nt * e->DP > 256 || user_like(e) || e->pcb || e->ada_on || e->cfg.time_kernels) return 0;
   if (e->evolve_rate > 0 && (e->W > 64 || e->evolve_cut >= 0)) return 0;   // (the new temperatures' chain-indexed image is then a separate launch)
   const bool evb = e->evolve_rate > 0 && e->beta_add;
   const size_t dlds = decide_lds_bytes(e->Nt, e->ms, e->Nt, e->evolve_rate > 0, evb);
@@ -1920,6 +2089,7 @@ static bool ladder_applies(ptm_engine* e, long long* grid_out = nullptr, size_t*
   // it fits, a step costs this kernel its ~6 us of latency whatever the walkers' number (64 walkers x 64 rungs of 12 dimensions with the
   // sampler's defaults: 14 us against 40 on two launches)
   if (user_like(e) || e->prior_cb || e->pcb) return false;
+  if (e->ada_on) return false;   // (an adaptive proposal set: exchange kernel + the lanes or general kernel's ADA build)
   const int R = 256 / e->DP, NB = (e->Nt + R - 1) / R;
   const long long grid = (long long)e->W * NB;
   const bool diag = e->prop_kind == PTM_PROP_DIAG;
@@ -2867,7 +3037,7 @@ extern "C" const char* ptm_sweep_kernel_name(ptm_engine* e) {
   char b[96];
   const SweepSel s = sweep_sel(e);
   const char* fv = getenv("PTM_FORCE_VALU");
-  if (e->DP == 32 && s.uni && !s.callback && !s.host_prop && !s.de && !(fv && *fv && *fv != '0')) {
+  if (e->DP == 32 && s.uni && !s.callback && !s.host_prop && !s.de && !s.ada && !(fv && *fv && *fv != '0')) {
     const char* cv = getenv("PTM_COMPACT");
     const bool g1 = !s.simple && e->all_uniform && (!e->has_bounds || e->bounds_box);
     const bool cpt = !(cv && *cv == '0') && (s.simple || g1) && !e->hist.rungs && !e->map.rungs && e->W >= 1024 && e->nloc <= 4096;   // (in PT steps; plain sweeps visit every chain)
@@ -2875,12 +3045,13 @@ extern "C" const char* ptm_sweep_kernel_name(ptm_engine* e) {
              (s.simple || s.lean_ev) ? 0 : ((e->all_uniform && (!e->has_bounds || e->bounds_box)) ? ((cpt && !e->has_mean && !e->any_oned && e->mix_K == 0) ? 3 : 1) : 2),
              (!s.simple && e->all_uniform && (!e->has_bounds || e->bounds_box) && e->betaC) ? ", true" : ", false", cpt ? "true" : "false");   // as rocprofv3 prints it
   }
-  else if ((e->DP == 64 || e->DP == 128) && s.uni && e->all_uniform && (!e->has_bounds || e->bounds_box) && !e->has_mean && !e->any_oned && e->mix_K == 0 && !s.callback &&
+  else if ((e->DP == 64 || e->DP == 128) && s.uni && e->all_uniform && (!e->has_bounds || e->bounds_box) && !e->has_mean && !e->any_oned && e->mix_K == 0 && !s.ada && !s.callback &&
            !s.host_prop && !e->hist.rungs && !e->map.rungs && !(fv && *fv && *fv != '0'))
     snprintf(b, sizeof b, "sweep_mfma%d_kernel<%d, %s, %s>", e->DP, s.kind == KIND_DIAG ? KIND_LOWER : s.kind, e->has_bounds ? "true" : "false", e->betaC ? "true" : "false");
   else if (e->DP >= 64 || s.host_prop || (!getenv("PTM_FORCE_VALU") && ((!s.uni && (long long)e->Nc * e->DP <= (e->DP >= 16 ? PTM_LANES_MAX : 4096ll * e->DP)) ||
                                                                            (s.uni && s.de && e->DP >= 16 && (long long)e->Nc * e->DP <= (e->DP >= 32 ? (1ll << 21) : (1ll << 19))))))   // (launch_kind's rule)
-    snprintf(b, sizeof b, "sweep_lanes_kernel<%d, %d, %s>", e->DP, s.kind, s.plain ? "false" : "true");
+    snprintf(b, sizeof b, s.ada ? "sweep_lanes_ada_kernel<%d, %d>" : "sweep_lanes_kernel<%d, %d, %s>", e->DP, s.kind, s.plain ? "false" : "true");
+  else if (s.ada) snprintf(b, sizeof b, "sweep_kernel<%d, %d, %s, false, true>", e->DP, s.kind, s.uni ? "true" : "false");
   else snprintf(b, sizeof b, "sweep_kernel<%d, %d, %s, %s>", e->DP, s.kind, s.uni ? "true" : "false", s.simple ? "true" : "false");
   e->kname = b;
   if (e->dfn) e->kname += " + device likelihood";   // (propose pass, pack, the user's work, scatter, accept pass)
@@ -2891,7 +3062,7 @@ extern "C" const char* ptm_step_kernel_name(ptm_engine* e) {
   if (!e) return "";
   static thread_local std::string name;
   char b[160];
-  const bool fused = e->DP <= 16 && (long long)e->Nt * e->DP <= 256 && !user_like(e) && !e->pcb && !e->cfg.time_kernels && !(getenv("PTM_FUSED") && *getenv("PTM_FUSED") == '0') &&
+  const bool fused = e->DP <= 16 && (long long)e->Nt * e->DP <= 256 && !user_like(e) && !e->pcb && !e->ada_on && !e->cfg.time_kernels && !(getenv("PTM_FUSED") && *getenv("PTM_FUSED") == '0') &&
                      !(e->evolve_rate > 0 && (e->W > 64 || e->evolve_cut >= 0));
   if (e->nloc != e->Nt) snprintf(b, sizeof b, "(sharded: ptm_exchange_* / ptm_shard_step) decide_kernel + %s", ptm_sweep_kernel_name(e));
   else if (ladder_applies(e)) snprintf(b, sizeof b, "ladder_persistent_kernel<%d, %d, %d>", e->DP, e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : KIND_DENSE, ladder_flavour(e));

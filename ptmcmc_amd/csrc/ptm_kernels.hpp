@@ -158,6 +158,18 @@ struct Dev {
   unsigned char* acc_out;        // [Nc] 1 accepted, 0 rejected, 2 no move (exchanged rung)
 };
 
+// adaptive proposal set (ptm_set_proposal_adaptive): a kernel argument of its own, of the ADA builds of the lanes and general kernels only
+// (the other builds' argument block stays as it is).  K top members, of which `nested` (or -1) is a set of Ki Gaussians; leaves
+// [nloc][K + Ki][2] = {scale, oneDfrac}; per-chain state structure-of-arrays: weights / thresholds [K + Ki][Nc], repeat bits / outcome
+// counts [2][Nc] (top set, nested set)
+struct AdaArgs {
+  int K, nested, Ki;
+  double rate, rate_in;
+  const double* leaf;
+  double *w, *th;
+  int *bits, *cnt;
+};
+
 // ------------------------------------------------------------------------------------------------
 // boundary::enforce (states.cc:11-58)
 // ------------------------------------------------------------------------------------------------
@@ -431,6 +443,68 @@ __device__ __forceinline__ bool de_ready(const Dev& p, unsigned int nh0) {   // 
   const long long rows = p.de_init_extra + 1 + (long long)((nh0 + (unsigned int)p.add_every_n - 1u) / (unsigned int)p.add_every_n);
   return rows >= 10ll * p.D;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Adaptive proposal set (ptm_set_proposal_adaptive): proposal_distribution_set::draw / accept / reject / reset_bins
+// (proposal_distribution.cc:37-59, 99-166; Tpow = 0) with each chain's shares, thresholds, last outcomes and outcome counts in
+// device arrays [member][Nc].  Only the ADA builds of the lanes and general kernels carry this code.
+// ------------------------------------------------------------------------------------------------
+struct AdaPick { int top, inner, leaf; };   // top member, member of the nested set (or -1), row of the leaf table
+// the pick: the top set's uniform is slot 3 of block 0 of the chain's MH stream (k_top), the nested set's slot 0 of block 0 of
+// TAG_SET; a set of one member draws none.  The first member that is ready and whose threshold lies above the uniform (every
+// set's last threshold is exactly 1); differential evolution that is not ready passes the pick on to the next member.
+__device__ __forceinline__ AdaPick ada_pick(const Dev& p, const AdaArgs& a, int c, int rl, uint32_t stream, uint64_t step, uint32_t k_top, unsigned int nh0) {
+  const int K = a.K;
+  const size_t Nc = p.Nc;
+  const double* leaf = a.leaf + (size_t)rl * (K + a.Ki) * 2;
+  const double x = K > 1 ? u01(k_top) : 0.0;
+  int i = K - 1;
+  for (int k = K - 2; k >= 0; --k)
+    if (x < a.th[(size_t)k * Nc + c]) i = k;
+  if (p.de_on && i != a.nested && leaf[2 * i] < 0 && i + 1 < K && !de_ready(p, nh0)) i += 1;   // (proposal_distribution.cc:111)
+  AdaPick r = {i, -1, i};
+  if (i == a.nested) {
+    const int Ki = a.Ki;
+    const double xi = Ki > 1 ? u01(draw_block(p.seed, TAG_SET, stream, step, 0).v0) : 0.0;
+    int j = Ki - 1;
+    for (int k = Ki - 2; k >= 0; --k)
+      if (xi < a.th[(size_t)(K + k) * Nc + c]) j = k;
+    r.inner = j; r.leaf = K + j;
+  }
+  return r;
+}
+// type code of a Gaussian leaf of type t (0, or 1 for a one-dimensional move): i + 10 t, or i + 10 (j + 10 t) inside the nested set
+__device__ __forceinline__ int ada_type(const AdaPick& q, int t) { return q.inner >= 0 ? q.top + 10 * (q.inner + 10 * t) : q.top + 10 * t; }
+// accept() / reject() of one set of n members whose member m was picked: weights at rows first.., bits / count in row b
+__device__ __forceinline__ void ada_set_outcome(const AdaArgs& a, size_t Nc, int c, int first, int n, int m, int b, double rate, bool acc) {
+  int bits = a.bits[(size_t)b * Nc + c];
+  if ((((bits >> m) & 1) != 0) == acc) {   // two accepts or two rejects in a row
+    double* w = a.w + (size_t)(first + m) * Nc + c;
+    *w = *w * (1 - rate * 0.25);
+  }
+  bits = acc ? (bits | (1 << m)) : (bits & ~(1 << m));
+  a.bits[(size_t)b * Nc + c] = bits;
+  const int cnt = a.cnt[(size_t)b * Nc + c] + 1;   // (never reset: from 10 n outcomes on the bins are rebuilt after every one)
+  a.cnt[(size_t)b * Nc + c] = cnt;
+  if (cnt >= 10 * n) {   // reset_bins: plain sequential sums and quotients
+    double sum = 0.0;
+    for (int k = 0; k < n; ++k) sum = sum + a.w[(size_t)(first + k) * Nc + c];
+    double last = 0.0;
+    for (int k = 0; k < n; ++k) {
+      const double wk = a.w[(size_t)(first + k) * Nc + c] / sum;
+      a.w[(size_t)(first + k) * Nc + c] = wk;
+      last = last + wk;
+      a.th[(size_t)(first + k) * Nc + c] = last;
+    }
+    for (int k = 0; k < n; ++k) a.th[(size_t)(first + k) * Nc + c] = a.th[(size_t)(first + k) * Nc + c] / last;
+  }
+}
+// the outcome of a Metropolis move made with pick q: to the top set, then to the picked nested set (each only if its rate is not 0)
+__device__ __forceinline__ void ada_outcome(const AdaArgs& a, size_t Nc, int c, const AdaPick& q, bool acc) {
+  if (a.rate != 0) ada_set_outcome(a, Nc, c, 0, a.K, q.top, 0, a.rate, acc);
+  if (q.inner >= 0 && a.rate_in != 0) ada_set_outcome(a, Nc, c, a.K, a.Ki, q.inner, 1, a.rate_in, acc);
+}
+
 template <int DP>
 __device__ __forceinline__ int de_draw(const Dev& p, int c, uint32_t stream, uint64_t step, unsigned int nh0, const double* __restrict__ row, double (&xn)[DP],
                                        double& log_hastings) {
@@ -523,8 +597,9 @@ __device__ __forceinline__ int de_draw(const Dev& p, int c, uint32_t stream, uin
 //   SIMPLE open boundaries, all-uniform prior, zero mean, no one-dimensional moves (the BASELINE workload):
 //          the general state-space / prior code is not even compiled in.
 // ------------------------------------------------------------------------------------------------
-template <int DP, int KIND, bool UNI, bool SIMPLE>
-__global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p) {
+//   ADA    an adaptive proposal set (ptm_set_proposal_adaptive, its state in `ada`): pick and update are in this build only
+template <int DP, int KIND, bool UNI, bool SIMPLE, bool ADA = false>
+__global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p, const AdaArgs ada) {
   // Per-wave LDS staging of the rung's proposal factor (UNI only): every rung has its own D x D factor, so unlike
   // the shared precision matrix it misses the scalar cache; one coalesced 512-B-per-instruction copy into LDS per
   // wave, then wave-uniform (broadcast) LDS reads feed the mat-vec.  Same-wave LDS traffic only: no barrier.
@@ -581,9 +656,16 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   // -- gaussian_prop::draw: D normals, optional one-dimensional move, offset = factor * z
   int type = 0, axis = -1, kmix = 0;
   double mix_scale = 1.0;
+  AdaPick apk = {0, -1, 0};
   if (!SIMPLE) {
     double f = as_c(p.onedfrac)[rl];
-    if (p.mix_K > 0) {   // proposal_distribution_set::draw: one uniform picks the member (a set of one draws nothing)
+    if (ADA) {           // adaptive set: the pick from the chain's own thresholds, then the leaf's scale and oneDfrac
+      apk = ada_pick(p, ada, c, rl, stream, p.step, o0.v3, p.nhist[c]);
+      const double* lf = ada.leaf + ((size_t)rl * (ada.K + ada.Ki) + apk.leaf) * 2;
+      kmix = apk.top;
+      mix_scale = lf[0];
+      f = lf[1];
+    } else if (p.mix_K > 0) {   // proposal_distribution_set::draw: one uniform picks the member (a set of one draws nothing)
       cdp mx = as_c(p.mix) + (size_t)rl * p.mix_K * 3;
       const double xs = p.mix_K > 1 ? u01(o0.v3) : 0.0;
       kmix = p.mix_K - 1;
@@ -648,8 +730,8 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
       if (mode == 1) { p.de_hast[c] = de_hast; p.de_type[c] = dt; }
     }
     type = kmix + 10 * dt;     // proposal_distribution.cc:117
-  } else if (!SIMPLE && p.mix_K > 0) {
-    type = kmix + 10 * type;   // proposal_distribution.cc:117
+  } else if (!SIMPLE && (ADA || p.mix_K > 0)) {
+    type = ADA ? ada_type(apk, type) : kmix + 10 * type;   // proposal_distribution.cc:117
     if (mode != 2) {
 #pragma unroll
       for (int d = 0; d < DP; ++d) xn[d] = mix_scale * xn[d];   // the member is scale_k times the rung's factor
@@ -717,6 +799,7 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   }
   if (accept && logH < 0) accept = dlog_u01(o0.v0) < logH;  // chain.cc:998-1001 (NaN stays accepted)
 
+  if (ADA) ada_outcome(ada, (size_t)p.Nc, c, apk, accept);   // proposal_distribution_set::accept() / reject() (chain.cc:1009,1015)
   const int ntries1 = p.ntries[c] + 1;
   p.ntries[c] = ntries1;
   const unsigned int nh0 = p.nhist[c];

@@ -39,9 +39,11 @@ __device__ __forceinline__ void lanes_stage(const Dev& p, double* lds_all) {
 // One MH_chain::step for the chains of this block's waves: wave `wslot0 + (threadIdx.x >> 6)` of the launch works for CPW
 // chains; the k-th chain of the launch is chain cbase + k * cstride (k < nslots).  The plain launch walks a contiguous range
 // (cbase = c_begin, cstride = 1); the fused small-ladder kernel walks ONE walker's rungs (cbase = walker, cstride = W).
-template <int DP, int KIND, bool GEN>
+// ADA (GEN only): an adaptive proposal set (ptm_set_proposal_adaptive) -- the pick from the chain's own thresholds and the update of
+// its state after the move; only sweep_lanes_ada_kernel carries it.
+template <int DP, int KIND, bool GEN, bool ADA = false>
 __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const int wslot0, const int cbase, const int cstride, const int nslots,
-                                           const uint64_t step) {   // (the step: a parameter of its own, see decide_body)
+                                           const uint64_t step, const AdaArgs& ada = AdaArgs()) {   // (the step: a parameter of its own, see decide_body)
   static_assert(DP == 4 || DP == 8 || DP == 16 || DP == 32 || DP == 64 || DP == 128 || DP == 256 || DP == 512 || DP == 1024, "lanes kernel: DP 4 .. 1024");
   constexpr int E = DP > 64 ? DP / 64 : 1;  // dimensions per lane: lane's d, d + 64, ...
   constexpr int LPC = DP / E;               // lanes per chain
@@ -111,9 +113,16 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
   const u32x4 o0 = draw_block(p.seed, TAG_MH, stream, step, 0);
   int type = 0, axis = -1, kmix = 0;
   double mix_scale = 1.0;
+  AdaPick apk = {0, -1, 0};
   if (GEN && !hp) {
     double f = p.onedfrac[rl];
-    if (p.mix_K > 0) {   // proposal_distribution_set::draw: one uniform picks the member (a set of one draws nothing)
+    if (ADA) {           // adaptive set: the pick from the chain's own thresholds, then the leaf's scale and oneDfrac
+      apk = ada_pick(p, ada, c, rl, stream, step, o0.v3, p.nhist[c]);
+      const double* lf = ada.leaf + ((size_t)rl * (ada.K + ada.Ki) + apk.leaf) * 2;
+      kmix = apk.top;
+      mix_scale = lf[0];
+      f = lf[1];
+    } else if (p.mix_K > 0) {   // proposal_distribution_set::draw: one uniform picks the member (a set of one draws nothing)
       const double* mx = p.mix + (size_t)rl * p.mix_K * 3;
       const double xs = p.mix_K > 1 ? u01(o0.v3) : 0.0;
       kmix = p.mix_K - 1;
@@ -192,8 +201,8 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
     sync_wave();
   }
   const double ll = p.ll[c], lp = p.lp[c];
-  if (GEN && p.mix_K > 0 && !hp) {
-    type = kmix + 10 * type;   // proposal_distribution.cc:117
+  if (GEN && (ADA || p.mix_K > 0) && !hp) {
+    type = ADA ? ada_type(apk, type) : kmix + 10 * type;   // proposal_distribution.cc:117
 #pragma unroll
     for (int e = 0; e < E; ++e) off[e] = mix_scale * off[e];     // the member is scale_k times the rung's factor
   }
@@ -430,6 +439,7 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
   if (hp && live && lead) p.acc_out[c] = tc ? (unsigned char)2 : (unsigned char)(accept ? 1 : 0);
 
   const bool act = live && !tc;
+  if (ADA && act && lead) ada_outcome(ada, (size_t)p.Nc, c, apk, accept);   // proposal_distribution_set::accept() / reject() (chain.cc:1009,1015)
   int mapw = 0;
   if (act) {
     const int ntries1 = p.ntries[c] + 1;
@@ -487,6 +497,13 @@ __global__ __launch_bounds__(256) void sweep_lanes_kernel(const Dev p) {
   extern __shared__ __attribute__((aligned(16))) double lds_all[];
   lanes_stage<DP>(p, lds_all);
   lanes_body<DP, KIND, GEN>(p, lds_all, blockIdx.x * 4, p.c_begin, 1, p.c_end - p.c_begin, p.step);
+}
+// the build of an adaptive proposal set (the GEN build plus its pick and update)
+template <int DP, int KIND>
+__global__ __launch_bounds__(256) void sweep_lanes_ada_kernel(const Dev p, const AdaArgs ada) {
+  extern __shared__ __attribute__((aligned(16))) double lds_all[];
+  lanes_stage<DP>(p, lds_all);
+  lanes_body<DP, KIND, true, true>(p, lds_all, blockIdx.x * 4, p.c_begin, 1, p.c_end - p.c_begin, p.step, ada);
 }
 
 }  // namespace ptm

@@ -21,9 +21,10 @@ struct SweepSel {
   bool callback;  // host-callback likelihood (propose / accept passes): general VALU kernel only
   bool host_prop; // host-side proposals (ptm_set_proposal_callback): the lanes kernel's general build, whatever the population
   bool de;        // differential evolution drawn on the device (ptm_set_proposal_de): the general VALU kernel or the lanes kernel, not the MFMA kernels
+  bool ada;       // adaptive proposal set (ptm_set_proposal_adaptive): the ADA builds of the lanes and general kernels, nothing else
 };
 #define PTM_DECL_DP(N)                                                                                              \
-  hipError_t launch_sweep_##N(const Dev& p, SweepSel s, hipStream_t st);                                            \
+  hipError_t launch_sweep_##N(const Dev& p, SweepSel s, hipStream_t st, const AdaArgs& ada);                                            \
   hipError_t launch_eval_##N(const Dev& p, int n, double* x, int* valid, double* lp, double* ll, int eval_like,     \
                              hipStream_t st);                                                                       \
   hipError_t launch_init_##N(const Dev& p, double* x, double* ll, double* lp, int* fail, long long cb_attempt,          \

@@ -52,14 +52,14 @@ static bool force_valu_path() {
 }
 
 template <int KIND>
-static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st) {
+static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st, const AdaArgs& ada) {
   const dim3 grid((p.c_end - p.c_begin + 255) / 256), block(256);
   // UNI kernels stage one copy of the rung's factor per wave in LDS (4 waves per block)
   // plus the 20 KB of Box-Muller tables every variant stages
   const size_t tab = BM_TABLE_DOUBLES * sizeof(double);
   const size_t lds = tab + ((s.uni && KIND != KIND_DIAG) ? (size_t)4 * p.prop_stride * sizeof(double) : 0);
 #if PTM_DP == 32
-  if (s.uni && p.mode == 0 && !s.callback && !s.host_prop && !s.de && !force_valu_path()) {
+  if (s.uni && p.mode == 0 && !s.callback && !s.host_prop && !s.de && !s.ada && !force_valu_path()) {
     constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // a diagonal factor is a (very sparse) Cholesky factor
     // the BASELINE workload: both matrix products on the f64 matrix cores (ptm_mfma_kernel.hpp)
     // LDS: tables | P2 tiles | box | 4 x 128 reduction slots | (general: 6 x 32 doubles + 3 x 32 ints + 4 x 128 slots)
@@ -119,7 +119,7 @@ static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st) {
   // 33..64 dimensions, whole waves per rung, the plain workload without history: both products on the f64 matrix cores
   // (ptm_mfma64_kernel.hpp); everything else at these dimensions keeps the lanes kernel
   // (the plain workload, or open / `limit` bounds and / or evolving ladders on top of it: template flags BND, EV)
-  if (s.uni && p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.has_mean && !p.any_oned && p.mix_K == 0 && p.mode == 0 && !s.callback && !s.host_prop &&
+  if (s.uni && p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.has_mean && !p.any_oned && p.mix_K == 0 && !s.ada && p.mode == 0 && !s.callback && !s.host_prop &&
       !p.hist.rungs && !p.map.rungs && !force_valu_path()) {
     constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // a diagonal factor is a (very sparse) Cholesky factor
     const size_t mlds = (size_t)m64_lds_doubles() * sizeof(double);
@@ -144,7 +144,7 @@ static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st) {
   // 65..128 dimensions, whole waves per rung, the plain workload without history: both products on the f64 matrix cores
   // (ptm_mfma128_kernel.hpp: 97 KB of LDS, one block per CU); everything else at these dimensions keeps the lanes kernel
   // (the plain workload, or open / `limit` bounds and / or evolving ladders on top of it: template flags BND, EV)
-  if (s.uni && p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.has_mean && !p.any_oned && p.mix_K == 0 && p.mode == 0 && !s.callback && !s.host_prop &&
+  if (s.uni && p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.has_mean && !p.any_oned && p.mix_K == 0 && !s.ada && p.mode == 0 && !s.callback && !s.host_prop &&
       !p.hist.rungs && !p.map.rungs && !force_valu_path()) {
     constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // a diagonal factor is a (very sparse) Cholesky factor
     const size_t mlds = (size_t)m128_lds_doubles() * sizeof(double);
@@ -186,18 +186,22 @@ static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st) {
     const dim3 lgrid((p.c_end - p.c_begin + 4 * CPW - 1) / (4 * CPW));
     const size_t llds = (size_t)lanes_lds_doubles<PTM_DP>(4) * sizeof(double);
     if (llds > 64 * 1024) {   // (65..128 dimensions: the packed precision matrix alone is 66 KB)
-      hipError_t rc = hipFuncSetAttribute(s.plain ? (const void*)sweep_lanes_kernel<PTM_DP, KIND, false> : (const void*)sweep_lanes_kernel<PTM_DP, KIND, true>,
+      hipError_t rc = hipFuncSetAttribute(s.ada ? (const void*)sweep_lanes_ada_kernel<PTM_DP, KIND>
+                                                : s.plain ? (const void*)sweep_lanes_kernel<PTM_DP, KIND, false> : (const void*)sweep_lanes_kernel<PTM_DP, KIND, true>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds);
       if (rc != hipSuccess) return rc;
     }
-    if (s.plain) hipLaunchKernelGGL((sweep_lanes_kernel<PTM_DP, KIND, false>), lgrid, block, llds, st, p);
+    if (s.ada) hipLaunchKernelGGL((sweep_lanes_ada_kernel<PTM_DP, KIND>), lgrid, block, llds, st, p, ada);
+    else if (s.plain) hipLaunchKernelGGL((sweep_lanes_kernel<PTM_DP, KIND, false>), lgrid, block, llds, st, p);
     else hipLaunchKernelGGL((sweep_lanes_kernel<PTM_DP, KIND, true>), lgrid, block, llds, st, p);
     return hipGetLastError();
   }
 #if PTM_DP <= 32
-  if (s.uni && s.simple) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, true>), grid, block, lds, st, p);
-  else if (s.uni) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, false>), grid, block, lds, st, p);
-  else hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, false, false>), grid, block, tab, st, p);
+  if (s.ada && s.uni) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, false, true>), grid, block, lds, st, p, ada);
+  else if (s.ada) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, false, false, true>), grid, block, tab, st, p, ada);
+  else if (s.uni && s.simple) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, true>), grid, block, lds, st, p, AdaArgs());
+  else if (s.uni) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, false>), grid, block, lds, st, p, AdaArgs());
+  else hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, false, false>), grid, block, tab, st, p, AdaArgs());
   return hipGetLastError();
 #else
   (void)grid; (void)lds; (void)tab;
@@ -205,11 +209,11 @@ static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st) {
 #endif
 }
 
-hipError_t PTM_CAT(launch_sweep_, PTM_DP)(const Dev& p, SweepSel s, hipStream_t st) {
+hipError_t PTM_CAT(launch_sweep_, PTM_DP)(const Dev& p, SweepSel s, hipStream_t st, const AdaArgs& ada) {
   switch (s.kind) {
-    case KIND_DIAG: return launch_kind<KIND_DIAG>(p, s, st);
-    case KIND_LOWER: return launch_kind<KIND_LOWER>(p, s, st);
-    default: return launch_kind<KIND_DENSE>(p, s, st);
+    case KIND_DIAG: return launch_kind<KIND_DIAG>(p, s, st, ada);
+    case KIND_LOWER: return launch_kind<KIND_LOWER>(p, s, st, ada);
+    default: return launch_kind<KIND_DENSE>(p, s, st, ada);
   }
 }
 

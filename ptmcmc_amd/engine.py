@@ -31,6 +31,7 @@ EXPORTS = [
     "ptm_debug_philox", "ptm_debug_boxmuller", "ptm_debug_sqrt_scan", "ptm_debug_evaluate",
     "ptm_dev_alloc", "ptm_dev_free", "ptm_dev_copy",
     "ptm_set_target_device", "ptm_target_device_rows", "ptm_get_best_evaluated",
+    "ptm_set_proposal_adaptive", "ptm_get_proposal_adapt_state", "ptm_set_proposal_adapt_state",
 ]
 
 
@@ -49,6 +50,10 @@ class PtmCalibration(C.Structure):
 
 class PtmDeParams(C.Structure):
     _fields_ = [("snooker", C.c_double), ("gamma_one_frac", C.c_double), ("reduce_gamma", C.c_double), ("ignore_frac", C.c_double)]
+
+
+class PtmAdaptiveSet(C.Structure):
+    _fields_ = [("K", C.c_int), ("nested", C.c_int), ("K_inner", C.c_int), ("rate", C.c_double), ("rate_inner", C.c_double)]
 
 
 class PtmError(RuntimeError):
@@ -167,6 +172,10 @@ def load():
         L.ptm_set_target_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ptm_target_device_rows.argtypes = [C.c_void_p]
         L.ptm_get_best_evaluated.argtypes = [C.c_void_p, _dp, _dp]
+    if hasattr(L, "ptm_set_proposal_adaptive"):
+        L.ptm_set_proposal_adaptive.argtypes = [C.c_void_p, C.POINTER(PtmAdaptiveSet), _dp, _dp, _dp, _dp, _i32p, _i32p]
+        L.ptm_get_proposal_adapt_state.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p]
+        L.ptm_set_proposal_adapt_state.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p]
     _lib = L
     return L
 
@@ -588,6 +597,42 @@ class Engine:
         q = PtmDeParams(snooker, gamma_one_frac, reduce_gamma, ignore_frac)
         ir = None if init_rows is None else np.ascontiguousarray(init_rows, dtype=np.float64).reshape(-1, self.Nc, self.D)
         _chk(self.L.ptm_set_proposal_de(self.h, C.byref(q), 0 if ir is None else ir.shape[0], None if ir is None else ir.ctypes.data_as(_dp)))
+
+    def set_proposal_adaptive(self, K, scales, one_d_fracs, weights, thresholds, repeat_bits=None, outcomes=None, nested=-1, K_inner=0,
+                              rate=0.0, rate_inner=0.0):
+        """an adaptive proposal set (ptm_set_proposal_adaptive): leaves scales / one_d_fracs [rung_count][K + K_inner] (scale < 0: the
+        differential-evolution member), the initial state per local chain in the engine's chain order: weights / thresholds
+        [Nc][K + K_inner], repeat bits / outcome counts [Nc][2] (default: every last outcome an accept, no outcomes yet)"""
+        L = K + K_inner
+        sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(self.nloc, L)
+        od = np.ascontiguousarray(one_d_fracs, dtype=np.float64).reshape(self.nloc, L)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(self.Nc, L)
+        th = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(self.Nc, L)
+        if repeat_bits is None:
+            repeat_bits = np.tile(np.array([(1 << K) - 1, (1 << K_inner) - 1], dtype=np.int32), (self.Nc, 1))
+        if outcomes is None:
+            outcomes = np.zeros((self.Nc, 2), dtype=np.int32)
+        rb = np.ascontiguousarray(repeat_bits, dtype=np.int32).reshape(self.Nc, 2)
+        oc = np.ascontiguousarray(outcomes, dtype=np.int32).reshape(self.Nc, 2)
+        a = PtmAdaptiveSet(int(K), int(nested), int(K_inner), float(rate), float(rate_inner))
+        _chk(self.L.ptm_set_proposal_adaptive(self.h, C.byref(a), sc.ctypes.data_as(_dp), od.ctypes.data_as(_dp), w.ctypes.data_as(_dp),
+                                              th.ctypes.data_as(_dp), rb.ctypes.data_as(_i32p), oc.ctypes.data_as(_i32p)))
+        self._ada_L = L
+
+    def proposal_adapt_state(self):
+        """the adaptive set's per-chain state (ptm_get_proposal_adapt_state): dict weights, thresholds [Nc][L], repeat_bits, outcomes [Nc][2]"""
+        L = getattr(self, "_ada_L", 0)
+        w = self._out(np.empty((self.Nc, max(L, 1)))); th = self._out(np.empty((self.Nc, max(L, 1))))
+        rb = self._out(np.empty((self.Nc, 2), dtype=np.int32)); oc = self._out(np.empty((self.Nc, 2), dtype=np.int32))
+        _chk(self.L.ptm_get_proposal_adapt_state(self.h, w.ctypes.data_as(_dp), th.ctypes.data_as(_dp), rb.ctypes.data_as(_i32p), oc.ctypes.data_as(_i32p)))
+        return dict(weights=w, thresholds=th, repeat_bits=rb, outcomes=oc)
+
+    def set_proposal_adapt_state(self, weights, thresholds, repeat_bits, outcomes):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        th = np.ascontiguousarray(thresholds, dtype=np.float64)
+        rb = np.ascontiguousarray(repeat_bits, dtype=np.int32)
+        oc = np.ascontiguousarray(outcomes, dtype=np.int32)
+        _chk(self.L.ptm_set_proposal_adapt_state(self.h, w.ctypes.data_as(_dp), th.ctypes.data_as(_dp), rb.ctypes.data_as(_i32p), oc.ctypes.data_as(_i32p)))
 
     def set_proposal_rung(self, local_rung, factor, one_d_frac=-1.0):
         f = np.ascontiguousarray(factor, dtype=np.float64)

@@ -1191,10 +1191,17 @@ class proposal_distribution_set : public proposal_distribution {
   }
   bool device_describe_de(ptm_de_params& q) const override {
     const int de = device_de_member();
-    return de >= 0 && adapt_rate == 0 && !(thermal_power > 0) && slots[de].prop->device_describe_de(q);
+    return de >= 0 && (adapt_rate == 0 || adaptive()) && !(thermal_power > 0) && slots[de].prop->device_describe_de(q);
   }
   bool device_describe(int dim, int& kind, std::vector<double>& f, double& odf) const override {
-    if (adapt_rate != 0 || thermal_power > 0) return false;   // shares that move are the host's business
+    if (thermal_power > 0) return false;   // temperature-dependent shares are the host's business
+    if (adaptive()) {                      // shares that move: the device's adaptive set (device_describe_adaptive)
+      ptm_adaptive_set a;
+      std::vector<double> sc, od;
+      odf = 0;
+      return device_describe_adaptive(dim, kind, f, a, sc, od);
+    }
+    if (adapt_rate != 0) return false;
     const int g0 = first_gaussian_member();
     if (device_de_member() == -2 || g0 < 0 || !slots[g0].prop->device_describe(dim, kind, f, odf)) return false;
     std::vector<double> cum, sc, od;
@@ -1204,7 +1211,7 @@ class proposal_distribution_set : public proposal_distribution {
   }
   // Gaussian members that are scalar multiples of one factor, and at most one differential evolution (scale -1: ptm_set_proposal_de)
   bool device_describe_mixture(int dim, std::vector<double>& cum, std::vector<double>& scales, std::vector<double>& odfs) const override {
-    if (adapt_rate != 0 || thermal_power > 0) return false;
+    if (adapt_rate != 0 || thermal_power > 0 || adaptive()) return false;
     const int de = device_de_member(), g0 = first_gaussian_member();
     if (de == -2 || g0 < 0) return false;
     int kind0; double odf0; std::vector<double> f0;
@@ -1223,6 +1230,97 @@ class proposal_distribution_set : public proposal_distribution {
       odfs.push_back(odf);
     }
     return true;
+  }
+  // ---- adaptive sets on the device (ptm_set_proposal_adaptive) ----
+  // the member that is itself a proposal_distribution_set (-1: none, -2: more than one)
+  int nested_member() const {
+    int at = -1;
+    for (size_t i = 0; i < slots.size(); i++)
+      if (dynamic_cast<const proposal_distribution_set*>(slots[i].prop)) {
+        if (at >= 0) return -2;
+        at = (int)i;
+      }
+    return at;
+  }
+  // do this set's shares, or those of a nested set, adapt?
+  bool adaptive() const {
+    if (adapt_rate != 0) return true;
+    const int n = nested_member();
+    return n >= 0 && ((const proposal_distribution_set*)slots[n].prop)->adapt_rate != 0;
+  }
+  // The adaptive set the device draws: Tpow = 0, up to eight top members -- at most one differential evolution that is not the last
+  // (scale -1), at most one nested adaptive set of Gaussians, and single Gaussians --, every Gaussian a scalar multiple of one factor
+  // (kind, f: the first Gaussian's).  Leaves: the top members, then the nested set's; the nested member's own entry is 1.
+  bool device_describe_adaptive(int dim, int& kind, std::vector<double>& f, ptm_adaptive_set& a, std::vector<double>& scales,
+                                std::vector<double>& odfs) const {
+    if (thermal_power > 0 || !adaptive() || slots.size() > 8) return false;
+    const int nest = nested_member(), de = device_de_member();
+    if (nest == -2 || de == -2 || (nest >= 0 && nest == de)) return false;
+    const proposal_distribution_set* in = nest >= 0 ? (const proposal_distribution_set*)slots[nest].prop : nullptr;
+    if (in && (in->thermal_power > 0 || in->slots.size() > 8 || in->nested_member() != -1 || in->device_de_member() != -1)) return false;
+    std::vector<const proposal_distribution*> gauss;   // every Gaussian leaf, in leaf order
+    for (size_t i = 0; i < slots.size(); i++)
+      if ((int)i != de && (int)i != nest) gauss.push_back(slots[i].prop);
+    if (in)
+      for (size_t j = 0; j < in->slots.size(); j++) gauss.push_back(in->slots[j].prop);
+    if (gauss.empty()) return false;
+    double odf0;
+    if (!gauss[0]->device_describe(dim, kind, f, odf0)) return false;
+    auto scale_of = [&](const proposal_distribution* p, double& sc, double& odf) {
+      int k;
+      std::vector<double> g;
+      if (dynamic_cast<const proposal_distribution_set*>(p) || !p->device_describe(dim, k, g, odf) || k != kind || g.size() != f.size()) return false;
+      sc = 0;
+      for (size_t i = 0; i < g.size(); i++) if (f[i] != 0) { sc = g[i] / f[i]; break; }
+      for (size_t i = 0; i < g.size(); i++)
+        if (std::fabs(g[i] - sc * f[i]) > 1e-12 * (std::fabs(g[i]) + std::fabs(sc * f[i])) + 1e-300) return false;   // not a multiple
+      return true;
+    };
+    scales.clear(); odfs.clear();
+    for (size_t i = 0; i < slots.size(); i++) {
+      double sc = 1.0, odf = 0.0;
+      if ((int)i == de) sc = -1.0;
+      else if ((int)i != nest && !scale_of(slots[i].prop, sc, odf)) return false;
+      scales.push_back(sc); odfs.push_back(odf);
+    }
+    if (in)
+      for (size_t j = 0; j < in->slots.size(); j++) {
+        double sc, odf;
+        if (!scale_of(in->slots[j].prop, sc, odf)) return false;
+        scales.push_back(sc); odfs.push_back(odf);
+      }
+    a.K = (int)slots.size(); a.nested = nest; a.K_inner = in ? (int)in->slots.size() : 0;
+    a.rate = adapt_rate; a.rate_inner = in ? in->adapt_rate : 0.0;
+    return true;
+  }
+  // this set's adaptive state and its nested set's, in the rows of ptm_set_proposal_adaptive / ptm_get_proposal_adapt_state:
+  // weights, thresholds [K + K_inner]; bits of the members whose last outcome was an accept, outcome counts [2] (top, nested)
+  void adapt_state(std::vector<double>& w, std::vector<double>& th, std::vector<int>& bits, std::vector<int>& cnt) const {
+    w.clear(); th.clear(); bits.assign(2, 0); cnt.assign(2, 0);
+    const int nest = nested_member();
+    const proposal_distribution_set* in = nest >= 0 ? (const proposal_distribution_set*)slots[nest].prop : nullptr;
+    for (int b = 0; b < (in ? 2 : 1); b++) {
+      const proposal_distribution_set* s = b ? in : this;
+      for (size_t i = 0; i < s->slots.size(); i++) {
+        w.push_back(s->slots[i].weight); th.push_back(s->upper[i]);
+        if (s->slots[i].repeated) bits[b] |= 1 << i;
+      }
+      cnt[b] = s->outcomes_seen;
+    }
+  }
+  // ... and back (the device's state, for the report)
+  void set_adapt_state(const double* w, const double* th, const int32_t* bits, const int32_t* cnt) {
+    const int nest = nested_member();
+    proposal_distribution_set* in = nest >= 0 ? (proposal_distribution_set*)slots[nest].prop : nullptr;
+    size_t k = 0;
+    for (int b = 0; b < (in ? 2 : 1); b++) {
+      proposal_distribution_set* s = b ? in : this;
+      for (size_t i = 0; i < s->slots.size(); i++, k++) {
+        s->slots[i].weight = w[k]; s->upper[i] = th[k];
+        s->slots[i].repeated = ((bits[b] >> i) & 1) != 0;
+      }
+      s->outcomes_seen = cnt[b];
+    }
   }
 };
 
@@ -1949,6 +2047,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   // evolution): all Ninit initial draws, then every saved row, pulled from the device's short history ring after each step.
   bool host_mode = false, want_host = false;
   bool want_de = false, de_built = false;   // differential evolution drawn on the device from the device's history
+  bool adaptive_dev = false;                // the proposal is an adaptive set drawn and adapted on the device (ptm_set_proposal_adaptive)
   int ring_rows = 0, ring_rungs = 0;   // the device history ring as the engine was created with it
   uint64_t eng_seed = 0;
   struct mirror_t {   // one chain's saved history, raw indexing as MH_chain::states / lposts / llikes (chain.hh:155-163)
@@ -2508,7 +2607,32 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       for (int i = 0; i < Ntemps; i++) props.push_back(proposal.clone());
       ptm_check(ptm_set_proposals(eng, kind, all.data(), odfs.data()), "set_proposals");
       std::vector<double> cum, sc, od;
-      if (proposal.device_describe_mixture(dim, cum, sc, od)) {   // a proposal_distribution_set of scaled Gaussians
+      proposal_distribution_set* ps = dynamic_cast<proposal_distribution_set*>(&proposal);
+      ptm_adaptive_set as;
+      int kind_a;
+      std::vector<double> f_a;
+      adaptive_dev = ps && ps->device_describe_adaptive(dim, kind_a, f_a, as, sc, od);
+      if (adaptive_dev) {
+        // an adaptive set (shares that move with the members' outcomes): drawn and adapted on the device, every chain's state
+        // starting from its rung's clone (the same bits the host path would start from)
+        const int L = as.K + as.K_inner;
+        std::vector<double> S((size_t)Ntemps * L), O(S.size()), Wt((size_t)Ntemps * W * L), Th(Wt.size());
+        std::vector<int32_t> B((size_t)Ntemps * W * 2), Cn(B.size());
+        for (int i = 0; i < Ntemps; i++) {
+          std::copy(sc.begin(), sc.end(), S.begin() + (size_t)i * L);
+          std::copy(od.begin(), od.end(), O.begin() + (size_t)i * L);
+          std::vector<double> w, th;
+          std::vector<int> bits, cnt;
+          ((proposal_distribution_set*)props[i])->adapt_state(w, th, bits, cnt);
+          for (int k = 0; k < W; k++) {
+            const size_t c = (size_t)i * W + k;
+            std::copy(w.begin(), w.end(), Wt.begin() + c * L);
+            std::copy(th.begin(), th.end(), Th.begin() + c * L);
+            B[2 * c] = bits[0]; B[2 * c + 1] = bits[1]; Cn[2 * c] = cnt[0]; Cn[2 * c + 1] = cnt[1];
+          }
+        }
+        ptm_check(ptm_set_proposal_adaptive(eng, &as, S.data(), O.data(), Wt.data(), Th.data(), B.data(), Cn.data()), "set_proposal_adaptive");
+      } else if (proposal.device_describe_mixture(dim, cum, sc, od)) {   // a proposal_distribution_set of scaled Gaussians
         const int K = (int)cum.size();
         std::vector<double> C((size_t)Ntemps * K), S(C.size()), O(C.size());
         for (int i = 0; i < Ntemps; i++)
@@ -2547,6 +2671,24 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   // chain::report_prop (chain.cc:2096-2109 flavour): every rung's proposal report, replica 0
   std::string report_prop(int style = 0) override {
     std::ostringstream ss;
+    if (adaptive_dev && !host_mode) {
+      // the device's adaptive shares (replica 0) into the rungs' clones, which then report them
+      // (the shares are not part of a checkpoint -- as on the host path and in the reference -- and start afresh on a restart)
+      const size_t N = (size_t)Ntemps * W;
+      std::vector<double> w, th;
+      std::vector<int> b0, c0;
+      ((proposal_distribution_set*)props[0])->adapt_state(w, th, b0, c0);
+      const size_t L = w.size();
+      std::vector<double> Wt(N * L), Th(N * L);
+      std::vector<int32_t> B(N * 2), Cn(N * 2);
+      ptm_check(ptm_batch_begin(eng), "report_prop");
+      ptm_check(ptm_get_proposal_adapt_state(eng, Wt.data(), Th.data(), B.data(), Cn.data()), "report_prop");
+      ptm_check(ptm_batch_end(eng), "report_prop");
+      for (int i = 0; i < Ntemps && i < (int)props.size(); i++) {
+        const size_t c = (size_t)i * W;   // (walker 0 of this engine: replica 0)
+        ((proposal_distribution_set*)props[i])->set_adapt_state(&Wt[c * L], &Th[c * L], &B[2 * c], &Cn[2 * c]);
+      }
+    }
     for (int i = 0; i < Ntemps && i < (int)props.size(); i++) ss << "  T=" << 1 / cur_beta(i, 0) << ": " << props[i]->report(style) << "\n";
     return ss.str();
   }
