@@ -357,7 +357,10 @@ enum {
   PTM_ARR_NACCEPT = 4,/* int32 */
   PTM_ARR_LAST_TYPE = 5, /* int32 */
   PTM_ARR_NHIST = 6,  /* int64: add_state calls */
-  PTM_ARR_NSIZE = 7   /* int64: history rows (chain.cc:935-946) */
+  PTM_ARR_NSIZE = 7,  /* int64: history rows (chain.cc:935-946) */
+  PTM_ARR_ROW_LABELS = 8 /* int32, a debug view: the rung slot of the device's row array that holds each chain's row.  Big populations
+                          * exchange these labels instead of 256-byte rows; every call that reads or writes the states puts the rows
+                          * back first (then: the chain's own rung).  This call reads the table as it stands. */
 };
 int ptm_get_states(ptm_engine* e, double* X);
 int ptm_get_array(ptm_engine* e, int which, void* out);

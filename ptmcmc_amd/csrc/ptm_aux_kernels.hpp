@@ -18,7 +18,8 @@ constexpr int PART_CHUNK = 16384;   // walkers per block: 1024 threads x 16 touc
 // moving chain, every rung exchanged once): the engine counts those steps and adds them to all of nhist in one pass when
 // somebody needs the array (nhist_flush_kernel).  Only a rung exchanged twice in the step gets its extra add at once.
 __global__ __launch_bounds__(1024) void partition_kernel(int W, int rung0, int nchunk, unsigned char* __restrict__ touch,
-                                                         unsigned int* __restrict__ nhist, int* __restrict__ cidx, int* __restrict__ ccnt) {
+                                                         unsigned int* __restrict__ nhist, int* __restrict__ cidx, int* __restrict__ ccnt,
+                                                         const unsigned short* __restrict__ rowof) {
   extern __shared__ int plist[];   // [PART_CHUNK] the block's listed walkers, then written out in one coalesced sweep
   __shared__ int wsum[16];
   __shared__ int sbase, stotal;
@@ -55,10 +56,16 @@ __global__ __launch_bounds__(1024) void partition_kernel(int W, int rung0, int n
   }
   __syncthreads();
   if (in) {
+    // row labels (rowof, W <= 65536): the listed entry carries the rung slot that holds the chain's row, walker | slot << 16
+    unsigned int slots[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rowof && zmask) {
+      const uint4 a = *reinterpret_cast<const uint4*>(rowof + c0), b = *reinterpret_cast<const uint4*>(rowof + c0 + 8);
+      slots[0] = a.x; slots[1] = a.y; slots[2] = a.z; slots[3] = a.w; slots[4] = b.x; slots[5] = b.y; slots[6] = b.z; slots[7] = b.w;
+    }
     int pos = wsum[threadIdx.x >> 6] + incl - mine;
 #pragma unroll
     for (int k = 0; k < 16; ++k)
-      if ((zmask >> k) & 1u) plist[pos++] = w0 + k;
+      if ((zmask >> k) & 1u) plist[pos++] = (w0 + k) | (int)(slots[k >> 1] >> (16 * (k & 1)) << 16);
     if (zmask != 0xFFFFu) *reinterpret_cast<uint4*>(touch + c0) = make_uint4(0, 0, 0, 0);
     if (twice) {
 #pragma unroll
@@ -69,6 +76,50 @@ __global__ __launch_bounds__(1024) void partition_kernel(int W, int rung0, int n
   __syncthreads();
   int* out = cidx + (size_t)rl * W + sbase;
   for (int i = threadIdx.x; i < stotal; i += 1024) out[i] = plist[i];
+}
+// Row labels back to the identity, the rows back to their own rungs (flush_rows of the engine): in place, one block per walker.  The
+// walker's labels go to LDS (L[r]: the slot that holds rung r's row, a permutation of the rungs); every displaced rung looks along its
+// cycle for a smaller member -- the one that finds none leads it -- and a 16-lane group carries a row (16 bytes a lane and 32 doubles)
+// along each led cycle: rung r's slot takes the row of slot L[r], then that slot its own, ... and the last one the leader's old row.
+// Cycles are disjoint, so the groups never meet.  Dynamic LDS: Nt labels + Nt leaders (16 bit each).
+__global__ __launch_bounds__(256) void restore_rows_kernel(double* __restrict__ x, unsigned short* __restrict__ rowof, int W, int Nt, int DP) {
+  extern __shared__ unsigned short rr_lds[];
+  __shared__ int nlead;
+  unsigned short* L = rr_lds;
+  unsigned short* lead = rr_lds + Nt;
+  const int w = xcd_walker(blockIdx.x, W);
+  if (threadIdx.x == 0) nlead = 0;
+  for (int r = threadIdx.x; r < Nt; r += 256) L[r] = rowof[(size_t)r * W + w];
+  __syncthreads();
+  for (int r = threadIdx.x; r < Nt; r += 256) {
+    int c = L[r];
+    if (c == r) continue;
+    int guard = 0;
+    while (c > r && ++guard <= Nt) c = L[c];
+    if (c == r) lead[atomicAdd(&nlead, 1)] = (unsigned short)r;
+  }
+  __syncthreads();
+  const int n = nlead, g = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  for (int k = g; k < n; k += 16) {
+    const int r = lead[k];
+    for (int hc = 2 * sub; hc < DP; hc += 32) {
+      const d2_t carry = *reinterpret_cast<const d2_t*>(x + ((size_t)r * W + w) * DP + hc);
+      int cur = r;
+      for (int guard = 0; guard <= Nt; ++guard) {
+        const int src = L[cur];
+        d2_t* dst = reinterpret_cast<d2_t*>(x + ((size_t)cur * W + w) * DP + hc);
+        if (src == r) { *dst = carry; break; }
+        *dst = *reinterpret_cast<const d2_t*>(x + ((size_t)src * W + w) * DP + hc);
+        cur = src;
+      }
+    }
+  }
+  for (int r = threadIdx.x; r < Nt; r += 256)
+    if (L[r] != r) rowof[(size_t)r * W + w] = (unsigned short)r;
+}
+__global__ __launch_bounds__(256) void identity_rows_kernel(unsigned short* __restrict__ rowof, int W, size_t Nc) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c < Nc) rowof[c] = (unsigned short)(c / (size_t)W);
 }
 // adds `n` to every chain's add_state counter (the steps the compacted sweep did not count one by one)
 __global__ __launch_bounds__(256) void nhist_flush_kernel(unsigned int* __restrict__ nhist, size_t Nc, unsigned int n) {

@@ -77,6 +77,10 @@ struct Decide {
   double* betaC_direct; // [Nc] few ladders: the chain-indexed image is written here as well (no transposition launch); else null
   double* beta_add;     // [Nc] with history / MAP tracking: the temperature each touched rung had at its last add_state of
                         // the phase (the sweep kernel saves that row); null otherwise
+  // Row labels (whole-ladder engines, big populations, no history / MAP): rowof[rung * W + walker] = the physical rung slot of x
+  // that holds the rung's row.  An accepted exchange then permutes 2-byte labels and no row moves; ll / lp stay indexed by
+  // logical chain and move as ever.  null: rows move.
+  unsigned short* rowof;
 };
 constexpr int HIST_DST = -(1 << 30);   // move-list destination code: HIST_DST - c = "into chain c's history"
 constexpr int MAP_DST = -(1 << 29);    //                             MAP_DST - c  = "chain c's new MAP" (c < 2^29)
@@ -767,6 +771,37 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   }
   __syncthreads();
   const int nmv = cnt[1];
+  if (p.rowof && nmv <= MVCAP) {
+    // ---- labelled rows: every listed move is local -> local (the whole ladder is here, nothing is recorded); the rungs exchange
+    //      their labels and scalars, the rows stay where they are.  Same discipline as below: every read of every thread has
+    //      landed before the first write (the moves form cycles over this ladder's own entries).
+    constexpr int NR = (MVCAP + DECIDE_THREADS - 1) / DECIDE_THREADS;
+    unsigned short lb[NR];
+    double sl[NR], sp[NR];
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+      const int j = lane + q * DECIDE_THREADS;
+      lb[q] = 0; sl[q] = 0.0; sp[q] = p.lp_const;
+      if (j < nmv) {
+        lb[q] = p.rowof[gs[j]];
+        sl[q] = llc[p.r0 + gd[j] / p.W];
+        if (!p.lp_is_const) sp[q] = p.lp[gs[j]];
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+      const int j = lane + q * DECIDE_THREADS;
+      if (j < nmv) {
+        const int d = gd[j];
+        p.rowof[d] = lb[q];
+        p.ll[d] = sl[q];
+        if (!p.lp_is_const) p.lp[d] = sp[q];
+      }
+    }
+    return;
+  }
   if (nmv > FCAP && nmv <= MVCAP) {   // too long for this block's registers: move_kernel takes it from here
     for (int j = lane; j < nmv; j += DECIDE_THREADS) {
       p.mv_src[(size_t)w * MVCAP + j] = gs[j];
@@ -916,9 +951,21 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
           row[DP + 3] = 0.0;
         }
       }
+      if (p.rowof) {   // labelled rows: the label takes the row's place in the walk below
+        const unsigned short carry = p.rowof[c0];
+        int cur = r;
+        for (int guard = 0; guard <= Nt; ++guard) {
+          const int src = perm[cur];
+          const int cc = (cur - p.r0) * p.W + w;
+          if (src == r) { p.rowof[cc] = carry; break; }
+          if (src < p.r0 || src >= r1) break;
+          p.rowof[cc] = p.rowof[(src - p.r0) * p.W + w];
+          cur = src;
+        }
+      }
       // one element of the row at a time (x[0..DP), llike, lprior), the head's old value carried in a register: no private
       // array -- a row-sized one would cost EVERY launch of this kernel a kilobyte of scratch per lane
-      for (int el = 0; el < DP + 2; ++el) {
+      for (int el = p.rowof ? DP : 0; el < DP + 2; ++el) {
         auto at = [&](int c) -> double* { return el < DP ? X + (size_t)c * DP + el : (el == DP ? p.ll + c : p.lp + c); };
         const double carry = *at(c0);
         int cur = r;

@@ -66,7 +66,7 @@ struct ptm_engine {
   bool own_stream = false;
   uint64_t step = 0;
   // device state
-  double *x = nullptr, *ll = nullptr, *lp = nullptr;   // rows [Nc][DP] and per-chain scalars, updated in place
+  double *xdev = nullptr, *ll = nullptr, *lp = nullptr;   // rows [Nc][DP] (read and written through xrows(), below) and per-chain scalars, updated in place
   int *ntries = nullptr, *naccept = nullptr, *last_type = nullptr, *err = nullptr;
   int *arr_below = nullptr, *arr_above = nullptr;
   int *mv_src = nullptr, *mv_dst = nullptr, *mv_n = nullptr;   // per-ladder move lists (exchange kernel -> move kernel)
@@ -131,6 +131,11 @@ struct ptm_engine {
   int *cidx = nullptr, *ccnt = nullptr;
   bool touched = false;
   bool compact_step = false;   // this step's (partial) sweeps are compacted
+  // row labels (ptm_decide.hpp): [Nc] the rung slot of xdev that holds each chain's row.  Only the exchange kernel and the compacted
+  // sweep of a labelled step know them; everybody else reaches the rows through xrows(), which puts them back first (flush_rows).
+  unsigned short* rowof = nullptr;
+  bool rows_labelled = false;   // the labels may differ from the identity
+  bool label_step = false;      // this step's exchange phase went by labels: its sweep must be the compacted one
   ShardComm* shard = nullptr;   // native RCCL sharding (ptm_shard_*)
   // recovery of runs longer than a halo (ptm_set_shard_map): the shards' ends, the nominal halo, per-ladder flags | count
   int* shard_ends = nullptr;
@@ -239,6 +244,15 @@ static int upload(T* d, const T* h, size_t n, hipStream_t s) {
   return PTM_OK;
 }
 
+// Row labels back to the identity and the rows back to their own rungs, in place (restore_rows_kernel; 1024 rungs x 16384 walkers
+// of 32 dimensions: see DESIGN 3.2 for its cost).  Queued on the stream; a failed launch stays with the runtime for the next check.
+static void flush_rows(ptm_engine* e);
+// the rows [Nc][DP], every chain's at its own place: what every reader and writer outside a labelled step takes
+static double* xrows(ptm_engine* e) {
+  if (e->rows_labelled) flush_rows(e);
+  return e->xdev;
+}
+
 extern "C" const char* ptm_last_error(void) { return g_err.c_str(); }
 extern "C" int ptm_abi_version(void) { return PTM_ABI_VERSION; }
 
@@ -328,8 +342,8 @@ static int build_engine(ptm_engine* e, const ptm_config* cfg) {
   if (cfg->stream) e->stream = (hipStream_t)cfg->stream;
   else { HIPCHK(hipStreamCreate(&e->stream)); e->own_stream = true; }
   const size_t Nc = e->Nc, D = e->DP;  // every per-dimension table is padded to DP
-  if ((rc = dalloc(&e->x, Nc * D)) || (rc = dalloc(&e->ll, Nc)) || (rc = dalloc(&e->lp, Nc))) return rc;
-  HIPCHK(hipMemsetAsync(e->x, 0, Nc * D * 8, e->stream));
+  if ((rc = dalloc(&e->xdev, Nc * D)) || (rc = dalloc(&e->ll, Nc)) || (rc = dalloc(&e->lp, Nc))) return rc;
+  HIPCHK(hipMemsetAsync(e->xdev, 0, Nc * D * 8, e->stream));
   if ((rc = dalloc(&e->ntries, Nc)) || (rc = dalloc(&e->naccept, Nc)) || (rc = dalloc(&e->last_type, Nc)) ||
       (rc = dalloc(&e->arr_below, (size_t)cfg->n_walkers)) || (rc = dalloc(&e->mv_src, (size_t)cfg->n_walkers * MVCAP)) ||
       (rc = dalloc(&e->mv_dst, (size_t)cfg->n_walkers * MVCAP)) || (rc = dalloc(&e->mv_n, (size_t)cfg->n_walkers)) ||
@@ -477,7 +491,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
   if (e->shared_handover) e->xprop = e->llike_new = nullptr, e->hastings = nullptr, e->htype = nullptr, e->hvalid = e->acc_out = nullptr;   // (these are the pinned vectors)
   if (e->hist_on_host) e->hist.x = e->hist.ll = e->hist.lp = e->hist.beta = nullptr, e->hist.meta = nullptr;
   for (auto& b : e->host_blocks) (void)hipHostFree(b.first);
-  void* ptrs[] = {e->x, e->ll, e->lp, e->ntries, e->naccept, e->last_type, e->arr_below, e->arr_above, e->mv_src, e->mv_dst, e->mv_n,
+  void* ptrs[] = {e->xdev, e->rowof, e->ll, e->lp, e->ntries, e->naccept, e->last_type, e->arr_below, e->arr_above, e->mv_src, e->mv_dst, e->mv_n,
                   e->err, e->nhist, e->swap_cnt, e->touch, e->swap_log, e->hist.x, e->hist.ll, e->hist.lp, e->hist.meta, e->map.lpost, e->map.ll, e->map.lp, e->map.x, e->blo,
                   e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
@@ -727,7 +741,7 @@ static int call_user_prior(ptm_engine* e, const pinned_vector<double>& rows, con
   e->prior_cb(e->prior_user, e->h_batch.data(), (int)n, (int)D, out.data());
   return PTM_OK;
 }
-// host prior: the log-priors of the states now in e->x (their rows in e->h_xprop) replace what the device prior gave -- except
+// host prior: the log-priors of the states now in e->xdev (their rows in e->h_xprop) replace what the device prior gave -- except
 // where that is -inf by the state's invalidity (the device's flat stand-in prior has no other way to say -inf)
 static int host_prior_of_states(ptm_engine* e) {
   const size_t Nc = e->Nc;
@@ -1200,7 +1214,7 @@ extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double
 }
 
 // ---- kernel argument block ----------------------------------------------------------------------------------
-static Dev make_dev(ptm_engine* e) {
+static Dev make_dev(ptm_engine* e, bool labelled = false) {   // labelled: the compacted sweep of a labelled step, which finds the rows by their labels
   Dev p;
   memset(&p, 0, sizeof p);
   p.D = e->D; p.DP = e->DP; p.Nt = e->Nt; p.r0 = e->r0; p.nloc = e->nloc; p.W = e->W; p.Nc = e->Nc; p.w_off = e->cfg.walker_begin;
@@ -1216,7 +1230,7 @@ static Dev make_dev(ptm_engine* e) {
   p.de_snooker = e->de.snooker; p.de_gamma_one = e->de.gamma_one_frac; p.de_gamma_div = e->de.reduce_gamma; p.de_ignore = e->de.ignore_frac;
   p.de_gamma_std = e->de_on ? 1.68 / std::sqrt((double)e->D) / e->de.reduce_gamma : 0.0;   // (the reference's own expression, proposal_distribution.cc:492)
   p.betaC = e->betaC; p.beta_add = e->beta_add; p.beta_w = e->beta_w;
-  p.x = e->x; p.ll = e->ll; p.lp = e->lp;
+  p.x = labelled ? e->xdev : xrows(e); p.ll = e->ll; p.lp = e->lp;
   p.ntries = e->ntries; p.naccept = e->naccept; p.last_type = e->last_type; p.nhist = e->nhist;
   p.touch = e->touch; p.err = e->err;
   p.hist = e->hist;
@@ -1268,6 +1282,26 @@ static int flush_nhist(ptm_engine* e) {
   HIPCHK(hipGetLastError());
   e->nhist_pending = 0;
   return PTM_OK;
+}
+
+// the conditions of the compacted sweep (PTM_COMPACT=0 switches it off) but for `touched`: an exchange phase ran since the last sweep
+static bool compact_applies(const ptm_engine* e, const SweepSel& sel) {
+  static const bool compact_ok = [] { const char* v = getenv("PTM_COMPACT"); return !(v && *v == '0'); }();
+  // ... and the box-bounds build (uniform priors, open / limit bounds, a mean, one-dimensional moves, scale mixtures, evolving ladders)
+  const bool gen1 = sel.uni && !sel.callback && !sel.host_prop && !sel.de && !sel.ada && e->all_uniform && (!e->has_bounds || e->bounds_box);
+  return compact_ok && e->DP == 32 && (sel.simple || gen1) && !e->hist.rungs && !e->map.rungs && !getenv("PTM_FORCE_VALU") &&
+         e->W >= 1024 && e->nloc <= 4096;   // (the same answer for every partial sweep of a step)
+}
+// Row labels: does a whole step of this engine (exchange phase, then ONE sweep of all rungs) exchange labels instead of rows?  Where its
+// sweep is the compacted one, the engine holds the whole ladder, and a walker fits the 16 bits a list entry leaves it.
+// PTM_ROW_LABELS=0 switches it off.
+static bool row_labels_apply(const ptm_engine* e) {
+  static const bool labels_ok = [] { const char* v = getenv("PTM_ROW_LABELS"); return !(v && *v == '0'); }();
+  return labels_ok && e->nloc == e->Nt && !e->shard && e->W <= 65536 && e->Nt > 1 && compact_applies(e, sweep_sel(e));
+}
+static void flush_rows(ptm_engine* e) {
+  e->rows_labelled = false;
+  hipLaunchKernelGGL(restore_rows_kernel, dim3(e->W), dim3(256), (size_t)4 * e->nloc, e->stream, e->xdev, e->rowof, e->W, e->nloc, e->DP);
 }
 
 // one fused MH sweep over local rungs [rung0, rung0 + nr); `last` closes the step (the step count is the RNG position)
@@ -1433,7 +1467,9 @@ static int devlike_debug(ptm_engine* e, const double* X, int n, double* llike) {
 #define NO_DEVLIKE(e, name) do { if ((e) && (e)->dfn) return fail(PTM_ERR_UNSUPPORTED, name " with a device likelihood is not built (rung-sharded steps)"); } while (0)
 
 static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = true) {
-  Dev p = make_dev(e);
+  const bool labelled = e->label_step;   // (set by this step's exchange phase under the very conditions of the compacted sweep below)
+  e->label_step = false;
+  Dev p = make_dev(e, labelled);
   if (nr < 0) nr = e->nloc - rung0;
   if (rung0 < 0 || nr < 0 || rung0 + nr > e->nloc) return fail(PTM_ERR_INVALID, "rung range out of the shard");
   p.c_begin = rung0 * e->W; p.c_end = (rung0 + nr) * e->W;
@@ -1454,22 +1490,19 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   const SweepSel sel = sweep_sel(e);
   if (e->betaC_stale && !lean_ev_sweeps(e)) { int rc = ensure_betaC(e); if (rc) return rc; }   // (a build that reads the chain-indexed temperatures)
   // Compacted sweep: after an exchange phase ~1/6 of a long ladder's chains make no move; the lean MFMA build on a big
-  // population then visits the moving chains only (partition_kernel packs them per rung).  PTM_COMPACT=0 switches it off.
-  static const bool compact_ok = [] { const char* v = getenv("PTM_COMPACT"); return !(v && *v == '0'); }();
-  // ... and the box-bounds build (uniform priors, open / limit bounds, a mean, one-dimensional moves, scale mixtures, evolving ladders)
-  const bool gen1 = sel.uni && !sel.callback && !sel.host_prop && !sel.de && !sel.ada && e->all_uniform && (!e->has_bounds || e->bounds_box);
-  const bool compact = compact_ok && e->touched && e->DP == 32 && (sel.simple || gen1) && !e->hist.rungs && !e->map.rungs && !getenv("PTM_FORCE_VALU") &&
-                       e->W >= 1024 && e->nloc <= 4096;   // (the same answer for every partial sweep of a step)
+  // population then visits the moving chains only (partition_kernel packs them per rung).
+  const bool compact = e->touched && compact_applies(e, sel);
+  if (labelled && !(compact && rung0 == 0 && nr == e->nloc)) return fail(PTM_ERR_HIP, "internal: a labelled exchange phase without its compacted sweep");
   if (!compact) { int rc = flush_nhist(e); if (rc) return rc; }
   if (compact) {
     if (!e->cidx) { int rc; if ((rc = dalloc(&e->cidx, (size_t)e->Nc)) || (rc = dalloc(&e->ccnt, (size_t)e->nloc))) return rc; }
     HIPCHK(hipMemsetAsync(e->ccnt + rung0, 0, (size_t)nr * sizeof(int), e->stream));
     const int nchunk = (e->W + PART_CHUNK - 1) / PART_CHUNK;
     hipLaunchKernelGGL(partition_kernel, dim3((unsigned)((size_t)nr * nchunk)), dim3(1024), (size_t)PART_CHUNK * sizeof(int), e->stream, e->W, rung0, nchunk, e->touch, e->nhist,
-                       e->cidx, e->ccnt);
+                       e->cidx, e->ccnt, labelled ? (const unsigned short*)e->rowof : nullptr);
     e->compact_step = true;   // (every partial sweep of this step goes the same way: the step is counted once, at its end)
     HIPCHK(hipGetLastError());
-    p.cidx = e->cidx; p.ccnt = e->ccnt;
+    p.cidx = e->cidx; p.ccnt = e->ccnt; p.cidx_slot = labelled ? 1 : 0;
   }
   // the timed bracket holds the sweep kernel alone (its name: ptm_sweep_kernel_name): the list fill and partition_kernel of a
   // compacted sweep stay outside, so that the events' mean is what rocprofv3 reports for that kernel
@@ -1495,7 +1528,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     // host-side proposals: fetch the rows and the exchange phase's touch flags, let the host propose for every chain that
     // moves this step, hand the proposals (whole states), their log-Hastings ratios, types and validity to the kernel
     const size_t Nc = e->Nc, D = e->D, DP = e->DP;
-    HIPCHK(hipMemcpyAsync(e->h_rows.data(), e->x, Nc * DP * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_rows.data(), xrows(e), Nc * DP * 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(e->h_touch.data(), e->touch, Nc, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->p_pick.clear();
@@ -1530,7 +1563,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     p.xprop = e->dl_xprop; p.lprior_new = e->dl_lprior_new; p.gate = e->dl_gate; p.llike_new = e->dl_llike_new;
     p.mode = 1;
     HIPCHK(launch(p));
-    { const int rc = devlike_eval(e, e->dl_gate, 2, 2, e->dl_xprop, e->x, e->dl_llike_new, nullptr, e->dl_lprior_new, true); if (rc) return rc; }
+    { const int rc = devlike_eval(e, e->dl_gate, 2, 2, e->dl_xprop, xrows(e), e->dl_llike_new, nullptr, e->dl_lprior_new, true); if (rc) return rc; }
     p.mode = 2;
     HIPCHK(launch(p));
   } else if (!e->cb) {
@@ -1590,15 +1623,16 @@ static int ensure_betaC(ptm_engine* e) {
 }
 
 static Decide make_decide(ptm_engine* e, const double* ll_below, const double* ll_above, int H, double* send_up, double* send_down,
-                          const double* ll_all = nullptr, const double* lp_all = nullptr) {
+                          const double* ll_all = nullptr, const double* lp_all = nullptr, bool labels = false) {
   Decide p;
   memset(&p, 0, sizeof p);
+  p.rowof = labels ? e->rowof : nullptr;
   p.ll_all = ll_all; p.lp_all = lp_all;
   p.shard_ends = e->shard_ends; p.nshards = e->nshards; p.halo_nominal = e->halo_nominal;
   p.redo_flag = e->redo_flag; p.redo_count = e->redo_flag ? e->redo_flag + e->W : nullptr;
   p.DP = e->DP; p.Nt = e->Nt; p.r0 = e->r0; p.nloc = e->nloc; p.W = e->W; p.Nc = e->Nc; p.ms = e->ms; p.w_off = e->cfg.walker_begin;
   p.seed = e->cfg.seed; p.step = e->step; p.thresh = e->thresh;
-  p.beta = e->beta; p.ll_below = ll_below; p.ll_above = ll_above; p.H = ll_above ? H : 0; p.x = e->x; p.ll = e->ll; p.lp = e->lp;
+  p.beta = e->beta; p.ll_below = ll_below; p.ll_above = ll_above; p.H = ll_above ? H : 0; p.x = labels ? e->xdev : xrows(e); p.ll = e->ll; p.lp = e->lp;
   p.touch = e->touch; p.arr_below = e->arr_below; p.arr_above = e->arr_above;
   p.swap_log = e->swap_log + (size_t)e->log_head * e->W * e->ms; p.send_up = send_up; p.send_down = send_down; p.row_cap = e->row_cap; p.err = e->err;
   p.mv_src = e->mv_src; p.mv_dst = e->mv_dst; p.mv_n = e->mv_n;
@@ -1617,8 +1651,17 @@ static Decide make_decide(ptm_engine* e, const double* ll_below, const double* l
 }
 
 static int launch_decide(ptm_engine* e, const double* ll_below, const double* ll_above, int H, double* send_up, double* send_down,
-                         const double* ll_all = nullptr, const double* lp_all = nullptr, bool redo = false) {
-  Decide p = make_decide(e, ll_below, ll_above, H, send_up, send_down, ll_all, lp_all);
+                         const double* ll_all = nullptr, const double* lp_all = nullptr, bool redo = false, bool labels = false) {
+  // labels: a whole step of a whole-ladder engine whose sweep will be the compacted one (two_launch_steps) -- the kernel exchanges
+  // row labels, and never looks at the rows
+  if (labels && !e->rowof) {
+    int rc = dalloc(&e->rowof, (size_t)e->Nc);
+    if (rc) return rc;
+    hipLaunchKernelGGL(identity_rows_kernel, dim3((unsigned)(((size_t)e->Nc + 255) / 256)), dim3(256), 0, e->stream, e->rowof, e->W, (size_t)e->Nc);
+    HIPCHK(hipGetLastError());
+  }
+  Decide p = make_decide(e, ll_below, ll_above, H, send_up, send_down, ll_all, lp_all, labels);
+  if (labels) { e->rows_labelled = true; e->label_step = true; }
   p.redo_only = redo ? 1 : 0;
   if (!redo && e->log_pending >= PTM_LOG_RING) { int rc = fold_swap_log(e); if (rc) return rc; }
   if (redo) {   // the second pass of the SAME step: the log slot, the messages and the move lists are the first pass's
@@ -1663,9 +1706,9 @@ static int launch_decide(ptm_engine* e, const double* ll_below, const double* ll
   // a pick lists at most four row moves (two rungs, each a local move and / or a departure) and one in-between row each for
   // the history and the MAP: short ladders
   // can never overflow the 64-thread block's own moves
-  if (per_pick * e->ms <= 64) return PTM_OK;
+  if (per_pick * e->ms <= 64 || labels) return PTM_OK;   // (labels: the block exchanged them itself whatever the list's length)
   Move m;
-  m.DP = e->DP; m.W = e->W; m.row_cap = e->row_cap; m.x = e->x; m.ll = e->ll; m.lp = e->lp; m.send_up = send_up; m.send_down = send_down;
+  m.DP = e->DP; m.W = e->W; m.row_cap = e->row_cap; m.x = xrows(e); m.ll = e->ll; m.lp = e->lp; m.send_up = send_up; m.send_down = send_down;
   m.mv_src = e->mv_src; m.mv_dst = e->mv_dst; m.mv_n = e->mv_n; m.err = e->err;
   m.hist = e->hist; m.add_every_n = e->cfg.add_every_n; m.nhist = e->nhist;
   m.naccept = e->naccept; m.ntries = e->ntries; m.last_type = e->last_type;
@@ -1682,7 +1725,7 @@ static int launch_decide(ptm_engine* e, const double* ll_below, const double* ll
 static int launch_install(ptm_engine* e, const double* recv_below, const double* recv_above) {
   if (!recv_below && !recv_above) return PTM_OK;
   Install q;
-  q.DP = e->DP; q.W = e->W; q.row_cap = e->row_cap; q.x = e->x; q.ll = e->ll; q.lp = e->lp;
+  q.DP = e->DP; q.W = e->W; q.row_cap = e->row_cap; q.x = xrows(e); q.ll = e->ll; q.lp = e->lp;
   q.recv_below = recv_below; q.recv_above = recv_above; q.arr_below = e->arr_below; q.arr_above = e->arr_above; q.err = e->err;
   e->touched = true;
   hipLaunchKernelGGL(install_kernel, dim3((e->row_cap + 15) / 16, 2), dim3(256), 0, e->stream, q);
@@ -1729,14 +1772,14 @@ static int reset_counters(ptm_engine* e) {
   e->step = 0;
   if (e->map.rungs) {    // MAP = the initial state (MH_chain::initialize -> add_state)
     if (!e->have_ladder) return fail(PTM_ERR_INVALID, "set the ladder before the states when tracking the MAP (ptm_set_ladder)");
-    hipLaunchKernelGGL(map_init_kernel, dim3((e->map.MC + 255) / 256), dim3(256), 0, e->stream, e->map, e->DP, e->W, e->r0, e->beta, e->x, e->ll,
+    hipLaunchKernelGGL(map_init_kernel, dim3((e->map.MC + 255) / 256), dim3(256), 0, e->stream, e->map, e->DP, e->W, e->r0, e->beta, xrows(e), e->ll,
                        e->lp);
     HIPCHK(hipGetLastError());
   }
   if (e->hist.rungs) {   // history row 0 = the initial state (chain.cc:871-875)
     HIPCHK(hipMemsetAsync(e->hist.meta, 0xFF, (size_t)e->hist.cap * e->hist.HC * sizeof(int4), e->stream));
     if (e->hist.beta && !e->have_ladder) return fail(PTM_ERR_INVALID, "set the ladder before the states (ptm_set_ladder)");
-    hipLaunchKernelGGL(hist_init_kernel, dim3((e->hist.HC + 255) / 256), dim3(256), 0, e->stream, e->hist, e->DP, e->x, e->ll, e->lp,
+    hipLaunchKernelGGL(hist_init_kernel, dim3((e->hist.HC + 255) / 256), dim3(256), 0, e->stream, e->hist, e->DP, xrows(e), e->ll, e->lp,
                        e->naccept, e->ntries, e->last_type, e->beta, e->betaC, e->W, e->r0);
     HIPCHK(hipGetLastError());
   }
@@ -1783,18 +1826,18 @@ extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llik
   const size_t Nc = e->Nc, D = e->D, DP = e->DP;
   const std::vector<double> rows = pad_rows(X, Nc, D, DP);
   int rc;
-  if ((rc = upload(e->x, rows.data(), Nc * DP, e->stream))) return rc;
+  if ((rc = upload(xrows(e), rows.data(), Nc * DP, e->stream))) return rc;
   if (llike && (rc = upload(e->ll, llike, Nc, e->stream))) return rc;
-  if ((rc = run_eval(e, (int)Nc, e->x, nullptr, e->lp, e->ll, (llike || user_like(e)) ? 0 : 1))) return rc;
+  if ((rc = run_eval(e, (int)Nc, xrows(e), nullptr, e->lp, e->ll, (llike || user_like(e)) ? 0 : 1))) return rc;
   if (e->dfn) {
     // the device likelihood evaluates the (enforced) start states; the best posterior starts over with them
     if ((rc = devlike_reset_best(e))) return rc;
-    if (!llike && (rc = devlike_eval(e, nullptr, 0, 0, e->x, e->x, e->ll, nullptr, e->lp, true))) return rc;
+    if (!llike && (rc = devlike_eval(e, nullptr, 0, 0, xrows(e), xrows(e), e->ll, nullptr, e->lp, true))) return rc;
   }
   if (e->cb && !llike) {
     // MH_chain::add_state(s) with the 999 sentinel: the likelihood plug-in evaluates the (enforced) start states (chain.cc:925)
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(e->h_xprop.data(), e->x, Nc * DP * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(e->h_xprop.data(), xrows(e), Nc * DP * 8, hipMemcpyDeviceToHost));
     std::vector<size_t> all(Nc);
     for (size_t c = 0; c < Nc; ++c) all[c] = c;
     if ((rc = call_user(e, e->h_xprop, all, e->h_llbatch))) return rc;
@@ -1803,7 +1846,7 @@ extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llik
   if (e->prior_cb) {
     if (!e->cb) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior needs the host-callback likelihood (ptm_set_target_callback)");
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(e->h_xprop.data(), e->x, Nc * DP * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(e->h_xprop.data(), xrows(e), Nc * DP * 8, hipMemcpyDeviceToHost));
     if ((rc = host_prior_of_states(e))) return rc;
   }
   if ((rc = reset_counters(e))) return rc;
@@ -1830,15 +1873,15 @@ static int launch_init(ptm_engine* e, const Dev& p, long long attempt, unsigned 
     return PTM_OK;
   }
   switch (e->DP) {
-    case 4: HIPCHK(launch_init_4(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 8: HIPCHK(launch_init_8(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 16: HIPCHK(launch_init_16(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 32: HIPCHK(launch_init_32(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 64: HIPCHK(launch_init_64(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 128: HIPCHK(launch_init_128(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 256: HIPCHK(launch_init_256(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 512: HIPCHK(launch_init_512(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 1024: HIPCHK(launch_init_1024(p, e->x, e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 4: HIPCHK(launch_init_4(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 8: HIPCHK(launch_init_8(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 16: HIPCHK(launch_init_16(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 32: HIPCHK(launch_init_32(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 64: HIPCHK(launch_init_64(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 128: HIPCHK(launch_init_128(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 256: HIPCHK(launch_init_256(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 512: HIPCHK(launch_init_512(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
+    case 1024: HIPCHK(launch_init_1024(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
     default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
   }
   return PTM_OK;
@@ -1872,7 +1915,7 @@ extern "C" int ptm_init_from_prior_k(ptm_engine* e, int kdraw) {
     size_t left = Nc;
     for (long long a = 0; left && a < 100000; ++a) {
       if ((rc = launch_init(e, p, a, e->dl_gate))) return rc;
-      if ((rc = devlike_eval(e, e->dl_gate, 3, 1, e->x, nullptr, e->dl_llike_new, e->dl_gate, e->lp, true))) return rc;
+      if ((rc = devlike_eval(e, e->dl_gate, 3, 1, xrows(e), nullptr, e->dl_llike_new, e->dl_gate, e->lp, true))) return rc;
       HIPCHK(hipMemcpyAsync(hg.data(), e->dl_gate, Nc, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
       left = (size_t)std::count_if(hg.begin(), hg.end(), [](unsigned char g) { return g != 2; });
@@ -1889,7 +1932,7 @@ extern "C" int ptm_init_from_prior_k(ptm_engine* e, int kdraw) {
     for (long long a = 0; left && a < 100000; ++a) {
       if ((rc = launch_init(e, p, a, e->gate))) return rc;
       HIPCHK(copy_unless_shared(e->h_gate, e->gate, Nc, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipMemcpyAsync(e->h_xprop.data(), e->x, Nc * DP * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->h_xprop.data(), xrows(e), Nc * DP * 8, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
       std::vector<size_t> pick;
       for (size_t c = 0; c < Nc; ++c)
@@ -2262,7 +2305,7 @@ static int ladder_steps(ptm_engine* e, int n) {
 static int two_launch_steps(ptm_engine* e, int n) {
   int rc;
   for (int k = 0; k < n; ++k) {
-    if (e->Nt > 1 && (rc = launch_decide(e, nullptr, nullptr, 0, nullptr, nullptr))) return rc;
+    if (e->Nt > 1 && (rc = launch_decide(e, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, false, row_labels_apply(e)))) return rc;
     if ((rc = launch_sweep(e))) return rc;
   }
   return PTM_OK;
@@ -2690,7 +2733,7 @@ extern "C" int ptm_get_states(ptm_engine* e, double* X) {
   if (!e || !X) return fail(PTM_ERR_INVALID, "null argument");
   const size_t Nc = e->Nc, D = e->D, DP = e->DP;
   const unsigned char* s;
-  FETCH(s, e->x, Nc * DP * 8);
+  FETCH(s, xrows(e), Nc * DP * 8);
   e->fetch_after.push_back([=] { unpad_rows((const double*)s, Nc, D, DP, X); });
   return fetch_done(e);
 }
@@ -2734,6 +2777,16 @@ extern "C" int ptm_get_array(ptm_engine* e, int which, void* out) {
         int64_t* o = (int64_t*)out;
         for (size_t c = 0; c < Nc; ++c) o[c] = which == PTM_ARR_NHIST ? (int64_t)h[c] : 1 + ((int64_t)h[c] + N - 1) / N;
       });
+      break;
+    }
+    case PTM_ARR_ROW_LABELS: {   // as they stand: this call puts no row back
+      if (!e->rowof) {
+        const int W = e->W;
+        e->fetch_after.push_back([=] { for (size_t c = 0; c < Nc; ++c) ((int32_t*)out)[c] = (int32_t)(c / (size_t)W); });
+        break;
+      }
+      FETCH(s, e->rowof, Nc * 2);
+      e->fetch_after.push_back([=] { for (size_t c = 0; c < Nc; ++c) ((int32_t*)out)[c] = ((const unsigned short*)s)[c]; });
       break;
     }
     default: return fail(PTM_ERR_INVALID, "unknown array id %d", which);

@@ -148,8 +148,11 @@ struct Dev {
   // (whole states, row layout) with their log-Hastings ratio, type code and validity; acc_out gets the outcome
   // compacted sweep (lean MFMA build, ptm_mfma_kernel.hpp): per local rung the walkers that make a Metropolis move this
   // step, packed at cidx[rl * W ..) by partition_kernel; ccnt[rl] of them.  null: every chain is visited in place.
+  // cidx_slot: the engine keeps row labels (ptm_decide.hpp) -- an entry is walker | slot << 16, the chain's row sits at rung slot
+  // `slot` of x instead of its own rung.
   const int* cidx;
   const int* ccnt;
+  int cidx_slot;
   uint64_t init_base;            // init_prior_kernel: first attempt number of this initial draw (ptm_init_from_prior_k)
   int host_prop;
   const double* hastings;        // [Nc]

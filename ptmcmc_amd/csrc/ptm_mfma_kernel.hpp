@@ -198,7 +198,10 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
     if constexpr (CPT) return p.cidx[lbase + (i < nact ? i : nact - 1)];
     else return w0 + i;
   };
-  const int wl = walker_of(l);
+  // (row labels: a listed entry carries the rung slot of the chain's row above the walker -- split where it is used, two integer
+  //  operations, so that no register holds the slots)
+  const int wmask = (CPT && p.cidx_slot) ? 0xFFFF : -1;
+  const int wl = walker_of(l) & wmask;
   const bool dead = CPT && l >= nact;
   const int c = CPT ? rl * p.W + wl : c0s + l;   // "my" chain for the per-chain work
   int wq[4];   // the walkers this lane works for in the matrix products: chain 16 g + j of the wave, g = 0..3
@@ -212,7 +215,9 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   auto ask_rows = [&](int gpp, mf_d2 (&rv)[GG][4], mf_d2* (&rp)[GG]) {
 #pragma unroll
     for (int gg = 0; gg < GG; ++gg) {
-      rp[gg] = reinterpret_cast<mf_d2*>(p.x + ((size_t)rl * p.W + wq[GG * gpp + gg]) * DP) + q;   // piece t at [4t]
+      const int e = wq[GG * gpp + gg];
+      const int slot = (CPT && p.cidx_slot) ? (int)((unsigned int)e >> 16) : rl;
+      rp[gg] = reinterpret_cast<mf_d2*>(p.x + ((size_t)slot * p.W + (e & wmask)) * DP) + q;   // piece t at [4t]
 #pragma unroll
       for (int t = 0; t < 4; ++t) rv[gg][t] = rp[gg][4 * t];
     }
@@ -291,7 +296,7 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
       double z[GG][4];
 #pragma unroll
       for (int gg = 0; gg < GG; ++gg) {
-        const uint32_t stream = (uint32_t)(wq[GG * gp + gg] + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg;
+        const uint32_t stream = (uint32_t)((wq[GG * gp + gg] & wmask) + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg;
         const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + 4 * hb + qd));
         boxmuller(o.v0, o.v1, (const double*)lds_all, z[gg][0], z[gg][1]);
         boxmuller(o.v2, o.v3, (const double*)lds_all, z[gg][2], z[gg][3]);

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PTM_ENGINE_LIB") or os.path.join(_HERE, "libptm_engin
 BOUND_OPEN, BOUND_LIMIT, BOUND_REFLECT, BOUND_WRAP = 0, 1, 2, 3
 PRIOR_FLAT, PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_POLAR, PRIOR_COPOLAR, PRIOR_LOG = 0, 1, 2, 3, 4, 5
 PROP_DENSE, PROP_DIAG, PROP_LOWER = 0, 1, 2
-ARR_LLIKE, ARR_LPRIOR, ARR_LPOST, ARR_NTRIES, ARR_NACCEPT, ARR_LAST_TYPE, ARR_NHIST, ARR_NSIZE = range(8)
+ARR_LLIKE, ARR_LPRIOR, ARR_LPOST, ARR_NTRIES, ARR_NACCEPT, ARR_LAST_TYPE, ARR_NHIST, ARR_NSIZE, ARR_ROW_LABELS = range(9)
 FN_LOG, FN_EXP, FN_SIN_0_PI, FN_COS_HPI, FN_SQRT, FN_DIV, FN_SQRT_RAW = range(7)
 PRIOR_NAMES = {"uni": 1, "uniform": 1, "gauss": 2, "gaussian": 2, "pol": 3, "polar": 3, "cpol": 4, "copol": 4, "log": 5}
 
@@ -724,7 +724,7 @@ class Engine:
 
     def array(self, which):
         dt = {ARR_LLIKE: np.float64, ARR_LPRIOR: np.float64, ARR_LPOST: np.float64, ARR_NTRIES: np.int32,
-              ARR_NACCEPT: np.int32, ARR_LAST_TYPE: np.int32, ARR_NHIST: np.int64, ARR_NSIZE: np.int64}[which]
+              ARR_NACCEPT: np.int32, ARR_LAST_TYPE: np.int32, ARR_NHIST: np.int64, ARR_NSIZE: np.int64, ARR_ROW_LABELS: np.int32}[which]
         out = self._out(np.empty(self.Nc, dtype=dt))
         _chk(self.L.ptm_get_array(self.h, which, out.ctypes.data_as(C.c_void_p)))
         return out
@@ -737,6 +737,7 @@ class Engine:
     last_type = property(lambda s: s.array(ARR_LAST_TYPE))
     nhist = property(lambda s: s.array(ARR_NHIST))
     nsize = property(lambda s: s.array(ARR_NSIZE))
+    row_labels = property(lambda s: s.array(ARR_ROW_LABELS))   # debug: rung slot holding each chain's row (identity once the states were read)
 
     def swap_counts(self):
         n = self.W * max(self.Nt - 1, 1)
