@@ -451,6 +451,27 @@ typedef struct ptm_calibration {
 } ptm_calibration;
 int ptm_calibrate(ptm_engine* e, ptm_calibration* out);
 
+/* ---- effective sample size on the device ------------------------------------------------------------------------------
+ * chain::report_effective_samples (chain.cc:126-643) as the facade's ess_estimator restates it (ptmcmc_amd/host/ptmcmc_gpu.hh), for
+ * every walker of a recorded rung at once: a series is one chain's saved history, its first nfeat parameters are the features, and
+ * the sample of nominal step s is saved row 1 + s / add_every_n if the ring still holds it.  The kernels keep the host
+ * estimator's order of operations: ess and nwin / length carry its very bits.  The table of nfeat x windows x lags cells per series is
+ * built for chunks of series that fit a workspace of PTM_ESS_WORKSPACE_MB MiB (read per call; default 256), which the engine allocates
+ * at the first call and frees when it is destroyed.  The engine calls run on the engine's stream and wait for it.
+ * A series' length is its chain's own count of add_state calls (PTM_ARR_NHIST; a rung exchanged twice in a step makes one more, so
+ * the walkers of a rung differ): every series gets the windows of its own length, in the same launches; ptm_ess_report groups the
+ * series whose lengths lead to the same widths and strides (esslimit < 0: as good as always all of them).
+ * PTM_ERR_INVALID: no history ring, rung >= history_rungs, nfeat < 1 or > dim.  No reference counterpart for the population form. */
+/* one pass with fixed windows (ess_estimator::windowed) over the saved history of local rung `rung` (< history_rungs), every walker at once */
+int ptm_ess_windowed(ptm_engine* e, int rung, int nfeat, int width, int every, int burn, double* ess /*[W]*/, int32_t* nwin /*[W]*/);
+/* ess_estimator::report (width doubling / coarse-to-fine stride search of esslimit >= 0), width >= 1, every >= 1 */
+int ptm_ess_report(ptm_engine* e, int rung, int nfeat, int width, int every, double esslimit, double* ess /*[W]*/, int32_t* length /*[W]*/);
+/* the same on a caller's series, host array series[(t*nseries + s)*nfeat + f], t < n: no engine needed */
+int ptm_ess_series_windowed(int device, const double* series, int64_t n, int nseries, int nfeat, int width, int every, int burn, double* ess, int32_t* nwin);
+int ptm_ess_series_report(int device, const double* series, int64_t n, int nseries, int nfeat, int width, int every, double esslimit, double* ess, int32_t* length);
+/* 1 if the last ptm_ess_* call of this engine ran the device kernels (0 also where the series were too short for one window: nothing to launch) */
+int ptm_ess_last_on_device(ptm_engine* e);
+
 /* ---- verification hooks (used by tests/ only; evaluate device functions on arrays) ---------------------- */
 enum { PTM_FN_LOG = 0, PTM_FN_EXP = 1, PTM_FN_SIN_0_PI = 2, PTM_FN_COS_HPI = 3, PTM_FN_SQRT = 4, PTM_FN_DIV = 5,
        PTM_FN_SQRT_RAW = 6 };

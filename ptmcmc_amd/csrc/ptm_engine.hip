@@ -19,6 +19,7 @@
 #include "../../include/ptm_engine.h"
 #include "ptm_aux_kernels.hpp"
 #include "ptm_devlike_kernels.hpp"
+#include "ptm_ess_kernels.hpp"
 #include "ptm_launch.hpp"
 #include "ptm_shard_rccl.hpp"
 
@@ -188,6 +189,10 @@ struct ptm_engine {
   std::vector<double> h_batch, h_llbatch;
   unsigned char* h_gate = nullptr;   // view into h_xprop's tail
   unsigned long long *sums = nullptr, *h_sums = nullptr;   // ptm_get_counter_sums
+  // effective sample size (ptm_ess_*): the workspace (lag list, answers, one chunk's table), allocated at the first call and grown on demand
+  void* ess_ws = nullptr;
+  size_t ess_ws_bytes = 0;
+  int ess_on_device = 0;   // the last ptm_ess_* call of this engine ran the kernels
   // timing
   hipEvent_t t0 = nullptr, t1 = nullptr;
   std::vector<hipEvent_t> kev;  // pairs
@@ -496,7 +501,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
                   e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
                   e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
-                  e->dl_lprior_new, e->dl_llike_new, e->dl_best};
+                  e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (e->h_sums) (void)hipHostFree(e->h_sums);
@@ -3123,6 +3128,271 @@ extern "C" const char* ptm_step_kernel_name(ptm_engine* e) {
   else snprintf(b, sizeof b, "decide_kernel + %s", ptm_sweep_kernel_name(e));
   name = b;
   return name.c_str();
+}
+
+// ---- effective sample size on the device (ptm_ess_kernels.hpp) ------------------------------------------------------------
+// ess_estimator::windowed (ptmcmc_amd/host/ptmcmc_gpu.hh) for nseries series at once.  The table of nfeat x nwin x nlag cells per series
+// lives in a workspace of at most PTM_ESS_WORKSPACE_MB (default 256) MiB: the series are done in chunks that fit it (one series at
+// least).  *ws / *ws_bytes: the caller's workspace, grown on demand.
+static size_t ess_budget() {
+  const char* v = getenv("PTM_ESS_WORKSPACE_MB");
+  const double mb = v && *v ? atof(v) : 256.0;
+  return mb > 0 ? (size_t)(mb * 1048576.0) : (size_t)256 << 20;
+}
+static std::vector<int> ess_lags(int every, int burn, int per_window) {   // the facade's loop
+  std::vector<int> lags(1, 0);
+  double grow = 1;
+  for (int k = 1; k < burn * per_window;) {
+    lags.push_back(every * k);
+    const int was = k;
+    while (k == was) { grow *= 1.1; k = (int)grow; }
+  }
+  return lags;
+}
+static size_t ess_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// steps_of (host, [series of the source], or null: src.steps for all) / sel (host list of the nseries series taken, or null: all in
+// order): the series of one pass may differ in length.  *launched: kernels ran (a pass too short for one window runs none).
+static int ess_windowed_run(hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, int nsource, const int* steps_of, const int* sel, int nseries,
+                            int nfeat, int width, int every, int burn, double* ess, int32_t* nwin_out, bool* launched) {
+  for (int s = 0; s < nseries; ++s) { ess[s] = 0; nwin_out[s] = 0; }
+  if (width < 2) width = 2;
+  if (every < 1) every = 1;
+  if (burn < 1) burn = 1;
+  const int per_window = width / every, span = per_window * every;
+  if (per_window < 1) return PTM_OK;
+  int steps_max = src.steps;
+  if (steps_of) {
+    steps_max = 0;
+    for (int k = 0; k < nseries; ++k) steps_max = std::max(steps_max, steps_of[sel ? sel[k] : k]);
+  }
+  const int nwin = steps_max / span - burn;   // of the longest series: the table's and the grid's
+  if (nwin < 1) return PTM_OK;
+  if (nwin > 65535) return fail(PTM_ERR_UNSUPPORTED, "ptm_ess: %d windows (at most 65535: widen them)", nwin);
+  if ((double)burn * per_window > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_ess: burn windows x samples per window overflows");
+  const std::vector<int> lags = ess_lags(every, burn, per_window);
+  const int nlag = (int)lags.size();
+  const size_t cells1 = (size_t)nfeat * nwin * nlag;                               // one series' table
+  const size_t per_series = cells1 * 20 + (size_t)nfeat * nwin * 8;
+  size_t chunk = ess_budget() / per_series;
+  if (chunk < 1) chunk = 1;
+  if (chunk > (size_t)nseries) chunk = (size_t)nseries;
+  if ((double)chunk * nfeat > 2.0e9) chunk = (size_t)(2.0e9 / nfeat);
+  const size_t lanes_max = chunk * nfeat;
+  const size_t o_lags = 0, o_ess = o_lags + ess_align((size_t)nlag * 4), o_nwin = o_ess + ess_align((size_t)nseries * 8),
+               o_sel = o_nwin + ess_align((size_t)nseries * 4), o_steps = o_sel + ess_align(sel ? (size_t)nseries * 4 : 0),
+               o_mean = o_steps + ess_align(steps_of ? (size_t)nsource * 4 : 0), o_cov = o_mean + ess_align(lanes_max * nwin * nlag * 8),
+               o_cnt = o_cov + ess_align(lanes_max * nwin * nlag * 8), o_e = o_cnt + ess_align(lanes_max * nwin * nlag * 4),
+               total = o_e + ess_align(lanes_max * nwin * 8);
+  if (*ws_bytes < total) {
+    if (*ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
+    HIPCHK(hipMalloc(ws, total));
+    *ws_bytes = total;
+  }
+  unsigned char* b = (unsigned char*)*ws;
+  int* d_lags = (int*)(b + o_lags);
+  double* d_ess = (double*)(b + o_ess);
+  int* d_nwin = (int*)(b + o_nwin);
+  double *d_mean = (double*)(b + o_mean), *d_cov = (double*)(b + o_cov), *d_e = (double*)(b + o_e);
+  int* d_cnt = (int*)(b + o_cnt);
+  EssWho who = {nullptr, nullptr, span, burn};
+  HIPCHK(hipMemcpyAsync(d_lags, lags.data(), (size_t)nlag * 4, hipMemcpyHostToDevice, st));
+  if (sel) { who.sel = (const int*)(b + o_sel); HIPCHK(hipMemcpyAsync(b + o_sel, sel, (size_t)nseries * 4, hipMemcpyHostToDevice, st)); }
+  if (steps_of) { who.steps_of = (const int*)(b + o_steps); HIPCHK(hipMemcpyAsync(b + o_steps, steps_of, (size_t)nsource * 4, hipMemcpyHostToDevice, st)); }
+  HIPCHK(hipStreamSynchronize(st));   // (the lag list is a local; the callers' lists may be too)
+  // no division per sample where the saved row of a sample is linear in its number and the ring has not wrapped
+  const bool linear = every % src.add_every == 0 && (long long)src.first_row + (steps_max - 1) / src.add_every < (long long)src.cap;
+  for (size_t s0 = 0; s0 < (size_t)nseries; s0 += chunk) {
+    const int ns = (int)std::min(chunk, (size_t)nseries - s0), lanes = ns * nfeat;
+    const dim3 grid((unsigned)((lanes + ESS_THREADS - 1) / ESS_THREADS), (unsigned)nwin, (unsigned)((nlag + ESS_LAGS - 1) / ESS_LAGS));
+    if (linear) hipLaunchKernelGGL(ess_accumulate_kernel<true>, grid, dim3(ESS_THREADS), 0, st, src, who, (int)s0, lanes, nfeat, per_window, every, nlag, d_lags, d_mean, d_cov, d_cnt);
+    else hipLaunchKernelGGL(ess_accumulate_kernel<false>, grid, dim3(ESS_THREADS), 0, st, src, who, (int)s0, lanes, nfeat, per_window, every, nlag, d_lags, d_mean, d_cov, d_cnt);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ess_combine_kernel, dim3(grid.x), dim3(ESS_THREADS), 0, st, src, who, (int)s0, lanes, nfeat, nwin, nlag, d_lags, width, every, d_mean, d_cov, d_cnt, d_e);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ess_reduce_kernel, dim3((unsigned)((ns + ESS_THREADS - 1) / ESS_THREADS)), dim3(ESS_THREADS), 0, st, src, who, (int)s0, ns, nfeat, nwin, d_e, d_ess + s0, d_nwin + s0);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(ess, d_ess, (size_t)nseries * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(nwin_out, d_nwin, (size_t)nseries * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (launched) *launched = true;
+  return PTM_OK;
+}
+// ess_estimator::report: the passes (width, every, burn) it makes for a series of `steps` steps -- they depend on the length and the
+// limit alone -- and whether the best of them is taken (the search of esslimit >= 0) or the one pass stands as it is
+struct EssPass { int width, every, burn; bool operator<(const EssPass& o) const { return width != o.width ? width < o.width : (every != o.every ? every < o.every : burn < o.burn); } };
+static std::vector<EssPass> ess_report_plan(int steps, int width, int every, double esslimit) {
+  const int min_burn = 2, min_per_window = 1000, max_windows = 20;
+  std::vector<EssPass> plan;
+  while (width < steps * 0.05) width *= 2;
+  if (esslimit < 0) {
+    while (width * (max_windows + min_burn) < steps) width *= 2;
+    plan.push_back(EssPass{width, every, min_burn});
+    return plan;
+  }
+  const double length = steps, reach = esslimit * 3.0;
+  for (bool last_round = false; !last_round; every *= 2) {
+    int windows = (int)(length / (min_per_window * every));
+    if (windows > max_windows) windows = max_windows;
+    if (windows < 1) break;
+    width = (int)(length / windows);
+    if (width * (windows - 1) > reach * every) {
+      windows = (int)(reach / min_per_window + 1);
+      if (windows > max_windows) windows = max_windows;
+      if (windows > 1) width = (int)((reach * every) / (windows - 1));
+      else { windows = 1; width = min_per_window * every; }
+    } else last_round = true;
+    if ((length - length / (max_windows + min_burn)) * 0.5 < windows * width) plan.push_back(EssPass{width, every, (int)(length / width - windows)});
+  }
+  return plan;
+}
+// ... for every series at once.  Series whose lengths give the same passes (all of them, unless their add_state counts differ and
+// with them a width) share each pass; windowed(pass, sel, n, e, nw) runs one for the n series listed in sel (null: all, in order).
+#include <map>
+template <class F>
+static int ess_report_run(const int* steps_of, int steps_common, int nseries, int width, int every, double esslimit, F windowed, double* ess, int32_t* length_out) {
+  std::map<std::vector<EssPass>, std::vector<int>> groups;
+  {
+    std::map<int, std::vector<EssPass>> plans;   // by length
+    for (int s = 0; s < nseries; ++s) {
+      const int st = steps_of ? steps_of[s] : steps_common;
+      auto it = plans.find(st);
+      if (it == plans.end()) it = plans.insert(std::make_pair(st, ess_report_plan(st, width, every, esslimit))).first;
+      groups[it->second].push_back(s);
+    }
+  }
+  for (int s = 0; s < nseries; ++s) { ess[s] = 0; length_out[s] = 0; }
+  for (const auto& g : groups) {
+    const std::vector<int>& who = g.second;
+    const int n = (int)who.size();
+    const int* sel = n == nseries ? nullptr : who.data();
+    std::vector<double> e((size_t)n);
+    std::vector<int32_t> nw((size_t)n);
+    for (const EssPass& p : g.first) {
+      const int rc = windowed(p, sel, n, e.data(), nw.data());
+      if (rc) return rc;
+      for (int k = 0; k < n; ++k) {
+        const int s = who[(size_t)k];
+        if (esslimit < 0 || e[(size_t)k] > ess[s]) { ess[s] = e[(size_t)k]; length_out[s] = p.width * nw[(size_t)k]; }
+      }
+    }
+  }
+  return PTM_OK;
+}
+
+// the saved history of local rung `rung` as the kernels' source; steps_of: every walker's own count of add_state calls
+static int ess_ring_source(ptm_engine* e, int rung, int nfeat, EssSrc* src, std::vector<int>* steps_of) {
+  if (!e->hist.rungs) return fail(PTM_ERR_INVALID, "this engine keeps no history (ptm_config.history_rungs)");
+  if (rung < 0 || rung >= e->hist.rungs) return fail(PTM_ERR_INVALID, "rung %d keeps no history (history_rungs = %d)", rung, e->hist.rungs);
+  if (nfeat < 1 || nfeat > e->D) return fail(PTM_ERR_INVALID, "nfeat must be in 1..dim (%d)", e->D);
+  std::vector<int64_t> nh((size_t)e->Nc);
+  int rc = ptm_get_array(e, PTM_ARR_NHIST, nh.data());
+  if (rc) return rc;
+  steps_of->resize((size_t)e->W);
+  bool same = true;
+  for (int w = 0; w < e->W; ++w) {
+    const int64_t st = nh[(size_t)rung * e->W + w];
+    if (st > 2000000000) return fail(PTM_ERR_UNSUPPORTED, "ptm_ess: more than 2e9 steps");
+    (*steps_of)[(size_t)w] = (int)st;
+    same = same && st == nh[(size_t)rung * e->W];
+  }
+  src->steps = (*steps_of)[0];
+  if (same) steps_of->clear();   // (one length for all: no per-series table)
+  src->x = e->hist.x + (size_t)rung * e->W * e->DP;
+  src->meta = e->hist.meta + (size_t)rung * e->W;
+  src->slot_stride = (long long)e->hist.HC * e->DP;
+  src->meta_stride = e->hist.HC;
+  src->series_stride = e->DP;
+  src->cap = e->hist.cap;
+  src->add_every = e->cfg.add_every_n;
+  src->first_row = 1;
+  src->permuted = (e->DP == 32 || e->DP == 64 || e->DP == 128) ? 1 : 0;
+  return PTM_OK;
+}
+
+extern "C" int ptm_ess_windowed(ptm_engine* e, int rung, int nfeat, int width, int every, int burn, double* ess, int32_t* nwin) {
+  if (!e || !ess || !nwin) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_ess_windowed");
+  e->ess_on_device = 0;
+  EssSrc src;
+  std::vector<int> steps_of;
+  int rc = ess_ring_source(e, rung, nfeat, &src, &steps_of);
+  if (rc) return rc;
+  bool launched = false;
+  if ((rc = ess_windowed_run(e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->W, steps_of.empty() ? nullptr : steps_of.data(), nullptr, e->W, nfeat, width, every, burn, ess, nwin, &launched))) return rc;
+  e->ess_on_device = launched ? 1 : 0;
+  return PTM_OK;
+}
+extern "C" int ptm_ess_report(ptm_engine* e, int rung, int nfeat, int width, int every, double esslimit, double* ess, int32_t* length) {
+  if (!e || !ess || !length) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_ess_report");
+  e->ess_on_device = 0;
+  if (width < 1 || every < 1) return fail(PTM_ERR_INVALID, "ptm_ess_report: width and every must be >= 1");
+  EssSrc src;
+  std::vector<int> steps_of;
+  int rc = ess_ring_source(e, rung, nfeat, &src, &steps_of);
+  if (rc) return rc;
+  const int* so = steps_of.empty() ? nullptr : steps_of.data();
+  bool launched = false;
+  auto pass = [&](const EssPass& p, const int* sel, int n, double* out_e, int32_t* out_n) {
+    return ess_windowed_run(e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->W, so, sel, n, nfeat, p.width, p.every, p.burn, out_e, out_n, &launched);
+  };
+  if ((rc = ess_report_run(so, src.steps, e->W, width, every, esslimit, pass, ess, length))) return rc;
+  e->ess_on_device = launched ? 1 : 0;
+  return PTM_OK;
+}
+extern "C" int ptm_ess_last_on_device(ptm_engine* e) { return e ? e->ess_on_device : 0; }
+
+// a caller's series on the device: series[(t * nseries + s) * nfeat + f]
+struct EssSeries {
+  double* x = nullptr;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  int device_before = -1;   // the caller's current device, put back when the call ends
+  EssSrc src;
+  ~EssSeries() {
+    if (x) (void)hipFree(x);
+    if (ws) (void)hipFree(ws);
+    if (device_before >= 0) (void)hipSetDevice(device_before);
+  }
+};
+static int ess_series_source(EssSeries* S, int device, const double* series, int64_t n, int nseries, int nfeat) {
+  int rc = need_device();
+  if (rc) return rc;
+  if (!series) return fail(PTM_ERR_INVALID, "null argument");
+  if (n < 1 || n > 2000000000 || nseries < 1 || nfeat < 1 || (double)nseries * nfeat > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_ess_series: bad shape");
+  if (device >= 0) {
+    int cur = -1;
+    HIPCHK(hipGetDevice(&cur));
+    if (cur != device) { HIPCHK(hipSetDevice(device)); S->device_before = cur; }
+  }
+  const size_t count = (size_t)n * nseries * nfeat;
+  HIPCHK(hipMalloc((void**)&S->x, count * 8));
+  HIPCHK(hipMemcpy(S->x, series, count * 8, hipMemcpyHostToDevice));
+  S->src.x = S->x; S->src.meta = nullptr;
+  S->src.slot_stride = (long long)nseries * nfeat; S->src.meta_stride = 0; S->src.series_stride = nfeat;
+  S->src.cap = (int)n; S->src.add_every = 1; S->src.first_row = 0; S->src.permuted = 0; S->src.steps = (int)n;
+  return PTM_OK;
+}
+extern "C" int ptm_ess_series_windowed(int device, const double* series, int64_t n, int nseries, int nfeat, int width, int every, int burn, double* ess,
+                                       int32_t* nwin) {
+  if (!ess || !nwin) return fail(PTM_ERR_INVALID, "null argument");
+  EssSeries S;
+  int rc = ess_series_source(&S, device, series, n, nseries, nfeat);
+  if (rc) return rc;
+  return ess_windowed_run(nullptr, &S.ws, &S.ws_bytes, S.src, nseries, nullptr, nullptr, nseries, nfeat, width, every, burn, ess, nwin, nullptr);
+}
+extern "C" int ptm_ess_series_report(int device, const double* series, int64_t n, int nseries, int nfeat, int width, int every, double esslimit, double* ess,
+                                     int32_t* length) {
+  if (!ess || !length) return fail(PTM_ERR_INVALID, "null argument");
+  if (width < 1 || every < 1) return fail(PTM_ERR_INVALID, "ptm_ess_series_report: width and every must be >= 1");
+  EssSeries S;
+  int rc = ess_series_source(&S, device, series, n, nseries, nfeat);
+  if (rc) return rc;
+  auto pass = [&](const EssPass& p, const int* sel, int k, double* out_e, int32_t* out_n) {
+    return ess_windowed_run(nullptr, &S.ws, &S.ws_bytes, S.src, nseries, nullptr, sel, k, nfeat, p.width, p.every, p.burn, out_e, out_n, nullptr);
+  };
+  return ess_report_run(nullptr, (int)n, nseries, width, every, esslimit, pass, ess, length);
 }
 
 // ---- verification hooks ------------------------------------------------------------------------------------------------

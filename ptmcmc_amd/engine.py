@@ -32,6 +32,7 @@ EXPORTS = [
     "ptm_dev_alloc", "ptm_dev_free", "ptm_dev_copy",
     "ptm_set_target_device", "ptm_target_device_rows", "ptm_get_best_evaluated",
     "ptm_set_proposal_adaptive", "ptm_get_proposal_adapt_state", "ptm_set_proposal_adapt_state",
+    "ptm_ess_windowed", "ptm_ess_report", "ptm_ess_series_windowed", "ptm_ess_series_report", "ptm_ess_last_on_device",
 ]
 
 
@@ -176,6 +177,12 @@ def load():
         L.ptm_set_proposal_adaptive.argtypes = [C.c_void_p, C.POINTER(PtmAdaptiveSet), _dp, _dp, _dp, _dp, _i32p, _i32p]
         L.ptm_get_proposal_adapt_state.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p]
         L.ptm_set_proposal_adapt_state.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p]
+    if hasattr(L, "ptm_ess_windowed"):
+        L.ptm_ess_windowed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _i32p]
+        L.ptm_ess_report.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i32p]
+        L.ptm_ess_series_windowed.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _i32p]
+        L.ptm_ess_series_report.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i32p]
+        L.ptm_ess_last_on_device.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -226,6 +233,33 @@ def debug_sqrt_scan(device=-1):
     n = C.c_uint64()
     _chk(load().ptm_debug_sqrt_scan(device, C.byref(n)))
     return n.value
+
+
+def _series3(series):
+    a = np.ascontiguousarray(series, dtype=np.float64)
+    if a.ndim != 3:
+        raise ValueError("series must be an array [n, nseries, nfeat]")
+    return a
+
+
+def ess_series_windowed(series, width, every, burn, device=-1):
+    """one pass of the effective-sample-size estimator with fixed windows over series [n, nseries, nfeat] (every feature of a
+    series is looked at), on the device: (ess[nseries], nwin[nseries]) (ptm_ess_series_windowed)"""
+    a = _series3(series)
+    n, ns, nf = a.shape
+    ess, nwin = np.empty(ns), np.empty(ns, dtype=np.int32)
+    _chk(load().ptm_ess_series_windowed(device, _d(a), n, ns, nf, int(width), int(every), int(burn), _d(ess), nwin.ctypes.data_as(_i32p)))
+    return ess, nwin
+
+
+def effective_samples_series(series, width, every, esslimit=-1, device=-1):
+    """chain::report_effective_samples for series [n, nseries, nfeat] on the device: (ess[nseries], useful length[nseries])
+    (ptm_ess_series_report; esslimit >= 0: the coarse-to-fine stride search)"""
+    a = _series3(series)
+    n, ns, nf = a.shape
+    ess, length = np.empty(ns), np.empty(ns, dtype=np.int32)
+    _chk(load().ptm_ess_series_report(device, _d(a), n, ns, nf, int(width), int(every), float(esslimit), _d(ess), length.ctypes.data_as(_i32p)))
+    return ess, length
 
 
 class DeviceBuffer:
@@ -683,6 +717,27 @@ class Engine:
         m = meta.reshape(sh + (4,))   # (views, not copies: inside a batch() the arrays are filled later)
         return dict(x=X.reshape(sh + (self.D,)), llike=ll.reshape(sh), lprior=lp.reshape(sh), naccept=m[..., 0],
                     ntries=m[..., 1], last_type=m[..., 2], row=m[..., 3], invtemp=b.reshape(sh))
+
+    def ess_windowed(self, rung=0, nfeat=None, width=40000, every=100, burn=2):
+        """one pass of the effective-sample-size estimator with fixed windows over the saved history of local rung `rung`, every
+        walker at once, on the device: (ess[W], nwin[W]) (ptm_ess_windowed); nfeat: the first parameters looked at (None: all)"""
+        ess, nwin = np.empty(self.W), np.empty(self.W, dtype=np.int32)
+        _chk(self.L.ptm_ess_windowed(self.h, int(rung), self.D if nfeat is None else int(nfeat), int(width), int(every), int(burn), _d(ess),
+                                     nwin.ctypes.data_as(_i32p)))
+        return ess, nwin
+
+    def effective_samples(self, rung=0, nfeat=None, width=40000, every=100, esslimit=-1):
+        """chain::report_effective_samples of every walker's chain on local rung `rung`, from the history ring, on the device:
+        (ess[W], useful length[W]) (ptm_ess_report)"""
+        ess, length = np.empty(self.W), np.empty(self.W, dtype=np.int32)
+        _chk(self.L.ptm_ess_report(self.h, int(rung), self.D if nfeat is None else int(nfeat), int(width), int(every), float(esslimit), _d(ess),
+                                   length.ctypes.data_as(_i32p)))
+        return ess, length
+
+    @property
+    def ess_last_on_device(self):
+        """the last ess_windowed / effective_samples call ran the device kernels (ptm_ess_last_on_device)"""
+        return bool(self.L.ptm_ess_last_on_device(self.h))
 
     @property
     def exchange_row_capacity(self):

@@ -1503,24 +1503,31 @@ class differential_evolution : public proposal_distribution {
 //     minimum over the features; the answer is the best n: early windows lengthen the correlation more than they add samples.
 // report() chooses width / stride like the reference: windows doubled until at most 20 + 2 of them cover the series, or, given
 // a limit on the ess worth resolving, a search from coarse to fine strides.
+// The pass with fixed windows can be handed to a backend (use_backend): the engine's kernels run it on the device's own history
+// ring, in this very order of operations -- same bits (ptm_ess_windowed); report() stays the one implementation of the search.
 class ess_estimator {
  public:
   // features of the state saved for nominal step `step` (false: none, the sample is skipped)
   typedef std::function<bool(int step, std::vector<double>& features)> reader;
+  // windowed(width, every, burn) computed elsewhere
+  typedef std::function<void(int width, int every, int burn, double& ess, int& nwin)> window_backend;
 
  private:
   int steps, nfeat;
   reader read;
+  window_backend backend;
   bool sample(int step, std::vector<double>& v) const { return step >= 0 && step < steps && read(step, v) && (int)v.size() >= nfeat; }
 
   struct cell { double mean, cov; int count; };
 
  public:
   ess_estimator(int steps, int nfeat, reader read) : steps(steps), nfeat(nfeat), read(read) {}
+  void use_backend(window_backend b) { backend = b; }
 
   // one pass with fixed windows: ess and the number of windows that gave it
   void windowed(int width, int every, int burn, double& ess_out, int& nwin_out) const {
     ess_out = 0; nwin_out = 0;
+    if (backend) { backend(width, every, burn, ess_out, nwin_out); return; }
     if (width < 2) width = 2;
     if (every < 1) every = 1;
     if (burn < 1) burn = 1;
@@ -2848,16 +2855,62 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "report_effective_samples");
     return (int)nh[(size_t)replica];
   }
-  std::pair<double, int> report_effective_samples(int imax = -1, int width = 40000, int every = 100, double esslimit = -1, bool reporting = true) {
+  // The device estimates from its own ring (ptm_ess_*: every replica at once, each with its own count of add_state calls, the host
+  // estimator's bits) when the ring is there; with host-side proposals (the history is the host mirror) and with PTM_HOST_ESS=1 the
+  // estimate is made here.
+  bool ess_on_device_possible() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_ESS"); return v && *v && *v != '0'; }();   // (A/B: keep the host path)
+    return !(off || host_mode || hist_rows <= 0);
+  }
+  int ess_features(int imax) const {
     if (imax < 0 || imax > dim) imax = dim;
-    if (imax > 20) imax = 20;   // (the reference's simplified interface looks at the first 20 parameters)
-    const int nf = imax;
+    return imax > 20 ? 20 : imax;   // (the reference's simplified interface looks at the first 20 parameters)
+  }
+  std::pair<double, int> report_effective_samples(int imax = -1, int width = 40000, int every = 100, double esslimit = -1, bool reporting = true) {
+    const int nf = ess_features(imax);
     ess_estimator est(cold_steps(), nf, [this](int step, std::vector<double>& row) { return cold_row(step, row); });
+    ess_dev_last = false;
+    if (ess_on_device_possible())
+      est.use_backend([this, nf](int width, int every, int burn, double& ess, int& nwin) {
+        std::vector<double> e((size_t)W);
+        std::vector<int32_t> n((size_t)W);
+        ptm_check(ptm_ess_windowed(eng, 0, nf, width, every, burn, e.data(), n.data()), "report_effective_samples");
+        if (ptm_ess_last_on_device(eng)) ess_dev_last = true;   // (a pass of the search too short for one window launches nothing)
+        ess = e[0]; nwin = n[0];
+      });
     const std::pair<double, int> r = est.report(width, every, esslimit, views.empty() ? 0 : views[0].size(), Ninit_rows);
-    if (reporting)
-      std::cout << "Over " << nf << " pars: ess=" << r.first << "  useful chain length is: " << r.second << " autocorrlen=" << (r.first > 0 ? r.second / r.first : 0.0) << std::endl;
+    if (reporting) print_effective_samples(imax, r);
     return r;
   }
+  void print_effective_samples(int imax, const std::pair<double, int>& r) {
+    std::cout << "Over " << ess_features(imax) << " pars: ess=" << r.first << "  useful chain length is: " << r.second << " autocorrlen=" << (r.first > 0 ? r.second / r.first : 0.0) << std::endl;
+  }
+  // the same for every replica of this process: (ess, useful chain length) of each cold chain
+  std::vector<std::pair<double, int> > report_effective_samples_all(int imax = -1, int width = 40000, int every = 100, double esslimit = -1) {
+    const int nf = ess_features(imax);
+    std::vector<std::pair<double, int> > out((size_t)W);
+    if (ess_on_device_possible() && width >= 1) {
+      if (every < 0) {   // the stride the series was saved with (ess_estimator::report)
+        const int rows = views.empty() ? 0 : views[0].size();
+        every = rows > Ninit_rows ? (int)(0.5 + ((double)cold_steps() - Ninit_rows) / (rows - Ninit_rows)) : 1;
+      }
+      if (every < 1) every = 1;
+      std::vector<double> e((size_t)W);
+      std::vector<int32_t> len((size_t)W);
+      ptm_check(ptm_ess_report(eng, 0, nf, width, every, esslimit, e.data(), len.data()), "report_effective_samples_all");
+      ess_dev_last = ptm_ess_last_on_device(eng) != 0;
+      for (int w = 0; w < W; w++) out[(size_t)w] = std::make_pair(e[(size_t)w], (int)len[(size_t)w]);
+      return out;
+    }
+    ess_dev_last = false;
+    for (int w = 0; w < W; w++) {
+      ess_estimator est(cold_steps(w), nf, [this, w](int step, std::vector<double>& row) { return cold_row(step, row, w); });
+      out[(size_t)w] = est.report(width, every, esslimit, views.empty() ? 0 : views[0].size(), Ninit_rows);
+    }
+    return out;
+  }
+  bool ess_dev_last = false;
+  bool ess_ran_on_device() const { return ess_dev_last; }   // the last estimate of this ladder launched the device's kernels
   // swap_count / swap_accept_count (chain.hh:244-245)
   void swap_counts(std::vector<int64_t>& tries, std::vector<int64_t>& accepts) {
     std::vector<int64_t> t((size_t)W * (Ntemps > 1 ? Ntemps - 1 : 1)), a(t.size());
@@ -3358,7 +3411,18 @@ class ptmcmc_sampler : public bayes_sampler {
             double esslimit = -1;
             *optValue("chain_ess_limit") >> esslimit;
             std::cout << "Effective sample size test" << std::endl;
-            const std::pair<double, int> ess_len = cc->report_effective_samples(-1, save_every * 1000, save_every, esslimit);
+            // a population on the device: one estimate of every replica; replica 0's is the reference's line and the criterion
+            // (the reference's behaviour), the population's spread follows it
+            std::pair<double, int> ess_len;
+            if (nrep > 1 && cc->ess_on_device_possible()) {
+              const std::vector<std::pair<double, int> > all = cc->report_effective_samples_all(-1, save_every * 1000, save_every, esslimit);
+              ess_len = all[0];
+              cc->print_effective_samples(-1, ess_len);
+              std::vector<double> e;
+              for (size_t k = 0; k < all.size(); k++) e.push_back(all[k].first);
+              std::sort(e.begin(), e.end());
+              std::cout << "Over " << e.size() << " replicas: ess min=" << e.front() << " median=" << e[e.size() / 2] << " max=" << e.back() << std::endl;
+            } else ess_len = cc->report_effective_samples(-1, save_every * 1000, save_every, esslimit);
             if (ess_len.first > ess_stop) {
               stop = true;
               std::cout << "ptmcmc_sampler::run: Stopping based on chain_ess_stop Effective Sample Size criterion." << std::endl;
