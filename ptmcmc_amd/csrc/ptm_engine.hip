@@ -283,7 +283,6 @@ extern "C" int ptm_shard_finalize(ptm_engine* e);
 static int build_engine(ptm_engine* e, const ptm_config* cfg);
 static int launch_beta_transpose(ptm_engine* e);
 static int ensure_betaC(ptm_engine* e);
-static bool lean_ev_sweeps(const ptm_engine* e);
 static int ladder_settle(ptm_engine* e);
 static int fill_evolving_ladders(ptm_engine* e);
 
@@ -1256,29 +1255,42 @@ static AdaArgs make_ada(const ptm_engine* e) {
   return a;
 }
 
+// the launches of a padded dimension's translation unit (ptm_launch.hpp)
+const DpLaunch* ptm::dp_launch(int DP) {
+  switch (DP) {
+    case 4: return &dp_launch_4;
+    case 8: return &dp_launch_8;
+    case 16: return &dp_launch_16;
+    case 32: return &dp_launch_32;
+    case 64: return &dp_launch_64;
+    case 128: return &dp_launch_128;
+    case 256: return &dp_launch_256;
+    case 512: return &dp_launch_512;
+    case 1024: return &dp_launch_1024;
+  }
+  return nullptr;
+}
+
 // a user likelihood, on the host (ptm_set_target_callback) or on the device (ptm_set_target_device): the propose / accept passes
 static inline bool user_like(const ptm_engine* e) { return e->cb != nullptr || e->dfn != nullptr; }
 
-static SweepSel sweep_sel(const ptm_engine* e) {
-  SweepSel s;
-  s.kind = e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : (e->prop_kind == PTM_PROP_LOWER ? KIND_LOWER : KIND_DENSE);
-  s.uni = (e->W % 64) == 0;
-  s.host_prop = e->pcb != nullptr;
-  if (s.host_prop) s.kind = KIND_DIAG;   // (no factor is read: any instantiation serves)
-  s.ada = e->ada_on && !s.host_prop;   // (host-side proposals take over from an adaptive set)
-  s.plain = !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !s.ada && !e->betaC && !s.host_prop;
-  s.simple = s.uni && s.plain;
-  s.lean_ev = s.uni && e->betaC && !e->has_bounds && e->all_uniform && !e->has_mean && !e->any_oned && !user_like(e) && e->mix_K == 0 && !s.ada && !s.host_prop &&
-              !e->hist.rungs && !e->map.rungs;
-  s.callback = user_like(e);
-  s.de = e->de_on;
-  return s;
+// the build a sweep over `chains` chains runs on (ptm_sweep_plan.hpp); step_sweep_plan: the sweep of a PT step -- every local rung, after an
+// exchange phase -- which is what the engine prepares for (row labels, temperatures) and what it reports by name
+static SweepPlan sweep_plan(const ptm_engine* e, long long chains, bool touched) {
+  SweepFacts f;
+  f.DP = e->DP; f.W = e->W; f.chains = chains; f.nloc = e->nloc;
+  f.kind = e->prop_kind == PTM_PROP_DIAG ? PLAN_DIAG : (e->prop_kind == PTM_PROP_LOWER ? PLAN_LOWER : PLAN_DENSE);
+  f.has_bounds = e->has_bounds; f.bounds_box = e->bounds_box; f.all_uniform = e->all_uniform; f.has_mean = e->has_mean; f.any_oned = e->any_oned;
+  f.mix_K = e->mix_K;
+  f.evolving = e->betaC != nullptr; f.tracked = e->hist.rungs || e->map.rungs;
+  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.de = e->de_on; f.ada = e->ada_on;
+  f.mode = f.user_like ? 1 : 0;   // (the propose and accept passes run on one build)
+  f.touched = touched;
+  return plan_sweep(f, sweep_env());
 }
+static SweepPlan step_sweep_plan(const ptm_engine* e) { return sweep_plan(e, e->Nc, true); }
 
-static bool lean_ev_sweeps(const ptm_engine* e) {
-  static const bool forced = [] { const char* v = getenv("PTM_FORCE_VALU"); return v && *v && *v != '0'; }();
-  return e->DP == 32 && !forced && sweep_sel(e).lean_ev;
-}
+static bool lean_ev_sweeps(const ptm_engine* e) { return reads_ladder_major_beta(step_sweep_plan(e)); }
 
 // the compacted sweep counts a step's add_state calls for all chains at once: bring nhist up to date before anything reads it
 static int flush_nhist(ptm_engine* e) {
@@ -1289,20 +1301,12 @@ static int flush_nhist(ptm_engine* e) {
   return PTM_OK;
 }
 
-// the conditions of the compacted sweep (PTM_COMPACT=0 switches it off) but for `touched`: an exchange phase ran since the last sweep
-static bool compact_applies(const ptm_engine* e, const SweepSel& sel) {
-  static const bool compact_ok = [] { const char* v = getenv("PTM_COMPACT"); return !(v && *v == '0'); }();
-  // ... and the box-bounds build (uniform priors, open / limit bounds, a mean, one-dimensional moves, scale mixtures, evolving ladders)
-  const bool gen1 = sel.uni && !sel.callback && !sel.host_prop && !sel.de && !sel.ada && e->all_uniform && (!e->has_bounds || e->bounds_box);
-  return compact_ok && e->DP == 32 && (sel.simple || gen1) && !e->hist.rungs && !e->map.rungs && !getenv("PTM_FORCE_VALU") &&
-         e->W >= 1024 && e->nloc <= 4096;   // (the same answer for every partial sweep of a step)
-}
 // Row labels: does a whole step of this engine (exchange phase, then ONE sweep of all rungs) exchange labels instead of rows?  Where its
 // sweep is the compacted one, the engine holds the whole ladder, and a walker fits the 16 bits a list entry leaves it.
 // PTM_ROW_LABELS=0 switches it off.
 static bool row_labels_apply(const ptm_engine* e) {
   static const bool labels_ok = [] { const char* v = getenv("PTM_ROW_LABELS"); return !(v && *v == '0'); }();
-  return labels_ok && e->nloc == e->Nt && !e->shard && e->W <= 65536 && e->Nt > 1 && compact_applies(e, sweep_sel(e));
+  return labels_ok && e->nloc == e->Nt && !e->shard && e->W <= 65536 && e->Nt > 1 && step_sweep_plan(e).compacted;
 }
 static void flush_rows(ptm_engine* e) {
   e->rows_labelled = false;
@@ -1492,11 +1496,11 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     ev0 = e->kev[e->kev_used]; ev1 = e->kev[e->kev_used + 1];
     e->kev_used += 2;
   }
-  const SweepSel sel = sweep_sel(e);
-  if (e->betaC_stale && !lean_ev_sweeps(e)) { int rc = ensure_betaC(e); if (rc) return rc; }   // (a build that reads the chain-indexed temperatures)
+  const SweepPlan plan = sweep_plan(e, p.c_end - p.c_begin, e->touched);
+  if (e->betaC_stale && !reads_ladder_major_beta(plan)) { int rc = ensure_betaC(e); if (rc) return rc; }   // (a build that reads the chain-indexed temperatures)
   // Compacted sweep: after an exchange phase ~1/6 of a long ladder's chains make no move; the lean MFMA build on a big
   // population then visits the moving chains only (partition_kernel packs them per rung).
-  const bool compact = e->touched && compact_applies(e, sel);
+  const bool compact = plan.compacted;
   if (labelled && !(compact && rung0 == 0 && nr == e->nloc)) return fail(PTM_ERR_HIP, "internal: a labelled exchange phase without its compacted sweep");
   if (!compact) { int rc = flush_nhist(e); if (rc) return rc; }
   if (compact) {
@@ -1513,20 +1517,9 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   // compacted sweep stay outside, so that the events' mean is what rocprofv3 reports for that kernel
   if (ev0) HIPCHK(hipEventRecord(ev0, e->stream));
   const AdaArgs ada = make_ada(e);
-  auto launch = [&](const Dev& q) -> hipError_t {
-    switch (e->DP) {
-      case 4: return launch_sweep_4(q, sel, e->stream, ada);
-      case 8: return launch_sweep_8(q, sel, e->stream, ada);
-      case 16: return launch_sweep_16(q, sel, e->stream, ada);
-      case 32: return launch_sweep_32(q, sel, e->stream, ada);
-      case 64: return launch_sweep_64(q, sel, e->stream, ada);
-      case 128: return launch_sweep_128(q, sel, e->stream, ada);
-      case 256: return launch_sweep_256(q, sel, e->stream, ada);
-      case 512: return launch_sweep_512(q, sel, e->stream, ada);
-      case 1024: return launch_sweep_1024(q, sel, e->stream, ada);
-    }
-    return hipErrorInvalidValue;
-  };
+  const DpLaunch* dl = dp_launch(e->DP);
+  if (!dl) return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  auto launch = [&](const Dev& q) { return dl->sweep(q, plan, e->stream, ada); };
 
   size_t npick = 0;
   if (e->pcb) {
@@ -1793,18 +1786,9 @@ static int reset_counters(ptm_engine* e) {
 
 static int run_eval(ptm_engine* e, int n, double* x, int* valid, double* lp, double* ll, int eval_like) {
   Dev p = make_dev(e);
-  switch (e->DP) {
-    case 4: HIPCHK(launch_eval_4(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 8: HIPCHK(launch_eval_8(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 16: HIPCHK(launch_eval_16(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 32: HIPCHK(launch_eval_32(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 64: HIPCHK(launch_eval_64(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 128: HIPCHK(launch_eval_128(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 256: HIPCHK(launch_eval_256(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 512: HIPCHK(launch_eval_512(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    case 1024: HIPCHK(launch_eval_1024(p, n, x, valid, lp, ll, eval_like, e->stream)); break;
-    default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
-  }
+  const DpLaunch* dl = dp_launch(e->DP);
+  if (!dl) return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  HIPCHK(dl->eval(p, n, x, valid, lp, ll, eval_like, e->stream));
   return PTM_OK;
 }
 
@@ -1862,33 +1846,10 @@ extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llik
 }
 
 static int launch_init(ptm_engine* e, const Dev& p, long long attempt, unsigned char* pending, double* x = nullptr, double* ll = nullptr, double* lp = nullptr) {
-  if (x) {   // (into a caller's staging arrays: ptm_draw_prior_rows)
-    switch (e->DP) {
-      case 4: HIPCHK(launch_init_4(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 8: HIPCHK(launch_init_8(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 16: HIPCHK(launch_init_16(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 32: HIPCHK(launch_init_32(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 64: HIPCHK(launch_init_64(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 128: HIPCHK(launch_init_128(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 256: HIPCHK(launch_init_256(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 512: HIPCHK(launch_init_512(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      case 1024: HIPCHK(launch_init_1024(p, x, ll, lp, e->err + 1, attempt, pending, e->stream)); break;
-      default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
-    }
-    return PTM_OK;
-  }
-  switch (e->DP) {
-    case 4: HIPCHK(launch_init_4(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 8: HIPCHK(launch_init_8(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 16: HIPCHK(launch_init_16(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 32: HIPCHK(launch_init_32(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 64: HIPCHK(launch_init_64(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 128: HIPCHK(launch_init_128(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 256: HIPCHK(launch_init_256(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 512: HIPCHK(launch_init_512(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    case 1024: HIPCHK(launch_init_1024(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream)); break;
-    default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
-  }
+  const DpLaunch* dl = dp_launch(e->DP);
+  if (!dl) return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  if (x) HIPCHK(dl->init(p, x, ll, lp, e->err + 1, attempt, pending, e->stream));   // (into a caller's staging arrays: ptm_draw_prior_rows)
+  else HIPCHK(dl->init(p, xrows(e), e->ll, e->lp, e->err + 1, attempt, pending, e->stream));
   return PTM_OK;
 }
 
@@ -2077,13 +2038,19 @@ extern "C" int ptm_sweep(ptm_engine* e, int n) {
 // Small ladders (rungs x padded dimensions <= the 1024 lanes of one workgroup, device target and proposals): whole PT steps in
 // ONE launch per batch, a block per walker-ladder looping over the steps (ptm_fused_kernel.hpp).  PTM_FUSED=0 keeps the
 // two-launch path.  Returns the steps taken (0: not this engine's case), or a negative status.
-static int fused_steps(ptm_engine* e, int n) {
+static size_t fused_decide_lds(const ptm_engine* e) { return decide_lds_bytes(e->Nt, e->ms, e->Nt, e->evolve_rate > 0, e->evolve_rate > 0 && e->beta_add); }
+static bool fused_applies(const ptm_engine* e) {
   static const bool fused_ok = [] { const char* v = getenv("PTM_FUSED"); return !(v && *v == '0'); }();
-  if (!fused_ok || e->DP > 16 || (long long)e->Nt * e->DP > 256 || user_like(e) || e->pcb || e->ada_on || e->cfg.time_kernels) return 0;
-  if (e->evolve_rate > 0 && (e->W > 64 || e->evolve_cut >= 0)) return 0;   // (the new temperatures' chain-indexed image is then a separate launch)
-  const bool evb = e->evolve_rate > 0 && e->beta_add;
-  const size_t dlds = decide_lds_bytes(e->Nt, e->ms, e->Nt, e->evolve_rate > 0, evb);
-  if (dlds > 96 * 1024) return 0;
+  StepFacts f;
+  f.DP = e->DP; f.Nt = e->Nt; f.W = e->W;
+  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.ada = e->ada_on; f.time_kernels = e->cfg.time_kernels != 0;
+  f.evolving = e->evolve_rate > 0; f.evolve_cut = e->evolve_cut >= 0;
+  f.decide_lds = fused_decide_lds(e);
+  return fused_applies(f, fused_ok);
+}
+static int fused_steps(ptm_engine* e, int n) {
+  if (!fused_applies(e)) return 0;
+  const size_t dlds = fused_decide_lds(e);
   int rc = flush_nhist(e);
   if (rc) return rc;
   if (e->log_pending >= PTM_LOG_RING && (rc = fold_swap_log(e))) return rc;
@@ -2093,13 +2060,7 @@ static int fused_steps(ptm_engine* e, int n) {
     Dev p = make_dev(e);
     const Decide d = make_decide(e, nullptr, nullptr, 0, nullptr, nullptr);
     const bool diag = e->prop_kind == PTM_PROP_DIAG;
-    hipError_t he;
-    switch (e->DP) {
-      case 4: he = launch_fused_4(p, d, diag, k, e->swap_log, e->log_head, dlds, e->stream); break;
-      case 8: he = launch_fused_8(p, d, diag, k, e->swap_log, e->log_head, dlds, e->stream); break;
-      default: he = launch_fused_16(p, d, diag, k, e->swap_log, e->log_head, dlds, e->stream); break;
-    }
-    HIPCHK(he);
+    HIPCHK(dp_launch(e->DP)->fused(p, d, diag, k, e->swap_log, e->log_head, dlds, e->stream));
     e->step += (uint64_t)k;
     e->log_head = (e->log_head + k) % PTM_LOG_RING;
     e->log_pending += k;
@@ -2143,10 +2104,11 @@ static bool ladder_applies(ptm_engine* e, long long* grid_out = nullptr, size_t*
   const bool diag = e->prop_kind == PTM_PROP_DIAG;
   const int fl = ladder_flavour(e);
   const bool ev_ = e->evolve_rate > 0;
-  const size_t lds = e->DP == 4 ? ladder_lds_4(e->Nt, e->ms, ev_) : e->DP == 8 ? ladder_lds_8(e->Nt, e->ms, ev_) : e->DP == 16 ? ladder_lds_16(e->Nt, e->ms, ev_) : ladder_lds_32(e->Nt, e->ms, ev_);
+  const DpLaunch* dl = dp_launch(e->DP);
+  const size_t lds = dl->ladder_lds(e->Nt, e->ms, ev_);
   if (lds > 160 * 1024) return false;
   int& cap = e->lad_capacity[diag ? 1 : 0][fl];   // (asked per build: the builds differ in registers, and the LDS attribute is per kernel)
-  if (cap < 0) cap = e->DP == 4 ? ladder_blocks_4(diag, fl, lds) : e->DP == 8 ? ladder_blocks_8(diag, fl, lds) : e->DP == 16 ? ladder_blocks_16(diag, fl, lds) : ladder_blocks_32(diag, fl, lds);
+  if (cap < 0) cap = dl->ladder_blocks(diag, fl, lds);
   // every workgroup must be resident at once (they wait for each other)
   if (grid > cap || grid > 1024) return false;
   if (grid_out) *grid_out = grid;
@@ -2265,8 +2227,7 @@ static int ladder_steps(ptm_engine* e, int n) {
     {
       std::lock_guard<std::mutex> lock(g_lad_mutex);
       if (g_lad_last && g_lad_last != e && g_lad_last->lad_event) HIPCHK(hipStreamWaitEvent(e->stream, g_lad_last->lad_event, 0));
-      HIPCHK(e->DP == 4 ? launch_ladder_4(p, a, diag, fl, (int)grid, lds, e->stream) : e->DP == 8 ? launch_ladder_8(p, a, diag, fl, (int)grid, lds, e->stream) :
-             e->DP == 16 ? launch_ladder_16(p, a, diag, fl, (int)grid, lds, e->stream) : launch_ladder_32(p, a, diag, fl, (int)grid, lds, e->stream));
+      HIPCHK(dp_launch(e->DP)->launch_ladder(p, a, diag, fl, (int)grid, lds, e->stream));
       // (the event costs a host call per launch: only a process with several engines on this path records it)
       static int engines_seen = 0;
       static ptm_engine* first_seen = nullptr;
@@ -3093,24 +3054,7 @@ extern "C" int ptm_calibrate(ptm_engine* e, ptm_calibration* out) {
 extern "C" const char* ptm_sweep_kernel_name(ptm_engine* e) {
   if (!e) return "";
   char b[96];
-  const SweepSel s = sweep_sel(e);
-  const char* fv = getenv("PTM_FORCE_VALU");
-  if (e->DP == 32 && s.uni && !s.callback && !s.host_prop && !s.de && !s.ada && !(fv && *fv && *fv != '0')) {
-    const char* cv = getenv("PTM_COMPACT");
-    const bool g1 = !s.simple && e->all_uniform && (!e->has_bounds || e->bounds_box);
-    const bool cpt = !(cv && *cv == '0') && (s.simple || g1) && !e->hist.rungs && !e->map.rungs && e->W >= 1024 && e->nloc <= 4096;   // (in PT steps; plain sweeps visit every chain)
-    snprintf(b, sizeof b, "sweep_mfma32_kernel<%d, %s, %d%s, %s>", s.kind == KIND_DIAG ? KIND_LOWER : s.kind, (e->hist.rungs || e->map.rungs) ? "true" : "false",
-             (s.simple || s.lean_ev) ? 0 : ((e->all_uniform && (!e->has_bounds || e->bounds_box)) ? ((cpt && !e->has_mean && !e->any_oned && e->mix_K == 0) ? 3 : 1) : 2),
-             (!s.simple && e->all_uniform && (!e->has_bounds || e->bounds_box) && e->betaC) ? ", true" : ", false", cpt ? "true" : "false");   // as rocprofv3 prints it
-  }
-  else if ((e->DP == 64 || e->DP == 128) && s.uni && e->all_uniform && (!e->has_bounds || e->bounds_box) && !e->has_mean && !e->any_oned && e->mix_K == 0 && !s.ada && !s.callback &&
-           !s.host_prop && !e->hist.rungs && !e->map.rungs && !(fv && *fv && *fv != '0'))
-    snprintf(b, sizeof b, "sweep_mfma%d_kernel<%d, %s, %s>", e->DP, s.kind == KIND_DIAG ? KIND_LOWER : s.kind, e->has_bounds ? "true" : "false", e->betaC ? "true" : "false");
-  else if (e->DP >= 64 || s.host_prop || (!getenv("PTM_FORCE_VALU") && ((!s.uni && (long long)e->Nc * e->DP <= (e->DP >= 16 ? PTM_LANES_MAX : 4096ll * e->DP)) ||
-                                                                           (s.uni && s.de && e->DP >= 16 && (long long)e->Nc * e->DP <= (e->DP >= 32 ? (1ll << 21) : (1ll << 19))))))   // (launch_kind's rule)
-    snprintf(b, sizeof b, s.ada ? "sweep_lanes_ada_kernel<%d, %d>" : "sweep_lanes_kernel<%d, %d, %s>", e->DP, s.kind, s.plain ? "false" : "true");
-  else if (s.ada) snprintf(b, sizeof b, "sweep_kernel<%d, %d, %s, false, true>", e->DP, s.kind, s.uni ? "true" : "false");
-  else snprintf(b, sizeof b, "sweep_kernel<%d, %d, %s, %s>", e->DP, s.kind, s.uni ? "true" : "false", s.simple ? "true" : "false");
+  format_sweep_name(step_sweep_plan(e), b, sizeof b);   // (in PT steps; the plain sweeps of a big population visit every chain)
   e->kname = b;
   if (e->dfn) e->kname += " + device likelihood";   // (propose pass, pack, the user's work, scatter, accept pass)
   return e->kname.c_str();
@@ -3120,11 +3064,9 @@ extern "C" const char* ptm_step_kernel_name(ptm_engine* e) {
   if (!e) return "";
   static thread_local std::string name;
   char b[160];
-  const bool fused = e->DP <= 16 && (long long)e->Nt * e->DP <= 256 && !user_like(e) && !e->pcb && !e->ada_on && !e->cfg.time_kernels && !(getenv("PTM_FUSED") && *getenv("PTM_FUSED") == '0') &&
-                     !(e->evolve_rate > 0 && (e->W > 64 || e->evolve_cut >= 0));
   if (e->nloc != e->Nt) snprintf(b, sizeof b, "(sharded: ptm_exchange_* / ptm_shard_step) decide_kernel + %s", ptm_sweep_kernel_name(e));
   else if (ladder_applies(e)) snprintf(b, sizeof b, "ladder_persistent_kernel<%d, %d, %d>", e->DP, e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : KIND_DENSE, ladder_flavour(e));
-  else if (fused) snprintf(b, sizeof b, "ladder_steps_kernel<%d, %d, %d>", e->DP, e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : KIND_DENSE, (long long)e->Nt * e->DP <= 64 ? 64 : 256);
+  else if (fused_applies(e)) snprintf(b, sizeof b, "ladder_steps_kernel<%d, %d, %d>", e->DP, e->prop_kind == PTM_PROP_DIAG ? KIND_DIAG : KIND_DENSE, (long long)e->Nt * e->DP <= 64 ? 64 : 256);
   else snprintf(b, sizeof b, "decide_kernel + %s", ptm_sweep_kernel_name(e));
   name = b;
   return name.c_str();

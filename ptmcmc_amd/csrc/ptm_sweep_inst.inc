@@ -1,4 +1,4 @@
-// ptm_sweep_inst.inc -- included by ptm_sweep_dp{4,8,16,32}.hip with PTM_DP defined.
+// ptm_sweep_inst.inc -- included by every ptm_sweep_dp*.hip with PTM_DP defined.
 #include <cstdlib>
 
 #include "ptm_launch.hpp"
@@ -24,192 +24,151 @@
 
 namespace ptm {
 
-// PTM_FORCE_VALU=1 in the environment keeps the VALU kernel on the MFMA kernel's workload (A/B measurements, tests)
-#if PTM_DP == 32
-// resident blocks of the MFMA kernel per CU for its persistent grid (ptm_mfma_kernel.hpp); PTM_PERSIST=0 in the environment
-// launches one block per 256-chain tile instead (A/B measurements)
-static int mfma_grid_blocks(const void* kernel, size_t lds, int ntiles, bool general) {
-  static const int persist = [] { const char* s = getenv("PTM_PERSIST"); return s && *s ? atoi(s) : -1; }();
-  if (persist == 0 || (general && !PTM_MFMA_GEN_PERSIST)) return ntiles;
-  static int ncu = 0;
-  if (!ncu) {
+static_assert(PLAN_DENSE == KIND_DENSE && PLAN_DIAG == KIND_DIAG && PLAN_LOWER == KIND_LOWER, "ptm_sweep_plan.hpp names the kinds of ptm_kernels.hpp");
+
+static int cu_count() {
+  static const int ncu = [] {
     int dev = 0;
     hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ncu = pr.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
-  int per_cu = persist > 0 ? persist : 0;
-  if (per_cu == 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess) per_cu = 0;
-  if (per_cu <= 0) per_cu = 2;
-  const int g = ncu * per_cu;
-  return g < ntiles ? g : ntiles;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) return pr.multiProcessorCount;
+    (void)hipGetLastError();
+    return 0;
+  }();
+  return ncu;
+}
+// how many blocks of a kernel the device holds at once (0: the runtime would not say)
+static int resident_blocks(const void* kernel, int threads, size_t lds) {
+  int per_cu = 0;
+  if (cu_count() <= 0 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); return 0; }
+  return per_cu * cu_count();
+}
+static hipError_t launch1(const void* kernel, int grid, int threads, size_t lds, hipStream_t st, const Dev& p) {
+  void* args[] = {(void*)&p};
+  return hipLaunchKernel(kernel, dim3(grid), dim3(threads), args, lds, st);
+}
+
+// ---- the builds of each family: the plan's template arguments -> the instantiation (every build there is is named here) ----
+#if PTM_DP == 32
+template <int MK>
+static const void* mfma32_kernel_of(const SweepPlan& s) {
+  static const struct { bool hist; int gen; bool ev, cpt; const void* kernel; } builds[] = {
+#define PTM_B(H, G, E, C) {H, G, E, C, (const void*)sweep_mfma32_kernel<MK, H, G, E, C>}
+      PTM_B(false, 0, false, false), PTM_B(true, 0, false, false), PTM_B(false, 0, false, true),   // lean (history; compacted)
+      PTM_B(false, 0, true, false), PTM_B(false, 0, true, true),                                   // lean with evolving ladders
+      PTM_B(false, 1, false, false), PTM_B(true, 1, false, false), PTM_B(false, 1, true, false), PTM_B(true, 1, true, false),   // the usual real-world case: uniform priors, limit bounds
+      PTM_B(false, 1, false, true), PTM_B(false, 1, true, true),                                   // ... compacted
+      PTM_B(false, 3, false, true), PTM_B(false, 3, true, true),                                   // ... and bounds and nothing else -- no mean, no one-dimensional moves, no mixture
+      PTM_B(false, 2, false, false), PTM_B(true, 2, false, false),                                 // everything
+#undef PTM_B
+  };
+  for (const auto& b : builds)
+    if (b.hist == s.hist && b.gen == s.mgen && b.ev == s.ev && b.cpt == s.compacted) return b.kernel;
+  return nullptr;
 }
 #endif
-
-static bool force_valu_path() {
-  static const bool v = [] { const char* s = getenv("PTM_FORCE_VALU"); return s && *s && *s != '0'; }();
-  return v;
+#if PTM_DP == 64 || PTM_DP == 128
+#if PTM_DP == 64
+#define PTM_MFMA_WIDE sweep_mfma64_kernel
+#else
+#define PTM_MFMA_WIDE sweep_mfma128_kernel
+#endif
+template <int MK>
+static const void* mfma_wide_kernel_of(bool bnd, bool ev) {
+  return bnd ? (ev ? (const void*)PTM_MFMA_WIDE<MK, true, true> : (const void*)PTM_MFMA_WIDE<MK, true, false>)
+             : (ev ? (const void*)PTM_MFMA_WIDE<MK, false, true> : (const void*)PTM_MFMA_WIDE<MK, false, false>);
 }
+#endif
+template <int KIND>
+static const void* lanes_kernel_of(const SweepPlan& s) {
+  if (s.family == FAM_LANES_ADA) return (const void*)sweep_lanes_ada_kernel<PTM_DP, KIND>;
+  return s.gen ? (const void*)sweep_lanes_kernel<PTM_DP, KIND, true> : (const void*)sweep_lanes_kernel<PTM_DP, KIND, false>;
+}
+#if PTM_DP <= 32
+template <int KIND>
+static const void* general_kernel_of(const SweepPlan& s) {
+  if (s.ada) return s.uni ? (const void*)sweep_kernel<PTM_DP, KIND, true, false, true> : (const void*)sweep_kernel<PTM_DP, KIND, false, false, true>;
+  if (!s.uni) return (const void*)sweep_kernel<PTM_DP, KIND, false, false>;
+  return s.simple ? (const void*)sweep_kernel<PTM_DP, KIND, true, true> : (const void*)sweep_kernel<PTM_DP, KIND, true, false>;
+}
+#endif
 
 template <int KIND>
-static hipError_t launch_kind(const Dev& p, SweepSel s, hipStream_t st, const AdaArgs& ada) {
-  const dim3 grid((p.c_end - p.c_begin + 255) / 256), block(256);
-  // UNI kernels stage one copy of the rung's factor per wave in LDS (4 waves per block)
-  // plus the 20 KB of Box-Muller tables every variant stages
-  const size_t tab = BM_TABLE_DOUBLES * sizeof(double);
-  const size_t lds = tab + ((s.uni && KIND != KIND_DIAG) ? (size_t)4 * p.prop_stride * sizeof(double) : 0);
+static hipError_t launch_kind(const Dev& p, const SweepPlan& s, hipStream_t st, const AdaArgs& ada) {
+  const int chains = p.c_end - p.c_begin;
+  (void)ada;
+  switch (s.family) {
 #if PTM_DP == 32
-  if (s.uni && p.mode == 0 && !s.callback && !s.host_prop && !s.de && !s.ada && !force_valu_path()) {
-    constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // a diagonal factor is a (very sparse) Cholesky factor
-    // the BASELINE workload: both matrix products on the f64 matrix cores (ptm_mfma_kernel.hpp)
-    // LDS: tables | P2 tiles | box | 4 x 128 reduction slots | (general: 6 x 32 doubles + 3 x 32 ints + 4 x 128 slots)
-    const size_t mlds_lean = (BM_TABLE_DOUBLES + 12 * 64 + 64 + 4 * 128) * sizeof(double);
-    const size_t mlds = (s.simple || s.lean_ev) ? mlds_lean : mlds_lean + (6 * 32 + 48 + 4 * 128 + 64) * sizeof(double);
-    const bool hist = p.hist.rungs != 0 || p.map.rungs != 0;   // the build that carries history / MAP code
-    const int ntiles = (p.c_end - p.c_begin + 255) / 256;
-#define PTM_LAUNCH_MFMA(...)                                                                             \
-    do {                                                                                                 \
-      const void* kf = (const void*)(__VA_ARGS__);                                                       \
-      hipLaunchKernelGGL((__VA_ARGS__), dim3(mfma_grid_blocks(kf, mlds, ntiles, !s.simple)), block, mlds, st, p);   \
-    } while (0)
-    if (s.simple && !hist && p.cidx) {   // compacted: the moving chains only (the engine ran partition_kernel)
-      const size_t mlds0 = mlds;
-      const size_t mlds = mlds0 + ((size_t)(p.c_end - p.c_begin) / p.W + 260) * sizeof(int);
-      PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, false, 0, false, true>);
-    } else if (s.simple) {
-      if (hist) PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, true, 0>);
-      else PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, false, 0>);
-    } else if (s.lean_ev) {   // the plain workload with evolving ladders: the lean build reading per-chain temperatures
-      const void* kf = p.cidx ? (const void*)sweep_mfma32_kernel<MK, false, 0, true, true> : (const void*)sweep_mfma32_kernel<MK, false, 0, true, false>;
-      const size_t mlds_ev = mlds + (p.cidx ? ((size_t)(p.c_end - p.c_begin) / p.W + 260) * sizeof(int) : 0);
-      const dim3 grid(mfma_grid_blocks(kf, mlds_ev, ntiles, false));
-      if (p.cidx) hipLaunchKernelGGL((sweep_mfma32_kernel<MK, false, 0, true, true>), grid, block, mlds_ev, st, p);
-      else hipLaunchKernelGGL((sweep_mfma32_kernel<MK, false, 0, true, false>), grid, block, mlds_ev, st, p);
-    } else if (p.all_uniform && (!p.has_bounds || p.bounds_box) && !hist && p.cidx) {   // ... compacted (no history)
-      const size_t mlds0 = mlds;
-      const size_t mlds = mlds0 + ((size_t)(p.c_end - p.c_begin) / p.W + 260) * sizeof(int);
-      const bool general = false;   // (a persistent grid, like the lean build's)
-#define PTM_LAUNCH_MFMA_P(...)                                                                           \
-      do {                                                                                               \
-        const void* kf = (const void*)(__VA_ARGS__);                                                     \
-        hipLaunchKernelGGL((__VA_ARGS__), dim3(mfma_grid_blocks(kf, mlds, ntiles, general)), block, mlds, st, p);   \
-      } while (0)
-      // (bounds and nothing else -- no mean, no one-dimensional moves, no mixture: the build that carries none of them, GEN 3)
-      const bool lite = !p.has_mean && !p.any_oned && p.mix_K == 0;
-      if (lite && p.betaC) PTM_LAUNCH_MFMA_P(sweep_mfma32_kernel<MK, false, 3, true, true>);
-      else if (lite) PTM_LAUNCH_MFMA_P(sweep_mfma32_kernel<MK, false, 3, false, true>);
-      else if (p.betaC) PTM_LAUNCH_MFMA_P(sweep_mfma32_kernel<MK, false, 1, true, true>);
-      else PTM_LAUNCH_MFMA_P(sweep_mfma32_kernel<MK, false, 1, false, true>);
-#undef PTM_LAUNCH_MFMA_P
-    } else if (p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.betaC) {   // the usual real-world case: uniform priors, limit bounds
-      if (hist) PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, true, 1>);
-      else PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, false, 1>);
-    } else if (p.all_uniform && (!p.has_bounds || p.bounds_box)) {                // ... with evolving ladders
-      if (hist) PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, true, 1, true>);
-      else PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, false, 1, true>);
-    } else {
-      if (hist) PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, true, 2>);
-      else PTM_LAUNCH_MFMA(sweep_mfma32_kernel<MK, false, 2>);
+    case FAM_MFMA32: {
+      // LDS: tables | P2 tiles | box | 4 x 128 reduction slots | (general: 6 x 32 doubles + 3 x 32 ints + 4 x 128 slots) | (compacted: the rungs' list ends)
+      const size_t lds = (BM_TABLE_DOUBLES + 12 * 64 + 64 + 4 * 128) * sizeof(double) + (s.mgen == 0 ? 0 : (6 * 32 + 48 + 4 * 128 + 64) * sizeof(double)) +
+                         (s.compacted ? ((size_t)chains / p.W + 260) * sizeof(int) : 0);
+      constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // (the plan never names a diagonal build of this family)
+      const void* kf = mfma32_kernel_of<MK>(s);
+      if (!kf) return hipErrorNotSupported;
+      // a persistent grid of the resident blocks for the lean and the compacted builds, one block per 256-chain tile for the others
+      // (PTM_MFMA_GEN_PERSIST); PTM_PERSIST=n in the environment: n blocks per CU, 0: one block per tile for all (A/B measurements)
+      static const int persist = [] { const char* v = getenv("PTM_PERSIST"); return v && *v ? atoi(v) : -1; }();
+      int grid = (chains + 255) / 256;
+      if (persist != 0 && (s.mgen == 0 || s.compacted || PTM_MFMA_GEN_PERSIST)) {
+        const int ncu = cu_count() > 0 ? cu_count() : 256;
+        int g = persist > 0 ? ncu * persist : resident_blocks(kf, 256, lds);
+        if (g <= 0) g = ncu * 2;
+        if (g < grid) grid = g;
+      }
+      return launch1(kf, grid, 256, lds, st, p);
     }
-#undef PTM_LAUNCH_MFMA
-    return hipGetLastError();
-  }
 #endif
+#if PTM_DP == 64 || PTM_DP == 128
+    case FAM_MFMA64:
+    case FAM_MFMA128: {
+      // (the 128-D kernel: 97 KB of LDS, one block per CU)
+      constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // (the plan never names a diagonal build of this family)
 #if PTM_DP == 64
-  // 33..64 dimensions, whole waves per rung, the plain workload without history: both products on the f64 matrix cores
-  // (ptm_mfma64_kernel.hpp); everything else at these dimensions keeps the lanes kernel
-  // (the plain workload, or open / `limit` bounds and / or evolving ladders on top of it: template flags BND, EV)
-  if (s.uni && p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.has_mean && !p.any_oned && p.mix_K == 0 && !s.ada && p.mode == 0 && !s.callback && !s.host_prop &&
-      !p.hist.rungs && !p.map.rungs && !force_valu_path()) {
-    constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // a diagonal factor is a (very sparse) Cholesky factor
-    const size_t mlds = (size_t)m64_lds_doubles() * sizeof(double);
-    const bool bnd = p.has_bounds != 0, ev = p.betaC != nullptr;
-    const void* kf = bnd ? (ev ? (const void*)sweep_mfma64_kernel<MK, true, true> : (const void*)sweep_mfma64_kernel<MK, true, false>)
-                         : (ev ? (const void*)sweep_mfma64_kernel<MK, false, true> : (const void*)sweep_mfma64_kernel<MK, false, false>);
-    const int ntiles = (p.c_end - p.c_begin + 255) / 256;
-    static int resident = 0;
-    if (!resident) {
-      int dev = 0, per_cu = 0;
-      hipDeviceProp_t pr;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)sweep_mfma64_kernel<MK, true, true>, 256, mlds) == hipSuccess && per_cu > 0)
-        resident = per_cu * pr.multiProcessorCount;   // (the build with the most registers: the same grid for all four)
-      else { (void)hipGetLastError(); resident = 512; }
-    }
-    void* args[] = {(void*)&p};
-    return hipLaunchKernel(kf, dim3(resident < ntiles ? resident : ntiles), block, args, mlds, st);
-  }
-#endif
-#if PTM_DP == 128
-  // 65..128 dimensions, whole waves per rung, the plain workload without history: both products on the f64 matrix cores
-  // (ptm_mfma128_kernel.hpp: 97 KB of LDS, one block per CU); everything else at these dimensions keeps the lanes kernel
-  // (the plain workload, or open / `limit` bounds and / or evolving ladders on top of it: template flags BND, EV)
-  if (s.uni && p.all_uniform && (!p.has_bounds || p.bounds_box) && !p.has_mean && !p.any_oned && p.mix_K == 0 && !s.ada && p.mode == 0 && !s.callback && !s.host_prop &&
-      !p.hist.rungs && !p.map.rungs && !force_valu_path()) {
-    constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // a diagonal factor is a (very sparse) Cholesky factor
-    const size_t mlds = (size_t)m128_lds_doubles() * sizeof(double);
-    const bool bnd = p.has_bounds != 0, ev = p.betaC != nullptr;
-    const void* kf = bnd ? (ev ? (const void*)sweep_mfma128_kernel<MK, true, true> : (const void*)sweep_mfma128_kernel<MK, true, false>)
-                         : (ev ? (const void*)sweep_mfma128_kernel<MK, false, true> : (const void*)sweep_mfma128_kernel<MK, false, false>);
-    const int ntiles = (p.c_end - p.c_begin + M128_THREADS - 1) / M128_THREADS;
-    static int resident = 0;
-    if (!resident) {
-      int dev = 0, per_cu = 0;
-      hipDeviceProp_t pr;
-      const void* all4[] = {(const void*)sweep_mfma128_kernel<MK, false, false>, (const void*)sweep_mfma128_kernel<MK, false, true>,
-                            (const void*)sweep_mfma128_kernel<MK, true, false>, (const void*)sweep_mfma128_kernel<MK, true, true>};
-      for (const void* f : all4)
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds) != hipSuccess) return hipGetLastError();
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, all4[3], M128_THREADS, mlds) == hipSuccess && per_cu > 0)
-        resident = per_cu * pr.multiProcessorCount;
-      else { (void)hipGetLastError(); resident = 256; }
-    }
-    void* args[] = {(void*)&p};
-    return hipLaunchKernel(kf, dim3(resident < ntiles ? resident : ntiles), dim3(M128_THREADS), args, mlds, st);
-  }
-#endif
-  // (33..128 dimensions: the lanes kernel serves small populations and the general workloads)
-  // (the host-callback passes -- mode 1 / 2 -- are in its general build; up to 8 dimensions a chain is little work for
-  //  one lane, and the lanes kernel is the choice of the latency regime only)
-  constexpr long long LANES_MAX = PTM_DP >= 16 ? PTM_LANES_MAX : 4096ll * PTM_DP;
-  // (differential evolution keeps a population with whole waves per rung off the matrix cores: from 9 dimensions on its moderate sizes
-  //  are better off with a lane per dimension than with a lane walking a chain)
-  //  (measured, tools/de_probe_walkers.sh, us per step lanes / lane-per-chain: 12 dimensions x 4096 chains 40 / 57, x 16384 50 / 62,
-  //   x 65536 96 / 75; 32 dimensions x 8192 chains 49 / 131)
-  constexpr long long LANES_MAX_DE = PTM_DP >= 32 ? (1ll << 21) : (1ll << 19);
-  const long long lanes_wanted = (long long)(p.c_end - p.c_begin) * PTM_DP;
-  if (PTM_DP >= 64 || s.host_prop || (!force_valu_path() && ((!s.uni && lanes_wanted <= LANES_MAX) || (s.uni && s.de && PTM_DP >= 16 && lanes_wanted <= LANES_MAX_DE)))) {
-    // small populations (fewer than 64 walkers per rung): a lane per dimension instead of a lane per chain -- a sixteenth
-    // of the latency, twice the lane-work per chain: the better trade until the chip is full of waves
-    constexpr int CPW = PTM_DP > 64 ? 1 : 64 / PTM_DP;
-    const dim3 lgrid((p.c_end - p.c_begin + 4 * CPW - 1) / (4 * CPW));
-    const size_t llds = (size_t)lanes_lds_doubles<PTM_DP>(4) * sizeof(double);
-    if (llds > 64 * 1024) {   // (65..128 dimensions: the packed precision matrix alone is 66 KB)
-      hipError_t rc = hipFuncSetAttribute(s.ada ? (const void*)sweep_lanes_ada_kernel<PTM_DP, KIND>
-                                                : s.plain ? (const void*)sweep_lanes_kernel<PTM_DP, KIND, false> : (const void*)sweep_lanes_kernel<PTM_DP, KIND, true>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds);
-      if (rc != hipSuccess) return rc;
-    }
-    if (s.ada) hipLaunchKernelGGL((sweep_lanes_ada_kernel<PTM_DP, KIND>), lgrid, block, llds, st, p, ada);
-    else if (s.plain) hipLaunchKernelGGL((sweep_lanes_kernel<PTM_DP, KIND, false>), lgrid, block, llds, st, p);
-    else hipLaunchKernelGGL((sweep_lanes_kernel<PTM_DP, KIND, true>), lgrid, block, llds, st, p);
-    return hipGetLastError();
-  }
-#if PTM_DP <= 32
-  if (s.ada && s.uni) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, false, true>), grid, block, lds, st, p, ada);
-  else if (s.ada) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, false, false, true>), grid, block, tab, st, p, ada);
-  else if (s.uni && s.simple) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, true>), grid, block, lds, st, p, AdaArgs());
-  else if (s.uni) hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, true, false>), grid, block, lds, st, p, AdaArgs());
-  else hipLaunchKernelGGL((sweep_kernel<PTM_DP, KIND, false, false>), grid, block, tab, st, p, AdaArgs());
-  return hipGetLastError();
+      constexpr int threads = 256;
+      const size_t lds = (size_t)m64_lds_doubles() * sizeof(double);
 #else
-  (void)grid; (void)lds; (void)tab;
-  return hipErrorNotSupported;
+      constexpr int threads = M128_THREADS;
+      const size_t lds = (size_t)m128_lds_doubles() * sizeof(double);
 #endif
+      static int resident = 0;   // (per factor kind; of the build with the most registers: the same grid for all four)
+      if (!resident) {
+#if PTM_DP == 128
+        for (int k = 0; k < 4; ++k)
+          if (hipFuncSetAttribute(mfma_wide_kernel_of<MK>(k & 2, k & 1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return hipGetLastError();
+#endif
+        resident = resident_blocks(mfma_wide_kernel_of<MK>(true, true), threads, lds);
+        if (!resident) resident = PTM_DP == 64 ? 512 : 256;
+      }
+      const int ntiles = (chains + threads - 1) / threads;
+      return launch1(mfma_wide_kernel_of<MK>(s.bnd, s.ev), resident < ntiles ? resident : ntiles, threads, lds, st, p);
+    }
+#endif
+    case FAM_LANES:
+    case FAM_LANES_ADA: {
+      constexpr int CPW = PTM_DP > 64 ? 1 : 64 / PTM_DP;   // chains per wave
+      const size_t lds = (size_t)lanes_lds_doubles<PTM_DP>(4) * sizeof(double);
+      const void* kf = lanes_kernel_of<KIND>(s);
+      if (lds > 64 * 1024) {   // (65..128 dimensions: the packed precision matrix alone is 66 KB)
+        hipError_t rc = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (rc != hipSuccess) return rc;
+      }
+      void* args[] = {(void*)&p, (void*)&ada};
+      return hipLaunchKernel(kf, dim3((chains + 4 * CPW - 1) / (4 * CPW)), dim3(256), args, lds, st);
+    }
+#if PTM_DP <= 32
+    case FAM_GENERAL: {
+      // the 20 KB of Box-Muller tables every variant stages; UNI builds stage one copy of the rung's factor per wave too (4 waves per block)
+      const size_t lds = BM_TABLE_DOUBLES * sizeof(double) + ((s.uni && KIND != KIND_DIAG) ? (size_t)4 * p.prop_stride * sizeof(double) : 0);
+      const AdaArgs none = AdaArgs();
+      void* args[] = {(void*)&p, (void*)(s.ada ? &ada : &none)};
+      return hipLaunchKernel(general_kernel_of<KIND>(s), dim3((chains + 255) / 256), dim3(256), args, lds, st);
+    }
+#endif
+    default: return hipErrorNotSupported;
+  }
 }
 
-hipError_t PTM_CAT(launch_sweep_, PTM_DP)(const Dev& p, SweepSel s, hipStream_t st, const AdaArgs& ada) {
+static hipError_t launch_sweep(const Dev& p, const SweepPlan& s, hipStream_t st, const AdaArgs& ada) {
   switch (s.kind) {
     case KIND_DIAG: return launch_kind<KIND_DIAG>(p, s, st, ada);
     case KIND_LOWER: return launch_kind<KIND_LOWER>(p, s, st, ada);
@@ -228,8 +187,7 @@ static hipError_t launch_fused_kt(const Dev& p, const Decide& d, int nsteps, int
   hipLaunchKernelGGL((ladder_steps_kernel<PTM_DP, KIND, T>), dim3(p.W), dim3(T), lds, st, p, d, nsteps, swap_log_base, log_head);
   return hipGetLastError();
 }
-hipError_t PTM_CAT(launch_fused_, PTM_DP)(const Dev& p, const Decide& d, bool diag, int nsteps, int* swap_log_base, int log_head, size_t decide_lds,
-                                          hipStream_t st) {
+static hipError_t launch_fused(const Dev& p, const Decide& d, bool diag, int nsteps, int* swap_log_base, int log_head, size_t decide_lds, hipStream_t st) {
   const int lanes = p.Nt * PTM_DP;
 #define PTM_FUSED_T(T)                                                                                                        \
   return diag ? launch_fused_kt<KIND_DIAG, T>(p, d, nsteps, swap_log_base, log_head, decide_lds, st)                            \
@@ -246,7 +204,7 @@ hipError_t PTM_CAT(launch_fused_, PTM_DP)(const Dev& p, const Decide& d, bool di
 
 #if PTM_DP <= 32
 // the persistent ladder kernel (ptm_ladder_kernel.hpp): DENSE serves Cholesky factors too (a lane reads its whole row)
-size_t PTM_CAT(ladder_lds_, PTM_DP)(int Nt, int ms, bool ev) {
+static size_t ladder_lds(int Nt, int ms, bool ev) {
   return (size_t)((lanes_lds_doubles<PTM_DP>(4) + 1) & ~1) * sizeof(double) + ladder_decide_lds_bytes(Nt, ms) + ladder_window_lds_bytes(PTM_DP) + ladder_psq_lds_bytes(PTM_DP) + 16 +
          (ev ? ladder_ev_lds_bytes(Nt, ms) : 0);
 }
@@ -271,31 +229,42 @@ static const void* ladder_kernel_of(bool diag, int fl) {
 #undef PTM_LK
 }
 // how many workgroups of that build the device holds at once (the dynamic-LDS attribute is set on THIS build: asked per build)
-int PTM_CAT(ladder_blocks_, PTM_DP)(bool diag, int fl, size_t lds) {
+static int ladder_blocks(bool diag, int fl, size_t lds) {
   const void* kf = ladder_kernel_of(diag, fl);
   if (lds > 64 * 1024 && hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  int dev = 0, per_cu = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, LADDER_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  return per_cu > 0 ? per_cu * pr.multiProcessorCount : 0;
+  return resident_blocks(kf, LADDER_THREADS, lds);
 }
-hipError_t PTM_CAT(launch_ladder_, PTM_DP)(const Dev& p, const LadderArgs& a, bool diag, int fl, int grid, size_t lds, hipStream_t st) {
+static hipError_t launch_ladder(const Dev& p, const LadderArgs& a, bool diag, int fl, int grid, size_t lds, hipStream_t st) {
   void* args[] = {(void*)&p, (void*)&a};
   return hipLaunchKernel(ladder_kernel_of(diag, fl), dim3(grid), dim3(LADDER_THREADS), args, lds, st);
 }
 #endif
 
-hipError_t PTM_CAT(launch_eval_, PTM_DP)(const Dev& p, int n, double* x, int* valid, double* lp, double* ll, int eval_like,
-                                         hipStream_t st) {
+static hipError_t launch_eval(const Dev& p, int n, double* x, int* valid, double* lp, double* ll, int eval_like, hipStream_t st) {
   hipLaunchKernelGGL((evaluate_kernel<PTM_DP>), dim3((n + 255) / 256), dim3(256), 0, st, p, n, x, valid, lp, ll, eval_like);
   return hipGetLastError();
 }
 
-hipError_t PTM_CAT(launch_init_, PTM_DP)(const Dev& p, double* x, double* ll, double* lp, int* fail, long long cb_attempt,
-                                         unsigned char* pending, hipStream_t st) {
+static hipError_t launch_init(const Dev& p, double* x, double* ll, double* lp, int* fail, long long cb_attempt, unsigned char* pending, hipStream_t st) {
   hipLaunchKernelGGL((init_prior_kernel<PTM_DP>), dim3((p.Nc + 255) / 256), dim3(256), 0, st, p, x, ll, lp, fail, cb_attempt, pending);
   return hipGetLastError();
 }
+
+// this dimension's entry of the launch table (ptm_launch.hpp); host code only
+#if !defined(__HIP_DEVICE_COMPILE__)
+extern const DpLaunch PTM_CAT(dp_launch_, PTM_DP) = {
+    launch_sweep, launch_eval, launch_init,
+#if PTM_DP <= 16
+    launch_fused,
+#else
+    nullptr,
+#endif
+#if PTM_DP <= 32
+    ladder_lds, ladder_blocks, launch_ladder,
+#else
+    nullptr, nullptr, nullptr,
+#endif
+};
+#endif
 
 }  // namespace ptm

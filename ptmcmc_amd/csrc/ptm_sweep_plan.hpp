@@ -1,0 +1,146 @@
+// ptm_sweep_plan.hpp -- which kernel a sweep (and a whole step) runs on: the decision, once, as plain C++ (no HIP: the
+// launches in ptm_sweep_inst.inc, the engine's preparations for them and the names it reports all read the same plan).
+#pragma once
+#include <cstddef>
+#include <cstdio>
+#include <cstdlib>
+
+namespace ptm {
+
+enum { PLAN_DENSE = 0, PLAN_DIAG = 1, PLAN_LOWER = 2 };   // the proposal factor's storage: KIND_* of ptm_kernels.hpp
+
+// everything the choice of a sweep kernel depends on
+struct SweepFacts {
+  int DP, W;            // padded dimension, walkers per rung
+  long long chains;     // the chains of this launch (c_end - c_begin)
+  int nloc;             // local rungs
+  int kind;             // PLAN_*
+  bool has_bounds, bounds_box, all_uniform, has_mean, any_oned;
+  int mix_K;
+  bool evolving;        // evolving ladders: per-chain temperatures (betaC)
+  bool tracked;         // history or MAP tracking
+  bool user_like;       // a user likelihood, on the host or on the device (propose / accept passes)
+  bool host_prop;       // host-side proposals: they take over from every device proposal
+  bool de, ada;         // differential evolution drawn on the device; an adaptive proposal set
+  int mode;             // 0: a whole sweep, 1 / 2: the propose / accept pass around a user likelihood
+  bool touched;         // an exchange phase ran since the last sweep
+};
+
+// the environment's say: PTM_FORCE_VALU set, non-empty and not "0" keeps every workload off the matrix cores and off the lanes
+// kernel's population rules (A/B measurements, tests); PTM_COMPACT=0 switches the compacted sweep off.  Read once per process.
+struct SweepEnv {
+  bool force_valu, compact_ok;
+};
+inline const SweepEnv& sweep_env() {
+  static const SweepEnv v = [] {
+    const char* f = getenv("PTM_FORCE_VALU");
+    const char* c = getenv("PTM_COMPACT");
+    return SweepEnv{f && *f && *f != '0', !(c && *c == '0')};
+  }();
+  return v;
+}
+
+enum SweepFamily { FAM_GENERAL, FAM_LANES, FAM_LANES_ADA, FAM_MFMA32, FAM_MFMA64, FAM_MFMA128 };
+
+// the chosen build: the family's kernel template and every argument of it
+struct SweepPlan {
+  SweepFamily family;
+  int DP, kind;          // all families (the matrix-core kernels take a diagonal factor as a Cholesky factor)
+  bool uni, simple, ada; // sweep_kernel<DP, KIND, UNI, SIMPLE, ADA>
+  bool gen;              // sweep_lanes_kernel<DP, KIND, GEN>   (sweep_lanes_ada_kernel<DP, KIND>)
+  bool hist;             // sweep_mfma32_kernel<KIND, HIST, MGEN, EV, compacted>
+  int mgen;
+  bool ev;
+  bool bnd;              // sweep_mfma{64,128}_kernel<KIND, BND, EV>
+  bool compacted;        // the moving chains' lists are to be built (partition_kernel) before the launch
+};
+// the lean matrix-core build of evolving ladders reads the ladder-major temperatures, every other build the chain-indexed image
+inline bool reads_ladder_major_beta(const SweepPlan& s) { return s.family == FAM_MFMA32 && s.mgen == 0 && s.ev; }
+
+// the lanes kernel (ptm_lanes_kernel.hpp) takes launches of at most this many lanes (chains x padded dimension)
+#define PTM_LANES_MAX (1ll << 20)
+
+inline SweepPlan plan_sweep(const SweepFacts& f, const SweepEnv& env) {
+  SweepPlan s = {};
+  s.DP = f.DP;
+  s.kind = f.host_prop ? PLAN_DIAG : f.kind;                 // (host-side proposals read no factor: any instantiation serves)
+  const bool uni = (f.W % 64) == 0;                          // whole waves per rung
+  const bool ada = f.ada && !f.host_prop;                    // (host-side proposals take over from an adaptive set)
+  const bool box = f.all_uniform && (!f.has_bounds || f.bounds_box);   // uniform priors, open / `limit` bounds
+  const bool recipe = f.has_mean || f.any_oned || f.mix_K != 0;         // a mean, one-dimensional moves, a scale mixture
+  // open bounds, all-uniform prior, zero mean, no 1-D moves, no mixture, fixed ladder, device target and proposals
+  const bool plain = !f.has_bounds && f.all_uniform && !recipe && !f.user_like && !ada && !f.evolving && !f.host_prop;
+  const bool simple = uni && plain;
+  // ... plain but for evolving ladders, untracked: the lean matrix-core build that reads per-chain temperatures
+  const bool lean_ev = uni && f.evolving && !f.has_bounds && f.all_uniform && !recipe && !f.user_like && !ada && !f.host_prop && !f.tracked;
+  const bool mfma_ok = uni && f.mode == 0 && !f.user_like && !f.host_prop && !ada && !env.force_valu;
+  const int mk = s.kind == PLAN_DIAG ? PLAN_LOWER : s.kind;  // a diagonal factor is a (very sparse) Cholesky factor
+
+  if (f.DP == 32 && mfma_ok && !f.de) {
+    // both matrix products on the f64 matrix cores (ptm_mfma_kernel.hpp).  Compacted: after an exchange phase ~1/6 of a long ladder's
+    // chains make no move, and the untracked builds of a big population visit the moving chains only (the same answer for every
+    // partial sweep of a step)
+    s.family = FAM_MFMA32; s.kind = mk;
+    s.compacted = env.compact_ok && f.touched && box && !f.tracked && f.W >= 1024 && f.nloc <= 4096;
+    s.hist = f.tracked;
+    // 0 lean; 1 uniform priors and box bounds with the recipe's code, 3 without it (built compacted only); 2 everything
+    s.mgen = (simple || lean_ev) ? 0 : !box ? 2 : (s.compacted && !recipe) ? 3 : 1;
+    s.ev = !simple && box && f.evolving;
+    return s;
+  }
+  if ((f.DP == 64 || f.DP == 128) && mfma_ok && box && !recipe && !f.tracked) {
+    // 33..128 dimensions, whole waves per rung, the plain workload (or open / `limit` bounds and / or evolving ladders on top of it)
+    // without history (ptm_mfma64_kernel.hpp, ptm_mfma128_kernel.hpp); everything else at these dimensions keeps the lanes kernel
+    s.family = f.DP == 64 ? FAM_MFMA64 : FAM_MFMA128; s.kind = mk;
+    s.bnd = f.has_bounds; s.ev = f.evolving;
+    return s;
+  }
+  // A lane per dimension instead of a lane per chain -- a sixteenth of the latency, twice the lane-work per chain: small populations
+  // (fewer than 64 walkers per rung) until the chip is full of waves; up to 8 dimensions a chain is little work for one lane, and the
+  // lanes kernel is the choice of the latency regime only.  Differential evolution keeps a population with whole waves per rung off
+  // the matrix cores: from 9 dimensions on its moderate sizes are better off here than with a lane walking a chain
+  // (measured, tools/de_probe_walkers.sh, us per step lanes / lane-per-chain: 12 dimensions x 4096 chains 40 / 57, x 16384 50 / 62,
+  //  x 65536 96 / 75; 32 dimensions x 8192 chains 49 / 131)
+  const long long lanes = f.chains * f.DP;
+  const long long lanes_max = f.DP >= 16 ? PTM_LANES_MAX : 4096ll * f.DP, lanes_max_de = f.DP >= 32 ? (1ll << 21) : (1ll << 19);
+  if (f.DP >= 64 || f.host_prop ||
+      (!env.force_valu && ((!uni && lanes <= lanes_max) || (uni && f.de && f.DP >= 16 && lanes <= lanes_max_de)))) {
+    s.family = ada ? FAM_LANES_ADA : FAM_LANES;
+    s.gen = !plain;
+    return s;
+  }
+  s.family = FAM_GENERAL;
+  s.uni = uni; s.simple = simple; s.ada = ada;
+  return s;
+}
+
+// the kernel's name as rocprofv3 prints it (sweep_kernel without its last, defaulted argument unless that is set); returns snprintf's count
+inline int format_sweep_name(const SweepPlan& s, char* b, size_t n) {
+  const auto tf = [](bool v) { return v ? "true" : "false"; };
+  switch (s.family) {
+    case FAM_MFMA32: return snprintf(b, n, "sweep_mfma32_kernel<%d, %s, %d, %s, %s>", s.kind, tf(s.hist), s.mgen, tf(s.ev), tf(s.compacted));
+    case FAM_MFMA64:
+    case FAM_MFMA128: return snprintf(b, n, "sweep_mfma%d_kernel<%d, %s, %s>", s.DP, s.kind, tf(s.bnd), tf(s.ev));
+    case FAM_LANES: return snprintf(b, n, "sweep_lanes_kernel<%d, %d, %s>", s.DP, s.kind, tf(s.gen));
+    case FAM_LANES_ADA: return snprintf(b, n, "sweep_lanes_ada_kernel<%d, %d>", s.DP, s.kind);
+    default: break;
+  }
+  if (s.ada) return snprintf(b, n, "sweep_kernel<%d, %d, %s, false, true>", s.DP, s.kind, tf(s.uni));
+  return snprintf(b, n, "sweep_kernel<%d, %d, %s, %s>", s.DP, s.kind, tf(s.uni), tf(s.simple));
+}
+
+// Small ladders (rungs x padded dimensions <= 256 lanes, device target and proposals): whole PT steps in one launch, a block per
+// walker-ladder (ptm_fused_kernel.hpp).  decide_lds: decide_lds_bytes of the engine's exchange phase, which shares the block's LDS.
+struct StepFacts {
+  int DP, Nt, W;
+  bool user_like, host_prop, ada, time_kernels;
+  bool evolving, evolve_cut;   // evolving ladders; ... with a posterior-ordering cut
+  size_t decide_lds;
+};
+inline bool fused_applies(const StepFacts& f, bool fused_ok) {
+  if (!fused_ok || f.DP > 16 || (long long)f.Nt * f.DP > 256 || f.user_like || f.host_prop || f.ada || f.time_kernels) return false;
+  if (f.evolving && (f.W > 64 || f.evolve_cut)) return false;   // (the new temperatures' chain-indexed image is then a separate launch)
+  return f.decide_lds <= 96 * 1024;
+}
+
+}  // namespace ptm
