@@ -472,6 +472,22 @@ int ptm_ess_series_report(int device, const double* series, int64_t n, int nseri
 /* 1 if the last ptm_ess_* call of this engine ran the device kernels (0 also where the series were too short for one window: nothing to launch) */
 int ptm_ess_last_on_device(ptm_engine* e);
 
+/* ---- log-evidence by thermodynamic integration on the device -------------------------------------------------------------
+ * parallel_tempering_chains::log_evidence_ratio and the total of the statistics block (chain.cc:1984-2012, 1585-1597) as the
+ * facade's evidence_estimator restates them (ptmcmc_amd/host/ptmcmc_gpu.hh), for every walker's ladder at once, on the saved
+ * llikes of the history ring.  Chain (rung r, walker w) looks at the last `ilen` of its own add_state calls (PTM_ARR_NHIST):
+ * saved rows [1 + (Nhist - ilen) / add_every_n, 1 + (Nhist - 1) / add_every_n) -- the newest saved row is left out and a chain
+ * shorter than ilen has no row (count 0, NaN: the reference's 0 / 0).  up[i*W + w] = mean of llike * (beta_i - beta_i+1) over
+ * rung i+1's window, down[i*W + w] = -mean of llike * (beta_i+1 - beta_i) over rung i's, with the chains' CURRENT inverse
+ * temperatures (the ladder's, or the walker's own once the ladders evolve); log_evidence[w] = sum_i (up_i + down_i) / 2 plus
+ * the last pair's term / (beta_Nt-2 / beta_Nt-1 - 1).  Every sum is sequential in the host's order: the host estimator's bits.
+ * Runs on the engine's stream and waits for it.  up / down / count may be NULL.
+ * PTM_ERR_INVALID: a null engine or output, ilen < 1, no history ring, history_rungs < n_rungs, n_rungs < 2, or a window row
+ * the ring no longer holds ("history_capacity must hold the evidence window": the outputs are left untouched).
+ * PTM_ERR_UNSUPPORTED: a rung shard (the reference has no MPI form either, chain.cc:1592); walker splits are ordinary engines. */
+int ptm_log_evidence(ptm_engine* e, int ilen, double* log_evidence /*[W]*/, double* up /*[(Nt-1)*W] or NULL*/,
+                     double* down /*[(Nt-1)*W] or NULL*/, int32_t* count /*[Nt*W] or NULL*/);
+
 /* ---- verification hooks (used by tests/ only; evaluate device functions on arrays) ---------------------- */
 enum { PTM_FN_LOG = 0, PTM_FN_EXP = 1, PTM_FN_SIN_0_PI = 2, PTM_FN_COS_HPI = 3, PTM_FN_SQRT = 4, PTM_FN_DIV = 5,
        PTM_FN_SQRT_RAW = 6 };

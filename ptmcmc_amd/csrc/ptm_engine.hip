@@ -20,6 +20,7 @@
 #include "ptm_aux_kernels.hpp"
 #include "ptm_devlike_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
+#include "ptm_evidence_kernels.hpp"
 #include "ptm_launch.hpp"
 #include "ptm_shard_rccl.hpp"
 
@@ -3335,6 +3336,59 @@ extern "C" int ptm_ess_series_report(int device, const double* series, int64_t n
     return ess_windowed_run(nullptr, &S.ws, &S.ws_bytes, S.src, nseries, nullptr, sel, k, nfeat, p.width, p.every, p.burn, out_e, out_n, nullptr);
   };
   return ess_report_run(nullptr, (int)n, nseries, width, every, esslimit, pass, ess, length);
+}
+
+// ---- log-evidence by thermodynamic integration on the device (ptm_evidence_kernels.hpp) --------------------------------------
+// evidence_estimator (ptmcmc_amd/host/ptmcmc_gpu.hh) on the ring where it lies, for every walker's ladder at once.  The kernels
+// write into the workspace; the caller's arrays are filled only when no row of a window was missing.
+extern "C" int ptm_log_evidence(ptm_engine* e, int ilen, double* log_evidence, double* up, double* down, int32_t* count) {
+  if (!e || !log_evidence) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_log_evidence");
+  if (ilen < 1) return fail(PTM_ERR_INVALID, "ptm_log_evidence: ilen must be >= 1");
+  if (!e->hist.rungs) return fail(PTM_ERR_INVALID, "this engine keeps no history (ptm_config.history_rungs)");
+  if (e->nloc != e->Nt) return fail(PTM_ERR_UNSUPPORTED, "ptm_log_evidence on a rung shard (the integral runs over the whole ladder; split populations by walkers)");
+  if (e->hist.rungs < e->Nt) return fail(PTM_ERR_INVALID, "ptm_log_evidence reads every rung's saved llikes: history_rungs (%d) must be n_rungs (%d)", e->hist.rungs, e->Nt);
+  if (e->Nt < 2) return fail(PTM_ERR_INVALID, "ptm_log_evidence needs a ladder of at least two rungs");
+  if (!e->have_ladder) return fail(PTM_ERR_INVALID, "no ladder set");
+  const size_t Nc = e->Nc, W = (size_t)e->W, np = (size_t)(e->Nt - 1) * W;
+  std::vector<int64_t> nh(Nc);
+  int rc = ptm_get_array(e, PTM_ARR_NHIST, nh.data());   // (settles a pending ladder launch and the uncounted adds first)
+  if (rc) return rc;
+  int64_t nh_max = 0;
+  for (size_t c = 0; c < Nc; ++c) nh_max = std::max(nh_max, nh[c]);
+  if (nh_max > 2000000000) return fail(PTM_ERR_UNSUPPORTED, "ptm_log_evidence: more than 2e9 steps");
+  // the newest saved row of the longest chain: below the capacity, no slot was ever written twice
+  const bool wrapped = 1 + (nh_max > 0 ? (nh_max - 1) / e->cfg.add_every_n : 0) >= (int64_t)e->hist.cap;
+  const size_t o_up = 0, o_dn = o_up + ess_align(np * 8), o_ev = o_dn + ess_align(np * 8), o_cnt = o_ev + ess_align(W * 8), o_flag = o_cnt + ess_align(Nc * 4),
+               total = o_flag + 256;
+  if (e->ess_ws_bytes < total) {
+    if (e->ess_ws) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ess_ws)); e->ess_ws = nullptr; e->ess_ws_bytes = 0; }
+    HIPCHK(hipMalloc(&e->ess_ws, total));
+    e->ess_ws_bytes = total;
+  }
+  unsigned char* b = (unsigned char*)e->ess_ws;
+  double *d_up = (double*)(b + o_up), *d_dn = (double*)(b + o_dn), *d_ev = (double*)(b + o_ev);
+  int *d_cnt = (int*)(b + o_cnt), *d_flag = (int*)(b + o_flag);
+  EvidSrc src;
+  src.ll = e->hist.ll; src.meta = e->hist.meta; src.nhist = e->nhist; src.beta = e->beta; src.beta_w = e->beta_w;
+  src.HC = e->hist.HC; src.cap = e->hist.cap; src.W = e->W; src.Nt = e->Nt; src.add_every = e->cfg.add_every_n; src.ilen = ilen;
+  HIPCHK(hipMemsetAsync(d_flag, 0, 4, e->stream));
+  const dim3 grid((unsigned)((Nc + EVID_THREADS - 1) / EVID_THREADS));
+  if (wrapped) hipLaunchKernelGGL(evidence_ratio_kernel<true>, grid, dim3(EVID_THREADS), 0, e->stream, src, d_up, d_dn, d_cnt, d_flag);
+  else hipLaunchKernelGGL(evidence_ratio_kernel<false>, grid, dim3(EVID_THREADS), 0, e->stream, src, d_up, d_dn, d_cnt, d_flag);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(evidence_total_kernel, dim3((unsigned)((W + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, e->stream, src, d_up, d_dn, d_ev);
+  HIPCHK(hipGetLastError());
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (flag) return fail(PTM_ERR_INVALID, "ptm_log_evidence: history_capacity must hold the evidence window (%d rows hold less than the last %d steps of every chain)", e->hist.cap, ilen);
+  HIPCHK(hipMemcpyAsync(log_evidence, d_ev, W * 8, hipMemcpyDeviceToHost, e->stream));
+  if (up) HIPCHK(hipMemcpyAsync(up, d_up, np * 8, hipMemcpyDeviceToHost, e->stream));
+  if (down) HIPCHK(hipMemcpyAsync(down, d_dn, np * 8, hipMemcpyDeviceToHost, e->stream));
+  if (count) HIPCHK(hipMemcpyAsync(count, d_cnt, Nc * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return PTM_OK;
 }
 
 // ---- verification hooks ------------------------------------------------------------------------------------------------

@@ -33,6 +33,7 @@ EXPORTS = [
     "ptm_set_target_device", "ptm_target_device_rows", "ptm_get_best_evaluated",
     "ptm_set_proposal_adaptive", "ptm_get_proposal_adapt_state", "ptm_set_proposal_adapt_state",
     "ptm_ess_windowed", "ptm_ess_report", "ptm_ess_series_windowed", "ptm_ess_series_report", "ptm_ess_last_on_device",
+    "ptm_log_evidence",
 ]
 
 
@@ -183,6 +184,8 @@ def load():
         L.ptm_ess_series_windowed.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _i32p]
         L.ptm_ess_series_report.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i32p]
         L.ptm_ess_last_on_device.argtypes = [C.c_void_p]
+    if hasattr(L, "ptm_log_evidence"):
+        L.ptm_log_evidence.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _i32p]
     _lib = L
     return L
 
@@ -738,6 +741,16 @@ class Engine:
     def ess_last_on_device(self):
         """the last ess_windowed / effective_samples call ran the device kernels (ptm_ess_last_on_device)"""
         return bool(self.L.ptm_ess_last_on_device(self.h))
+
+    def log_evidence(self, ilen, out=None):
+        """log-evidence of every walker's ladder by thermodynamic integration over the last `ilen` steps of each chain's saved llikes,
+        on the device (ptm_log_evidence): (log_evidence[W], up[Nt-1][W], down[Nt-1][W], count[Nt][W]).  out: arrays to fill instead
+        (they keep their contents when the call fails)."""
+        if out is None:
+            out = (np.empty(self.W), np.empty((self.Nt - 1, self.W)), np.empty((self.Nt - 1, self.W)), np.empty((self.Nt, self.W), dtype=np.int32))
+        ev, up, down, count = out
+        _chk(self.L.ptm_log_evidence(self.h, int(ilen), _d(ev), _d(up), _d(down), count.ctypes.data_as(_i32p)))
+        return ev, up, down, count
 
     @property
     def exchange_row_capacity(self):

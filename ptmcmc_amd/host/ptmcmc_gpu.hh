@@ -1648,6 +1648,159 @@ class ess_estimator {
   }
 };
 
+// ---- log-evidence by thermodynamic integration over the ladder (chain.cc:1577-1676, 1984-2012) ----------------------------------
+// evidence_estimator: parallel_tempering_chains::log_evidence_ratio and the total of the statistics block, on plain arrays.
+//   * the window of chain b is MH_chain::get_state_idx (chain.cc:1041-1049) of Nhist - ilen and of Nhist -- an index outside
+//     [0, Nhist) becomes Nhist - 1 --: saved rows [1 + (Nhist - ilen) / add_every_N, 1 + (Nhist - 1) / add_every_N) in the ring's
+//     numbering (row 0 the start state).  So the newest saved row is left out and a chain with Nhist < ilen has no row: 0 / 0.
+//   * ratio(a, b) = sum of llike_b[row] * (beta_a - beta_b) in row order / count (chain.cc:1998-2007): multiply, then add;
+//   * up[i] = ratio(i, i+1), down[i] = -ratio(i+1, i), evidence += (up[i] + down[i]) / 2.0 in that order, then the term of the last
+//     pair / (beta[Nt-2] / beta[Nt-1] - 1) for what lies below the hottest rung (chain.cc:1586-1597).
+// The engine's kernels run the same operations in the same order on the device's own ring (ptm_log_evidence): same bits.
+class evidence_estimator {
+ public:
+  // llike of saved row `row` (the ring's numbering) of rung `rung`; false: the row is not there any more
+  typedef std::function<bool(int rung, long long row, double& llike)> reader;
+  struct result {
+    double evidence;
+    std::vector<double> up, down;   // [Nt - 1]
+    std::vector<int> count;         // [Nt] rows of each rung's window
+    bool complete;                  // false: a row of a window was missing (nothing else is to be believed then)
+  };
+  static long long state_idx(long long i, long long Nhist, int add_every_N) {   // Ninit = 1, Nzero = 0
+    if (i < 0 || i >= Nhist) i = Nhist - 1;
+    return 1 + i / add_every_N;
+  }
+  static void window(long long Nhist, int ilen, int add_every_N, long long& first, long long& last) {
+    first = state_idx(Nhist - ilen, Nhist, add_every_N);
+    last = state_idx(Nhist, Nhist, add_every_N);
+  }
+  // one ladder: Nhist[Nt] add_state calls and beta[Nt] current inverse temperatures of its chains
+  static result estimate(int Nt, int add_every_N, int ilen, const long long* Nhist, const double* beta, const reader& read) {
+    result r;
+    r.up.assign(Nt > 1 ? Nt - 1 : 0, 0.0); r.down = r.up; r.count.assign(Nt, 0); r.complete = true; r.evidence = 0;
+    auto ratio = [&](int ia, int ib) {
+      long long first, last;
+      window(Nhist[ib], ilen, add_every_N, first, last);
+      const double amb = beta[ia] - beta[ib];
+      double sum = 0, count = 0;
+      for (long long row = first; row < last; row++) {
+        double ll = 0;
+        if (!read(ib, row, ll)) r.complete = false;
+        volatile double x = ll * amb;   // (the product rounded before the sum, whatever the compiler's contraction rule)
+        sum += x;
+        count++;
+      }
+      r.count[ib] = (int)count;
+      return sum / count;
+    };
+    for (int i = 0; i < Nt - 1; i++) {
+      r.up[i] = ratio(i, i + 1);
+      r.down[i] = -ratio(i + 1, i);
+      r.evidence += (r.up[i] + r.down[i]) / 2.0;
+    }
+    if (Nt > 1) r.evidence += (r.up[Nt - 2] + r.down[Nt - 2]) / 2.0 / (beta[Nt - 2] / beta[Nt - 1] - 1);
+    return r;
+  }
+};
+
+// evidence_records: what the statistics block keeps of the totals (chain.cc:1603-1675) -- the pyramid total_evidence_records (level 0
+// every total from the second epoch on; level i the average of the last two of level i-1 whenever evidence_count is a multiple of
+// 2^i), the "recent ev analysis" over the newest 2 (Ndim - j) + 1 entries of each level but the top one, and the smallest standard
+// error seen (1e100 until there is one: six epochs) -- and the lines it prints, as written there.
+class evidence_records {
+  std::vector<std::vector<double> > records;
+  int evidence_count, records_dim;
+  double best_stderr;
+
+ public:
+  evidence_records() : evidence_count(0), records_dim(0), best_stderr(1e100) {}
+  double best() const { return best_stderr; }
+  int epochs() const { return evidence_count; }
+  const std::vector<std::vector<double> >& levels() const { return records; }
+  // one more total; returns the lines of chain.cc:1600-1675 (default stream formatting)
+  std::string push(double evidence, bool verbose_evid = true) {
+    std::ostringstream os;
+    os << "Total log-evidence: " << evidence << "\n";
+    evidence_count++;
+    int Ndim = 0;
+    while ((2 << Ndim) <= evidence_count) Ndim++;   // (int)log2(evidence_count)
+    if (Ndim > records_dim) { records.push_back(std::vector<double>()); records_dim++; }
+    if (records_dim > 0) {   // (saved from the second epoch of every scale on)
+      records[0].push_back(evidence);
+      os << "total_evidence_records[0][" << evidence_count - 2 << "]=" << evidence << "\n";
+    }
+    for (int i = 1; i < records_dim; i++)
+      if (evidence_count % (1 << i) == 0) {
+        os << "i=" << i << " ec=" << evidence_count << " 1<<(i)=" << (1 << i) << " mod=" << (evidence_count % (1 << i)) << "\n";
+        const int iend = (int)records[i - 1].size() - 1;
+        records[i].push_back((records[i - 1][iend - 1] + records[i - 1][iend]) / 2.0);
+      }
+    if (Ndim > 0) {
+      os << "total_log_evs:\n";
+      const int ndisplaymax = verbose_evid ? 20 : -1, ntot = (int)records[0].size();
+      const int ndisplay = ntot > ndisplaymax ? ndisplaymax : ntot;
+      for (int i = ntot - ndisplay; i < ntot; i++) {
+        for (int j = 0; j < (int)records.size(); j++) {
+          const int ind = (ntot + 1) / (1 << j) + (i - ntot) - 1;
+          if (ind >= 0) os << records[j][ind] << "\t";
+          else os << "      ---      " << "\t";
+        }
+        os << "\n";
+      }
+    }
+    os << "recent ev analysis:\n";
+    Ndim = (int)records.size();
+    for (int j = 0; j < Ndim - 1; j++) {
+      const int Nvar = 2 * (Ndim - j) + 1, N = (int)records[j].size();
+      if (N < Nvar) continue;
+      double sum1 = 0, sum2 = 0;
+      for (int i = N - Nvar; i < N; i++) {
+        const double ev = records[j][i];
+        volatile double sq = ev * ev;
+        sum1 += ev;
+        sum2 += sq;
+      }
+      const double mean = sum1 / Nvar;
+      volatile double sm = sum1 * mean;
+      const double variance = (sum2 - sm) / (Nvar - 1);
+      const double stderr_ = std::sqrt(variance / Nvar);
+      os << j << ": N=" << Nvar << " <ev>=" << sum1 / Nvar << " sigma=" << std::sqrt(variance) << " StdErr=" << stderr_ << "\n";
+      if (stderr_ < best_stderr) best_stderr = stderr_;
+    }
+    return os.str();
+  }
+  // checkpoint: the records, evidence_count, the best stderr
+  void write(std::ostream& os) const {
+    const int32_t head[3] = {evidence_count, records_dim, (int32_t)records.size()};
+    os.write((const char*)head, sizeof head);
+    os.write((const char*)&best_stderr, 8);
+    for (size_t j = 0; j < records.size(); j++) {
+      const uint64_t n = records[j].size();
+      os.write((const char*)&n, 8);
+      os.write((const char*)records[j].data(), (std::streamsize)(n * 8));
+    }
+  }
+  bool read(std::istream& is) {
+    int32_t head[3];
+    double best = 0;
+    is.read((char*)head, sizeof head);
+    is.read((char*)&best, 8);
+    if (!is || head[0] < 0 || head[2] < 0 || head[2] > 31 || head[1] != head[2]) return false;
+    std::vector<std::vector<double> > rec((size_t)head[2]);
+    for (size_t j = 0; j < rec.size(); j++) {
+      uint64_t n = 0;
+      is.read((char*)&n, 8);
+      if (!is || n > (uint64_t)head[0]) return false;
+      rec[j].resize((size_t)n);
+      is.read((char*)rec[j].data(), (std::streamsize)(n * 8));
+      if (!is) return false;
+    }
+    records.swap(rec); evidence_count = head[0]; records_dim = head[1]; best_stderr = best;
+    return true;
+  }
+};
+
 // A small persistent worker pool for the likelihood batches: starting and joining threads for every batch costs more than
 // a cheap plug-in's whole batch.  run(n, chunk, f) calls f(k0, k1) over [0, n) in chunks, on the workers and the caller.
 class eval_pool {
@@ -2206,6 +2359,80 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     refresh();
     return betas[(size_t)w * Ntemps + i];
   }
+  // ---- log-evidence by thermodynamic integration (chain.cc:1358-1360, 1577-1676): every istatsbin steps the total of every
+  // replica's ladder over the last istatsbin add_state calls of its chains, from the device's own ring (ptm_log_evidence) or --
+  // with host-side proposals, whose history is the host mirror, and with PTM_HOST_EVIDENCE=1 -- evidence_estimator here
+  bool do_evid = false, verbose_evid = true;
+  int istatsbin = 10000, icount = 0;
+  std::vector<evidence_records> ev_records;            // [W]
+  std::vector<double> ev_last, ev_up, ev_down;         // [W], [(Ntemps-1)*W] of the last epoch
+  int evidence_rows() const { return istatsbin / add_every_N + 2; }
+  static bool evidence_on_host() {
+    static const bool on = [] { const char* v = getenv("PTM_HOST_EVIDENCE"); return v && *v && *v != '0'; }();   // (A/B: keep the host path)
+    return on;
+  }
+  void evidence_epoch() {
+    const size_t Wn = (size_t)W, np = (size_t)(Ntemps - 1) * Wn;
+    ev_last.assign(Wn, 0.0); ev_up.assign(np, 0.0); ev_down.assign(np, 0.0);
+    if (!host_mode && !evidence_on_host()) {
+      ptm_check(ptm_log_evidence(eng, istatsbin, ev_last.data(), ev_up.data(), ev_down.data(), nullptr), "parallel_tempering_chains: log-evidence");
+    } else {
+      const size_t HC = (size_t)Ntemps * Wn, cap = (size_t)ring_rows;
+      std::vector<int64_t> nh(HC);
+      std::vector<double> rl;
+      std::vector<int32_t> rm;
+      ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "parallel_tempering_chains: log-evidence");
+      if (!host_mode) {
+        rl.resize(cap * HC); rm.resize(cap * HC * 4);
+        ptm_check(ptm_get_history_chains(eng, 0, (int)HC, nullptr, rl.data(), nullptr, rm.data(), nullptr), "parallel_tempering_chains: log-evidence");
+      }
+      for (size_t w = 0; w < Wn; w++) {
+        std::vector<long long> nhw((size_t)Ntemps);
+        std::vector<double> bw((size_t)Ntemps);
+        for (int i = 0; i < Ntemps; i++) { nhw[(size_t)i] = nh[(size_t)i * Wn + w]; bw[(size_t)i] = cur_beta(i, (int)w); }
+        evidence_estimator::reader read;
+        if (host_mode) read = [&, w](int rung, long long row, double& ll) {   // (the mirror counts its initial draws in front: chain.cc:1044)
+          const mirror_t& m = mirror[(size_t)rung * Wn + w];
+          const long long at = row - 1 + Ninit_rows;
+          if (at < 0 || (size_t)at >= m.rows()) return false;
+          ll = m.llike[(size_t)at];
+          return true;
+        };
+        else read = [&, w](int rung, long long row, double& ll) {
+          const size_t o = (size_t)(row % (long long)cap) * HC + (size_t)rung * Wn + w;
+          if (rm[4 * o + 3] != (int32_t)row) return false;
+          ll = rl[o];
+          return true;
+        };
+        const evidence_estimator::result r = evidence_estimator::estimate(Ntemps, add_every_N, istatsbin, nhw.data(), bw.data(), read);
+        if (!r.complete) { std::cout << "parallel_tempering_chains: the saved history no longer holds the evidence window (" << istatsbin << " steps)" << std::endl; exit(1); }
+        ev_last[w] = r.evidence;
+        for (int i = 0; i < Ntemps - 1; i++) { ev_up[(size_t)i * Wn + w] = r.up[(size_t)i]; ev_down[(size_t)i * Wn + w] = r.down[(size_t)i]; }
+      }
+    }
+    // replica 0's lines are the reference's; with a population one more gives its spread
+    for (size_t w = 0; w < Wn; w++) {
+      const std::string lines = ev_records[w].push(ev_last[w], verbose_evid);
+      if (w == 0) std::cout << lines << std::flush;
+    }
+    if (W > 1) {
+      std::vector<double> e(ev_last);
+      std::sort(e.begin(), e.end());
+      std::cout << "Over " << e.size() << " replicas: log-evidence min=" << e.front() << " median=" << e[e.size() / 2] << " max=" << e.back() << std::endl;
+    }
+  }
+  // the engine calls of n steps, cut where a statistics bin ends
+  template <class F>
+  void step_in_bins(int n, F advance) {
+    while (n > 0) {
+      const int k = do_evid ? std::min(n, std::max(1, istatsbin - icount)) : n;
+      advance(k);
+      n -= k;
+      if (!do_evid) continue;
+      icount += k;
+      if (icount >= istatsbin) { evidence_epoch(); icount = 0; }   // chain.cc:1577, 1684
+    }
+  }
   void refresh() {
     if (fresh) return;
     ptm_check(ptm_batch_begin(eng), "parallel_tempering_chains");
@@ -2225,6 +2452,8 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
                             bool verbose_evid = true, double dpriormin = -30)
       : Ntemps(Ntemps), add_every_N(add_every_N), Tmax(Tmax), swap_rate(swap_rate), dpriormin(dpriormin), eng(nullptr),
         sp(nullptr), dim(0), nstep(0), hist_rows(0), W(1), temps(Ntemps, 1.0), fresh(false) {
+    this->do_evid = do_evid && Ntemps > 1; this->verbose_evid = verbose_evid;
+    istatsbin = 10000 * (add_every_N / 10 + 1);   // chain.cc:1358-1360
     // geometric ladder, chain.cc:1181-1183
     double tratio = Ntemps > 1 ? std::exp(std::log(Tmax) / (Ntemps - 1)) : 1.0;
     for (int i = 1; i < Ntemps; i++) temps[i] = temps[i - 1] * tratio;
@@ -2247,6 +2476,20 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   // streams of walker w; every accessor below takes the replica as an optional last argument (default 0).  Multiples
   // of 64 fill whole wavefronts and take the fast kernels.
   void set_replicas(int n) { W = n < 1 ? 1 : n; }
+  // ---- the evidence (do_evid): the reference marks its bin of 10000 (add_every_N / 10 + 1) steps "make this user adjustable?";
+  // set_stats_bin does (before initialize(): the history ring is sized by it).  bestEvidenceErr: the smallest standard error
+  // of the recent totals so far (replica 0; 1e100 until six bins have passed), the sampler's pt_stop_evid_err criterion.
+  void set_stats_bin(int steps) {
+    if (steps < 1) steps = 1;
+    if (eng && do_evid && steps > istatsbin) { std::cout << "parallel_tempering_chains::set_stats_bin: call before initialize() (the history ring holds " << istatsbin << " steps)" << std::endl; exit(1); }
+    istatsbin = steps;
+  }
+  int stats_bin() const { return istatsbin; }
+  bool evidence_on() const { return do_evid; }
+  double bestEvidenceErr(int replica = 0) const { return do_evid && (size_t)replica < ev_records.size() ? ev_records[(size_t)replica].best() : 1e100; }
+  int evidence_epochs() const { return ev_records.empty() ? 0 : ev_records[0].epochs(); }
+  double lastEvidence(int replica = 0) const { return (size_t)replica < ev_last.size() ? ev_last[(size_t)replica] : 0.0 / 0.0; }
+  const evidence_records& evidenceRecords(int replica = 0) const { return ev_records[(size_t)replica]; }
   // Several GPUs: one process per GPU, each with its own share of the replicas -- replicas `begin .. begin + n - 1` of the
   // population (call before initialize(); `device` < 0: the process's current device, e.g. through HIP_VISIBLE_DEVICES).
   // Replicas are independent ladders, so there is nothing to exchange between the processes, and a replica's chains are the
@@ -2362,6 +2605,13 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       for (auto pp : props) pp->checkpoint(dir);
     }
     if (!os) { std::cout << "parallel_tempering_chains::checkpoint: write failed" << std::endl; exit(1); }
+    if (do_evid) {   // the evidence's own file: PTchain.cp holds the same bytes with and without it
+      std::ofstream oe((dir + "PTevidence.cp").c_str(), std::ios::binary);
+      const int32_t head[4] = {0x45564431, W, istatsbin, icount};
+      oe.write((const char*)head, sizeof head);
+      for (size_t w = 0; w < ev_records.size(); w++) ev_records[w].write(oe);
+      if (!oe) { std::cout << "parallel_tempering_chains::checkpoint: cannot write " << dir << "PTevidence.cp" << std::endl; exit(1); }
+    }
   }
   // into a ladder set up exactly like the one that was saved (same sizes, seed, likelihood, prior, proposal, evolve_temps)
   void restart(const std::string& path) {
@@ -2425,6 +2675,17 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     }
     nstep = h.nstep;
     fresh = hist_fresh = map_fresh = false;
+    if (do_evid) {
+      std::ifstream ie((dir + "PTevidence.cp").c_str(), std::ios::binary);
+      int32_t head[4] = {0, 0, 0, 0};
+      ie.read((char*)head, sizeof head);
+      bool good = (bool)ie && head[0] == 0x45564431 && head[1] == W && head[2] == istatsbin && head[3] >= 0 && head[3] < istatsbin;
+      std::vector<evidence_records> rec((size_t)W);
+      for (size_t w = 0; good && w < rec.size(); w++) good = rec[w].read(ie);
+      if (!good) { std::cout << "parallel_tempering_chains::restart: " << dir << "PTevidence.cp is missing or does not match this ladder (replicas, statistics bin)" << std::endl; exit(1); }
+      ev_records.swap(rec);
+      icount = head[3];
+    }
   }
   // chain.cc:1281-1365: n prior draws per rung (the device draws them: any prior type but the improper flat one); the last one
   // is the chain's start, the others seed the history that history-reading proposals draw from (ptmcmc.cc:86: de_ni * Npar)
@@ -2466,6 +2727,21 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     Ninit_rows = host ? Ninit_asked : 1;
     // differential evolution on the device: every rung's history stays there, in a ring as long as the run (keep_history), with the
     // extra draws of initialize(n) beside it; the rows keep the ring's numbering (row 0 = the start state)
+    if (do_evid) {   // every rung's saved llikes of a whole statistics bin (with host-side proposals the host mirror has them)
+      if (!host) {
+        hist_rows = std::max(hist_rows, evidence_rows());
+        hist_rungs = 0;
+        const int dp = dim > 16 ? 32 * ((dim + 31) / 32) : (dim > 8 ? 16 : (dim > 4 ? 8 : 4));
+        const double bytes = (double)hist_rows * Ntemps * W * (8.0 * dp + 40.0);
+        if (bytes >= 16e9) {
+          std::cout << "parallel_tempering_chains: the evidence needs " << hist_rows << " saved rows of all " << Ntemps << " rungs x " << W << " replicas on the device ("
+                    << bytes / 1e9 << " GB, above the 16 GB limit): fewer replicas, a larger save_every or a shorter statistics bin" << std::endl;
+          exit(1);
+        }
+      }
+      ev_records.assign((size_t)W, evidence_records());
+      icount = 0;
+    }
     de_built = !host && want_de && hist_rows > 0;
     const int draws = (host || de_built) ? Ninit_asked : 1;
     // host-side proposals: every rung's saved rows pass through a SHORT device ring into the host mirror after each step
@@ -2703,7 +2979,8 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   void set_proposal_factors(int kind, const std::vector<double>& factors, const std::vector<double>& oneDfracs = std::vector<double>()) {
     ptm_check(ptm_set_proposals(eng, kind, factors.data(), oneDfracs.empty() ? nullptr : oneDfracs.data()), "set_proposals");
   }
-  void step() override {
+  void step() override { step_in_bins(1, [this](int) { step_one(); }); }
+  void step_one() {
     ptm_check(ptm_step(eng, 1), "parallel_tempering_chains::step");
     nstep++;
     fresh = hist_fresh = map_fresh = false;
@@ -2722,16 +2999,13 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   void step_n(int n) {
     if (n <= 0) return;
     if (host_mode || tracking) { for (int k = 0; k < n; k++) step(); return; }
-    ptm_check(ptm_step(eng, n), "parallel_tempering_chains::step_n");
-    nstep += n;
-    fresh = hist_fresh = map_fresh = false;
+    step_in_bins(n, [this](int k) {
+      ptm_check(ptm_step(eng, k), "parallel_tempering_chains::step_n");
+      nstep += k;
+      fresh = hist_fresh = map_fresh = false;
+    });
   }
-  void step(int n) {
-    if (tracking || host_mode) { for (int k = 0; k < n; k++) step(); return; }
-    ptm_check(ptm_step(eng, n), "parallel_tempering_chains::step");
-    nstep += n;
-    fresh = hist_fresh = map_fresh = false;
-  }
+  void step(int n) { step_n(n); }
   double getMAPlpost() override { return views[0].getMAPlpost(); }   // the cold rung's (chain.cc:1570-1571)
   state getMAPstate() override { return views[0].getMAPstate(); }
   state getState(int = -1, bool = false) override { return views[0].getState(); }
@@ -2927,7 +3201,10 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     for (int i = 0; i < Ntemps; i++) {   // replica 0
       const size_t c = (size_t)i * W;
       s << "T=" << 1 / cur_beta(i, 0) << ": lpost=" << lpost[c] << " llike=" << llike[c] << " acc=" << (double)na[c] / nt[c] << "\n";
+      if (do_evid && verbose_evid && i < Ntemps - 1 && !ev_up.empty())   // chain.cc:2065
+        s << " log eratio:(" << ev_down[(size_t)i * W] << "," << ev_up[(size_t)i * W] << ")" << std::endl;
     }
+    if (do_evid) s << "Best evidence stderr=" << bestEvidenceErr() << std::endl;   // chain.cc:2092
     return s.str();
   }
   // MH_chain::dumpChain row format of the current state (chain.cc:1112-1135): i lpost llike acc type: params invtemp
@@ -2997,7 +3274,7 @@ class ptmcmc_sampler : public bayes_sampler {
   bool restarting;
   std::string restart_dir;
   int checkp_at_step;
-  double ess_stop, prop_adapt_rate, dpriormin;
+  double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0;
   int nreplicas, replica_begin = 0, device = -1;
 
   // every flag read into a typed value (a flag without a value reads as T())
@@ -3025,6 +3302,7 @@ class ptmcmc_sampler : public bayes_sampler {
     if (Nptc == 0) dump_n = 1;
     prop_adapt_rate = flag<double>("prop_adapt_rate");
     ess_stop = flag<double>("chain_ess_stop");
+    pt_stop_evid_err = flag<double>("pt_stop_evid_err");
     dpriormin = flag<double>("chain_dprior_min");
     nreplicas = optSet("replicas") ? flag<int>("replicas") : 1;
     replica_begin = optSet("replica_begin") ? flag<int>("replica_begin") : 0;
@@ -3079,7 +3357,7 @@ class ptmcmc_sampler : public bayes_sampler {
         {"pt_reboot_thermal", "0", "Temperature-dependent part of that deficit (not built here). [0]"},
         {"pt_reboot_blindly", "0", "Restart at random at this level even without a deficit (not built here). [0]"},
         {"pt_reboot_grad", no_value, "Make the grace period grow towards the cold rungs, with this mean (not built here)."},
-        {"pt_stop_evid_err", "0", "Stop once the evidence estimate is consistent to this error (not built here). [0: off]"},
+        {"pt_stop_evid_err", "0", "Integrate the log-evidence over the ladder every 10000*(save_every/10+1) steps and stop once the standard error of the recent totals is below this. [0: off]"},
         // the default proposal recipe
         {"prop", "", "No longer used."},
         {"gauss_draw_frac", "0.20", "Share of Gaussian steps in the default proposal mixture. [0.20]"},
@@ -3163,8 +3441,6 @@ class ptmcmc_sampler : public bayes_sampler {
     double v = 0; std::string sv;
     *optValue("pt_reboot_rate") >> v;
     if (v > 0) { std::cout << "ptmcmc_sampler: pt_reboot_rate > 0 (rebooting laggard chains) is not built in the GPU step engine." << std::endl; exit(1); }
-    *optValue("pt_stop_evid_err") >> v;
-    if (v > 0) { std::cout << "ptmcmc_sampler: pt_stop_evid_err > 0 (evidence integration) is not built in the GPU step engine." << std::endl; exit(1); }
     *optValue("chain_init_file") >> sv;
     if (!sv.empty()) { std::cout << "ptmcmc_sampler: chain_init_file is not built in the GPU step engine." << std::endl; exit(1); }
     if (Nptc < 2) { std::cout << "ptmcmc_sampler: this build drives parallel-tempering ladders: set --pt=N with N >= 2." << std::endl; exit(1); }
@@ -3329,7 +3605,8 @@ class ptmcmc_sampler : public bayes_sampler {
     if (!parallel_tempering) { std::cout << "ptmcmc_sampler::initialize: this build drives parallel-tempering ladders: set --pt=N with N >= 2." << std::endl; exit(1); }
     int Ninit = chain_Ninit;
     if (restarting || Nstep <= 0) Ninit = 1;
-    cc.reset(new parallel_tempering_chains(Nptc, Tmax, swap_rate, save_every, false, false, dpriormin));
+    const bool do_evid = pt_stop_evid_err > 0;   // ptmcmc.cc:399,509: do_evid = verbose_evid
+    cc.reset(new parallel_tempering_chains(Nptc, Tmax, swap_rate, save_every, do_evid, do_evid, dpriormin));
     cc_base = cc.get();
     have_cc = true;
     // the chain files are written from the device's history ring, every "nevery" steps: it must hold what one such
@@ -3405,6 +3682,10 @@ class ptmcmc_sampler : public bayes_sampler {
         std::cout << "   MaxPosterior=" << chain_llike->bestPost() << std::endl;
         for (int w = 0; w < nrep; w++)
           for (int ich = 0; ich < dn; ich++) cc->dumpChain(ich, *out[(size_t)w * dn + ich], istep - every + 1, skip, w);
+        if (cc->bestEvidenceErr() < pt_stop_evid_err) {   // ptmcmc.cc:608-612
+          stop = true;
+          std::cout << "ptmcmc_sampler::run: Stopping based on pt_stop_evid_err criterion." << std::endl;
+        }
         if (0 == istep % (every * 4)) {   // ptmcmc.cc:620-651
           std::cout << "Proposal report:\n" << cc->report_prop(1) << "\nacceptance report:\n" << cc->report_prop(0) << std::endl;
           if (ess_stop > 0) {   // ptmcmc.cc:628-649
