@@ -83,17 +83,18 @@ class Estimator:
                     cov[w, l] = s2 / nn - mu * mu
         return nwin, lags, mean, cov, count
 
-    def windowed(self, width, every, burn, detail=False):
-        """(ess[s], nwin[s]); detail=True adds the feature that set the minimum at the winning n"""
+    def feature_ess(self, width, every, burn):
+        """e[n - 1][s][f]: feature f's own ess over the newest n windows, n = 1 .. nwin (a feature is a lane of its own: its numbers do
+        not depend on which other features are looked at); None where windowed() returns (0, 0) at once"""
         ns, nf = self.nseries, self.nfeat
-        ess_out, nwin_out, feat_out = np.zeros(ns), np.zeros(ns, dtype=np.int32), np.full(ns, -1)
         t = self.table(width, every, burn)
         if t is None:
-            return (ess_out, nwin_out, feat_out) if detail else (ess_out, nwin_out)
+            return None
         width, every = max(int(width), 2), max(int(every), 1)
         nwin, lags, mean, cov, count = t
         nlag = len(lags)
         cnt = count.astype(np.float64)[..., None]
+        out = np.empty((nwin, ns, nf))
         with np.errstate(all="ignore"):
             for n in range(1, nwin + 1):
                 msum = np.zeros((ns, nf))
@@ -122,7 +123,19 @@ class Estimator:
                     length = np.where(going, length + term, length)
                     last_lag = np.where(going, float(lags[l]), last_lag)
                 e = float(n * width) / length
-                e = np.where(length < every, float(n * width) / 3.0 / float(every), e)
+                out[n - 1] = np.where(length < every, float(n * width) / 3.0 / float(every), e)
+        return out
+
+    def windowed(self, width, every, burn, detail=False):
+        """(ess[s], nwin[s]); detail=True adds the feature that set the minimum at the winning n"""
+        ns, nf = self.nseries, self.nfeat
+        ess_out, nwin_out, feat_out = np.zeros(ns), np.zeros(ns, dtype=np.int32), np.full(ns, -1)
+        e_of_n = self.feature_ess(width, every, burn)
+        if e_of_n is None:
+            return (ess_out, nwin_out, feat_out) if detail else (ess_out, nwin_out)
+        with np.errstate(all="ignore"):
+            for n in range(1, len(e_of_n) + 1):
+                e = e_of_n[n - 1]
                 worst, worst_f = np.full(ns, 1e100), np.full(ns, -1)
                 for f in range(nf):
                     less = e[:, f] < worst
