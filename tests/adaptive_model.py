@@ -150,15 +150,22 @@ class SteeredOracle:
             return rows >= 10 * self.D
         return ready
 
-    def step(self, n=1):
+    def sweep(self, n=1):
+        """plain MH sweeps: every chain moves, no exchange phase"""
+        self.step(n, exchange=False)
+
+    def step(self, n=1, exchange=True):
         L = O.lib()
         lad = self.lad
         Nt, W = self.Nt, self.W
         N = Nt * W
         nleaf = self.scales.shape[1]
         for _ in range(n):
-            L.ptmo_exchange_phase(lad.s, lad.rng)
-            touched = np.ctypeslib.as_array(lad.s.contents.touched, shape=(N,)).copy()
+            if exchange:
+                L.ptmo_exchange_phase(lad.s, lad.rng)
+                touched = np.ctypeslib.as_array(lad.s.contents.touched, shape=(N,)).copy()
+            else:
+                touched = np.zeros(N, dtype=np.uint8)
             nsize = lad.nsize
             step = lad.step
             for oc in range(N):

@@ -45,12 +45,13 @@ def problem_for(D, Nt, tmax):
 
 
 def make_pair(D, Nt, W, tmax, kind=E.PROP_LOWER, seed=0x5EED0001, swap_rate=0.1, one_d_frac=None, add_every_n=1,
-              bounds=None, prior=None, mean=None, min_prior=-30.0, init="prior", x0=None, history_cap=0):
+              bounds=None, prior=None, mean=None, min_prior=-30.0, init="prior", x0=None, history_cap=0, time_kernels=False):
     """An engine and its oracle twin on the same synthetic Gaussian problem and the same start states (history_cap > 0: both record
-    every rung's history -- every add_every_n-th add -- and MAP)."""
+    every rung's history -- every add_every_n-th add -- and MAP; time_kernels: the engine times its kernels, which keeps its PT steps
+    on the two-launch path)."""
     pr = problem_for(D, Nt, tmax)
     eng = E.Engine(D, Nt, W, seed=seed, swap_rate=swap_rate, add_every_n=add_every_n, min_prior=min_prior,
-                   history_rungs=Nt if history_cap else 0, history_capacity=history_cap, map_rungs=Nt if history_cap else 0)
+                   history_rungs=Nt if history_cap else 0, history_capacity=history_cap, map_rungs=Nt if history_cap else 0, time_kernels=time_kernels)
     odf = None if one_d_frac is None else np.full(Nt, one_d_frac)
     fac = pr.configure(eng, kind, odf)
     if bounds is not None:

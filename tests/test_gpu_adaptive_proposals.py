@@ -9,21 +9,10 @@ import oracle_lib as O
 import parity_util as PU
 from ptmcmc_amd import engine as E
 from ptmcmc_amd.problems import GaussianProblem
+from proposal_pairs import (SEED, adaptive_pair as _setup, assert_same_adaptive as _assert_same, assert_same_adaptive_history as _assert_history,
+                            doubling as _doubling, one_level as _one_level)
 
 pytestmark = pytest.mark.gpu
-
-SEED = 0x5EED0001
-
-
-def _doubling(n):
-    g = [2.0 ** (k + 1) for k in range(n)]
-    t = sum(g)
-    return [v / t for v in g]
-
-
-def _one_level(K, odf):
-    """K scaled Gaussians of doubling shares: (top shares, leaf scales, leaf oneDfracs)"""
-    return _doubling(K), [2.0 ** -(K - 1 - k) for k in range(K)], [odf] * K
 
 
 def _recipe(de_share=0.8, odf=0.5):
@@ -33,60 +22,6 @@ def _recipe(de_share=0.8, odf=0.5):
     scales = [-1.0, 1.0] + [2.0 ** -(5 - k) for k in range(6)]
     odfs = [0.0, 0.0] + [odf] * 6
     return top, inner, scales, odfs
-
-
-def _setup(D, Nt, W, kind, top, scales, odfs, rate, nested=-1, inner=None, rate_in=0.0, cap=0, de=None, ninit=0, evolve=0.0, swap_rate=0.1):
-    pr, eng, lad = PU.make_pair(D, Nt, W, 1e3, kind=kind, seed=SEED, swap_rate=swap_rate, history_cap=cap)
-    K, Ki = len(top), (len(inner) if inner else 0)
-    chains = [AM.ChainSet(top, rate, nested, inner, rate_in) for _ in range(Nt * W)]
-    w, th, bits, cnt = AM.states_of(chains)
-    sc, od = np.tile(scales, (Nt, 1)), np.tile(odfs, (Nt, 1))
-    eng.set_proposal_adaptive(K, sc, od, w, th, bits, cnt, nested=nested, K_inner=Ki, rate=rate, rate_inner=rate_in)
-    if de is not None:
-        init = None
-        if ninit:
-            rng = np.random.default_rng(D * 100 + Nt)
-            init = rng.uniform(-1.0, 1.0, size=(ninit, Nt * W, D)) * np.asarray(pr.halfwidths)[None, None, :] * 0.02
-        eng.set_proposal_de(de, 0.3, 4.0, 0.0, init_rows=init)
-        lad.set_de(de, 0.3, 4.0, 0.0, init_rows=None if init is None else np.stack([PU.to_oracle_order(init[k], Nt, W) for k in range(ninit)]))
-    if evolve:
-        eng.set_evolve_temps(evolve); lad.evolve_temps(evolve)
-    model = AM.SteeredOracle(lad, SEED, chains, sc, od, de_init_extra=ninit)
-    return pr, eng, lad, model
-
-
-def _assert_same(eng, lad, model, what):
-    Nt, W = eng.Nt, eng.W
-    xe, xo = eng.states(), PU.to_engine_order(lad.x, Nt, W)
-    assert np.array_equal(xe, xo), "%s: states differ at %s" % (what, np.argwhere(xe != xo)[:4].tolist())
-    for name in ("llike", "lprior", "ntries", "naccept", "nhist", "nsize"):
-        a, b = getattr(eng, name), PU.to_engine_order(getattr(lad, name), Nt, W)
-        assert np.array_equal(a, b), "%s: %s differ at %s" % (what, name, np.argwhere(a != b)[:4].tolist())
-    lt = model.last_type()
-    assert np.array_equal(eng.last_type, lt), "%s: last_type differ at %s" % (what, np.argwhere(eng.last_type != lt)[:4].tolist())
-    st = eng.proposal_adapt_state()
-    w, th, bits, cnt = model.state()
-    for name, got, want in (("weights", st["weights"], w), ("thresholds", st["thresholds"], th), ("repeat bits", st["repeat_bits"], bits),
-                            ("outcomes", st["outcomes"], cnt)):
-        assert np.array_equal(got, want), "%s: adaptive %s differ at %s" % (what, name, np.argwhere(got != want)[:4].tolist())
-
-
-def _assert_history(eng, lad, model, cap):
-    Nt, W = eng.Nt, eng.W
-    he, ho = eng.history(), lad.history()
-    nsize = eng.nsize
-    assert nsize.max() <= cap
-    for name in ("x", "llike", "lprior", "naccept", "ntries", "last_type", "invtemp"):
-        for s_ in range(int(nsize.max())):
-            have = nsize > s_
-            want = PU.to_engine_order(ho[name][:, s_], Nt, W)
-            if name == "last_type":
-                want = np.array([AM.nested_type(v, model.K, model.nested) for v in want])
-            got = he[name][s_ % cap][have]
-            assert np.array_equal(got, want[have]), (name, s_)
-    m = eng.map()
-    assert np.array_equal(m["lpost"], PU.to_engine_order(lad.map_lpost, Nt, W))
-    assert np.array_equal(m["x"], PU.to_engine_order(lad.map_x, Nt, W))
 
 
 def _run(eng, lad, model, steps, chunks=(1, 7)):

@@ -7,18 +7,9 @@ import pytest
 import oracle_lib as O
 import parity_util as PU
 from ptmcmc_amd import engine as E
+from proposal_pairs import de_pair as _pair, de_recipe as _recipe
 
 pytestmark = pytest.mark.gpu
-
-
-def _recipe(Nt, K, de_share, odf):
-    """the reference sampler's default set (ptmcmc.cc:60-143): differential evolution first, then K Gaussians of doubling shares"""
-    g = 2.0 ** np.arange(1, K + 1)
-    shares = np.concatenate([[de_share], (1 - de_share) * g / g.sum()])
-    cum = np.tile(np.cumsum(shares), (Nt, 1)); cum[:, -1] = 1.0
-    scales = np.tile(np.concatenate([[-1.0], 2.0 ** -np.arange(K)[::-1]]), (Nt, 1))
-    odfs = np.tile(np.concatenate([[0.0], np.full(K, odf)]), (Nt, 1))
-    return cum, scales, odfs
 
 
 DE_CASES = [
@@ -37,28 +28,6 @@ DE_CASES = [
     (100, 3, 2, E.PROP_DENSE, 2, 0.4, 10, 1, 24),    # 65..128 dimensions: two dimensions per lane
     (12, 24, 4, E.PROP_DIAG, 1, 0.2, 10, 6, 40),     # four chains per wave: snooker and parallel moves and Gaussians side by side in a wave
 ]
-
-
-def _pair(D, Nt, W, kind, N, snooker, ninit, K, cap, de_share=0.7, ignore=0.0, seed=0x5EED0001):
-    pr = PU.problem_for(D, Nt, 1e3)
-    eng = E.Engine(D, Nt, W, seed=seed, swap_rate=0.3, add_every_n=N, history_rungs=Nt, history_capacity=cap, map_rungs=Nt)
-    fac = pr.configure(eng, kind)
-    eng.init_from_prior()
-    x0 = eng.states()
-    lad = O.Ladder(PU.oracle_problem(pr), pr.beta, W=W, swap_rate=0.3, add_every_N=N)
-    lad.set_proposals([(PU.KIND_TO_ORACLE[kind], fac[r], 0.0) for r in range(Nt)])
-    lad.use_philox(seed)
-    lad.enable_history(cap)
-    lad.set_states(PU.to_oracle_order(x0, Nt, W))
-    cum, scales, odfs = _recipe(Nt, K, de_share, 0.5)
-    eng.set_proposal_mixture(cum, scales, odfs); lad.set_mixture(cum, scales, odfs)
-    rng = np.random.default_rng(D * 1000 + Nt)
-    init = None
-    if ninit:
-        init = rng.uniform(-1.0, 1.0, size=(ninit * D, Nt * W, D)) * np.asarray(pr.halfwidths)[None, None, :] * 0.02
-    eng.set_proposal_de(snooker, 0.3, 4.0, ignore, init_rows=init)
-    lad.set_de(snooker, 0.3, 4.0, ignore, init_rows=None if init is None else np.stack([PU.to_oracle_order(init[k], Nt, W) for k in range(init.shape[0])]))
-    return pr, eng, lad
 
 
 @pytest.mark.parametrize("D,Nt,W,kind,N,snooker,ninit,K,steps", DE_CASES)

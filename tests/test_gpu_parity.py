@@ -10,6 +10,7 @@ import golden_io
 import oracle_lib as O
 import parity_util as PU
 from ptmcmc_amd import engine as E
+from proposal_pairs import ladder_flavour_pair as _ladder_flavour_pair
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -1559,28 +1560,6 @@ LADDER_FLAVOURS = [
     (32, 8, 5, E.PROP_LOWER, 0.35, 0.4, 2, 5),       # one workgroup per ladder
     (9, 41, 2, E.PROP_LOWER, 0.45, 0.25, 1, 1),      # a set of one (draws nothing), many exchanges per step
 ]
-
-
-def _ladder_flavour_pair(D, Nt, W, kind, sr, odf, K, N, cap=64):
-    pr = PU.problem_for(D, Nt, 1e4)
-    eng = E.Engine(D, Nt, W, swap_rate=sr, add_every_n=max(N, 1), history_rungs=Nt if N else 0, history_capacity=cap if N else 0, map_rungs=Nt if N else 0)
-    fac = pr.configure(eng, kind, np.full(Nt, odf) if odf > 0 else None)
-    eng.init_from_prior()
-    x0 = eng.states()
-    lad = O.Ladder(PU.oracle_problem(pr), pr.beta, W=W, swap_rate=sr, add_every_N=max(N, 1))
-    lad.set_proposals([(PU.KIND_TO_ORACLE[kind], fac[r], odf) for r in range(Nt)])
-    lad.use_philox(0x5EED0001)
-    if N:
-        lad.enable_history(cap)
-    lad.set_states(PU.to_oracle_order(x0, Nt, W))
-    if K:
-        rng = np.random.default_rng(K)
-        shares = 2.0 ** np.arange(1, K + 1)
-        cum = np.tile(np.cumsum(shares) / shares.sum(), (Nt, 1)); cum[:, -1] = 1.0
-        scales = np.tile(3.0 ** -np.arange(K)[::-1] * 1.2, (Nt, 1)) * rng.uniform(0.8, 1.2, (Nt, 1))
-        odfs = np.tile(np.where(np.arange(K) % 2 == 0, odf, 0.0), (Nt, 1))
-        eng.set_proposal_mixture(cum, scales, odfs); lad.set_mixture(cum, scales, odfs)
-    return pr, eng, lad
 
 
 def _assert_same_history_and_map(eng, lad, cap=64):
