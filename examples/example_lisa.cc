@@ -125,7 +125,8 @@ int main(int argc, char* argv[]) {
     std::cout << ps->chains()->status();
     std::cout << "MAP: lpost = " << ps->chains()->getMAPlpost() << " at " << ps->chains()->getMAPstate().get_string() << std::endl;
     std::cout << "proposals drawn on the " << (ps->chains()->proposals_on_host() ? "host" : "device")
-              << (ps->chains()->draws_de_on_device() ? " (differential evolution from the device's own history)" : "") << std::endl;
+              << (ps->chains()->draws_de_on_device() ? " (differential evolution from the device's own history)" : "")
+              << (ps->chains()->draws_prior_on_device() ? " (prior draws on the device; PTM_HOST_PRIOR_DRAW=1: the host path)" : "") << std::endl;
     delete s;
   }
   // summary

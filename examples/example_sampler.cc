@@ -69,5 +69,6 @@ int main(int argc, char** argv) {
   mcmc.run(argv[1]);
   printf("%s", mcmc.chains()->status().c_str());
   printf("step kernel: %s%s\n", ptm_step_kernel_name(mcmc.chains()->engine()), mcmc.chains()->draws_de_on_device() ? "  (differential evolution drawn on the device)" : "");
+  if (mcmc.chains()->draws_prior_on_device()) printf("prior draws (--prior_draw_frac) made on the device\n");
   return 0;
 }

@@ -221,7 +221,8 @@ int ptm_get_proposal_adapt_state(ptm_engine* e, double* weights, double* thresho
 int ptm_set_proposal_adapt_state(ptm_engine* e, const double* weights, const double* thresholds, const int32_t* repeat_bits, const int32_t* outcomes);
 
 /* Host-side proposals -- the "host fallback step" for everything that is not a Gaussian the device can draw itself
- * (involutions, draws from the prior, temperature-dependent shares, user proposals with callbacks ...):
+ * (involutions, draws from a distribution other than the engine's prior, temperature-dependent shares of a set that adapts, user
+ * proposals with callbacks ...; draws from the prior itself are a device member: ptm_set_proposal_prior_draw):
  * every sweep fetches the current states, calls `propose` once for all moving chains, and runs the rest of
  * MH_chain::step on the device.  `result` (may be NULL) is told the outcomes after the accept kernel.  Replaces the
  * proposals of ptm_set_proposals; propose == NULL goes back to them.  Whole-shard sweeps only (ptm_sweep, ptm_step,
@@ -246,6 +247,26 @@ typedef struct ptm_de_params {
   double ignore_frac;     /* early fraction of a long history that is not drawn from (sampler: 0) */
 } ptm_de_params;
 int ptm_set_proposal_de(ptm_engine* e, const ptm_de_params* q, int n_init_extra, const double* init_rows);
+/* INDEPENDENT DRAWS FROM THE PRIOR as a member of the current proposal set, drawn ON THE DEVICE -- the reference's draw_from_dist over
+ * the prior (proposal_distribution.hh:119-132; the sampler's --prior_draw_frac, ptmcmc.cc:93-104).  `member` names the member of the
+ * set given to ptm_set_proposal_mixture, or of the TOP level of ptm_set_proposal_adaptive, that proposes this way; -1 switches it off.
+ * A new set (either call) forgets the member: name it again.  A chain whose pick lands on the member
+ *   draws   dimension d from block d of its own stream (global walker and rung) under tag 4 at the PT step, the block's words used as
+ *           ptm_init_from_prior uses them for the dimension's prior type; one draw, no redraw;
+ *   is      a state of its own (valid unless enforcing the boundaries fails), not a sum on the current one;
+ *   weighs  log_hastings = lprior(current) - lprior(proposed) into the Metropolis test (a NaN ratio rejects);
+ *   reports type code = member (no one-dimensional moves: the member's oneDfrac is not read; its scale is not read either).
+ * Differential evolution that is not ready hands its pick to the member behind it, which may be this one (the sampler's order).
+ * Temperature-dependent shares (--prior_draw_Tpow) of a set that does not adapt need nothing more: give every rung its own cumulative
+ * shares (mixture) or initial thresholds (adaptive set with top rate 0).
+ * Unlike differential evolution it needs no history: rung shards (mixture), walker splits, ptm_sweep_rungs and the propose / accept
+ * passes of user likelihoods all carry it (the accept pass makes member and ratio anew).  Steps of such an engine take the exchange
+ * kernel and the lanes or the general sweep kernel, as with an adaptive set: never the matrix-core, fused small-ladder or persistent
+ * kernels -- a 32-dimensional population of whole waves per rung runs where it runs with differential evolution.
+ * Every argument is checked before anything changes.  PTM_ERR_INVALID: member out of range, the nested set, or a member of negative
+ * scale (differential evolution); host-side proposals are set.  PTM_ERR_UNSUPPORTED: a flat prior dimension, or a prior callback
+ * (ptm_set_prior_callback) -- also reported by the next step if the prior changes to one of these afterwards. */
+int ptm_set_proposal_prior_draw(ptm_engine* e, int member);
 
 /* ---- state ------------------------------------------------------------------------------------------ */
 /* X[n_local_chains][D]; llike may be NULL (the device target evaluates it).  Resets counters the way

@@ -44,8 +44,9 @@ __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
 }
 
 // counter layout of the engine: c0 = block, c1 = stream, c2 = step[31:0], c3 = step[55:32] | tag << 24
-// (TAG_SET: the nested set's pick of an adaptive proposal set, ptm_set_proposal_adaptive: slot 0 of block 0)
-enum { TAG_MH = 0, TAG_PT = 1, TAG_INIT = 2, TAG_SET = 3 };
+// (TAG_SET: the nested set's pick of an adaptive proposal set, ptm_set_proposal_adaptive: slot 0 of block 0;
+//  TAG_PRIOR: a proposal drawn from the prior, ptm_set_proposal_prior_draw: block d is dimension d's)
+enum { TAG_MH = 0, TAG_PT = 1, TAG_INIT = 2, TAG_SET = 3, TAG_PRIOR = 4 };
 __device__ __forceinline__ philox_state draw_block_begin(uint64_t seed, int tag, uint32_t stream, uint64_t step, uint32_t block) {
   return {block, stream, (uint32_t)step, ((uint32_t)(step >> 32) & 0x00FFFFFFu) | ((uint32_t)tag << 24), (uint32_t)seed, (uint32_t)(seed >> 32)};
 }

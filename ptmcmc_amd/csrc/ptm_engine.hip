@@ -97,6 +97,10 @@ struct ptm_engine {
   ptm_adaptive_set ada = {0, -1, 0, 0, 0};
   double *ada_leaf = nullptr, *ada_dbl = nullptr;
   int* ada_int = nullptr;
+  // the member of the current set that draws from the prior (ptm_set_proposal_prior_draw), or -1; which (top) members of the current set
+  // have a negative scale on some rung -- differential evolution's mark
+  int prior_member = -1;
+  std::vector<char> set_neg;
   // evolving ladders (ptm_set_evolve_temps): per-ladder inverse temperatures [W][Nt] and their chain-indexed image [Nc]
   double evolve_rate = 0, evolve_cut = -1;
   double *beta_w = nullptr, *betaC = nullptr, *beta_add = nullptr;
@@ -966,6 +970,7 @@ extern "C" int ptm_set_proposal_mixture(ptm_engine* e, int K, const double* cum_
   if (K < 0 || K > 64) return fail(PTM_ERR_INVALID, "mixture size must be in 0..64");
   if (e->mix) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->mix)); e->mix = nullptr; }
   e->mix_K = 0;
+  e->prior_member = -1; e->set_neg.clear();           // (the prior member is named anew for every set: ptm_set_proposal_prior_draw)
   { const int rc = ada_off(e); if (rc) return rc; }   // (a fixed mixture, or none, replaces an adaptive set)
   if (K == 0) return PTM_OK;
   if (!cum_shares || !scales || !one_d_fracs) return fail(PTM_ERR_INVALID, "null argument");
@@ -983,6 +988,10 @@ extern "C" int ptm_set_proposal_mixture(ptm_engine* e, int K, const double* cum_
   int rc;
   if ((rc = dalloc(&e->mix, t.size())) || (rc = upload(e->mix, t.data(), t.size(), e->stream))) return rc;
   e->mix_K = K;
+  e->set_neg.assign((size_t)K, 0);
+  for (int r = 0; r < nloc; ++r)
+    for (int k = 0; k < K; ++k)
+      if (scales[(size_t)r * K + k] < 0) e->set_neg[k] = 1;
   if (oned) e->any_oned = 1;
   return PTM_OK;
 }
@@ -1083,7 +1092,37 @@ extern "C" int ptm_set_proposal_adaptive(ptm_engine* e, const ptm_adaptive_set* 
   e->ada_leaf = nleaf; e->ada_dbl = ndbl; e->ada_int = nint;
   e->ada = *a;
   e->ada_on = true;
+  e->prior_member = -1;   // (named anew for every set)
+  e->set_neg.assign((size_t)a->K, 0);
+  for (int r = 0; r < nloc; ++r)
+    for (int k = 0; k < a->K; ++k)
+      if (k != a->nested && scales[(size_t)r * L + k] < 0) e->set_neg[k] = 1;
   if (oned) e->any_oned = 1;
+  return PTM_OK;
+}
+
+// can the engine's prior be drawn from, dimension by dimension, on the device?  (what a prior member needs: ptm_set_proposal_prior_draw)
+static int prior_drawable(const ptm_engine* e) {
+  if (e->prior_cb) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior (ptm_set_prior_callback) cannot be drawn from on the device: draw on the host (ptm_set_proposal_callback)");
+  for (int d = 0; d < e->D; ++d)
+    if (e->h_ptype[d] == PTM_PRIOR_FLAT) return fail(PTM_ERR_UNSUPPORTED, "a flat prior (dimension %d) cannot be drawn from", d);
+  return PTM_OK;
+}
+
+// A member of the current set draws whole states from the prior (include/ptm_engine.h).  Every check first: a refused call changes nothing.
+extern "C" int ptm_set_proposal_prior_draw(ptm_engine* e, int member) {
+  if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_set_proposal_prior_draw");
+  if (member == -1) { e->prior_member = -1; return PTM_OK; }
+  const int K = e->ada_on ? e->ada.K : e->mix_K;
+  if (K == 0) return fail(PTM_ERR_INVALID, "no proposal set to name a member of (ptm_set_proposal_mixture, ptm_set_proposal_adaptive)");
+  if (member < 0 || member >= K) return fail(PTM_ERR_INVALID, "prior draw: member %d is not one of the set's %d (top) members", member, K);
+  if (e->ada_on && member == e->ada.nested) return fail(PTM_ERR_INVALID, "prior draw: member %d is the nested set", member);
+  if (e->set_neg[member]) return fail(PTM_ERR_INVALID, "prior draw: member %d has a negative scale, which marks differential evolution", member);
+  if (e->pcb) return fail(PTM_ERR_INVALID, "host-side proposals are set (ptm_set_proposal_callback): they replace every device proposal");
+  { const int rc = prior_drawable(e); if (rc) return rc; }
+  e->prior_member = member;
   return PTM_OK;
 }
 
@@ -1234,6 +1273,7 @@ static Dev make_dev(ptm_engine* e, bool labelled = false) {   // labelled: the c
   p.de_on = e->de_on ? 1 : 0; p.de_init_extra = e->de_init_extra; p.de_init = e->de_init; p.de_hast = e->de_hast; p.de_type = e->de_type;
   p.de_snooker = e->de.snooker; p.de_gamma_one = e->de.gamma_one_frac; p.de_gamma_div = e->de.reduce_gamma; p.de_ignore = e->de.ignore_frac;
   p.de_gamma_std = e->de_on ? 1.68 / std::sqrt((double)e->D) / e->de.reduce_gamma : 0.0;   // (the reference's own expression, proposal_distribution.cc:492)
+  p.prior_k = e->prior_member + 1;
   p.betaC = e->betaC; p.beta_add = e->beta_add; p.beta_w = e->beta_w;
   p.x = labelled ? e->xdev : xrows(e); p.ll = e->ll; p.lp = e->lp;
   p.ntries = e->ntries; p.naccept = e->naccept; p.last_type = e->last_type; p.nhist = e->nhist;
@@ -1284,7 +1324,8 @@ static SweepPlan sweep_plan(const ptm_engine* e, long long chains, bool touched)
   f.has_bounds = e->has_bounds; f.bounds_box = e->bounds_box; f.all_uniform = e->all_uniform; f.has_mean = e->has_mean; f.any_oned = e->any_oned;
   f.mix_K = e->mix_K;
   f.evolving = e->betaC != nullptr; f.tracked = e->hist.rungs || e->map.rungs;
-  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.de = e->de_on; f.ada = e->ada_on;
+  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.ada = e->ada_on;
+  f.de = e->de_on || e->prior_member >= 0;   // (a prior member routes as differential evolution does: only the lanes and general kernels draw it)
   f.mode = f.user_like ? 1 : 0;   // (the propose and accept passes run on one build)
   f.touched = touched;
   return plan_sweep(f, sweep_env());
@@ -1738,6 +1779,7 @@ static int ready(ptm_engine* e) {
   if (!e->have_ladder) return fail(PTM_ERR_INVALID, "no ladder set (ptm_set_ladder)");
   if (!e->have_prop) return fail(PTM_ERR_INVALID, "no proposals set (ptm_set_proposals)");
   if (!e->have_state) return fail(PTM_ERR_INVALID, "no states set (ptm_set_states / ptm_init_from_prior)");
+  if (e->prior_member >= 0) return prior_drawable(e);   // (the prior may have changed since the member was named)
   return PTM_OK;
 }
 
@@ -2044,7 +2086,7 @@ static bool fused_applies(const ptm_engine* e) {
   static const bool fused_ok = [] { const char* v = getenv("PTM_FUSED"); return !(v && *v == '0'); }();
   StepFacts f;
   f.DP = e->DP; f.Nt = e->Nt; f.W = e->W;
-  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.ada = e->ada_on; f.time_kernels = e->cfg.time_kernels != 0;
+  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.ada = e->ada_on || e->prior_member >= 0; f.time_kernels = e->cfg.time_kernels != 0;
   f.evolving = e->evolve_rate > 0; f.evolve_cut = e->evolve_cut >= 0;
   f.decide_lds = fused_decide_lds(e);
   return fused_applies(f, fused_ok);
@@ -2100,6 +2142,7 @@ static bool ladder_applies(ptm_engine* e, long long* grid_out = nullptr, size_t*
   // sampler's defaults: 14 us against 40 on two launches)
   if (user_like(e) || e->prior_cb || e->pcb) return false;
   if (e->ada_on) return false;   // (an adaptive proposal set: exchange kernel + the lanes or general kernel's ADA build)
+  if (e->prior_member >= 0) return false;   // (a member that draws from the prior: only the lanes and general kernels carry it)
   const int R = 256 / e->DP, NB = (e->Nt + R - 1) / R;
   const long long grid = (long long)e->W * NB;
   const bool diag = e->prop_kind == PTM_PROP_DIAG;

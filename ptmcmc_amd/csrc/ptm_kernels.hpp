@@ -130,6 +130,9 @@ struct Dev {
   double de_snooker, de_gamma_one, de_gamma_std, de_gamma_div, de_ignore;   // gamma_std = 1.68 / sqrt(D) / reduce_gamma, made by the host
   double* de_hast;            // [Nc] host-callback likelihood: the propose pass hands its log-Hastings ratio and type to the accept pass
   int* de_type;               // [Nc]
+  // a member of the set that draws the whole state from the prior (ptm_set_proposal_prior_draw; draw_from_dist of the reference,
+  // proposal_distribution.hh:119-132): 1 + the member's index in the mixture or in the adaptive set's top level, 0: none
+  int prior_k;
   // state (in place)
   double* x;                              // [Nc][DP] rows
   double *ll, *lp;                        // [Nc]
@@ -448,6 +451,36 @@ __device__ __forceinline__ bool de_ready(const Dev& p, unsigned int nh0) {   // 
 }
 
 // ------------------------------------------------------------------------------------------------
+// draw_from_dist::draw (proposal_distribution.hh:119-132) with the engine's own prior as the distribution: the proposed state is an
+// independent draw from the prior, its log-Hastings ratio lprior(current) - lprior(proposed).  Dimension d takes block d of the chain's
+// stream under TAG_PRIOR at the PT step, its words used as init_prior_kernel uses them; one draw, no redraw.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double prior_draw_dim(const Dev& p, uint32_t stream, uint64_t step, int d, const double* bmtab) {
+  const int t = as_c(p.ptype)[d];
+  const double lo = as_c(p.plo)[d], hi = as_c(p.phi)[d];
+  const u32x4 o = draw_block(p.seed, TAG_PRIOR, stream, step, (uint32_t)d);
+  if (t == P_UNIFORM) return u01(o.v0) * (hi - lo) + lo;
+  if (t == P_GAUSSIAN) { double z0, z1; boxmuller(o.v0, o.v1, bmtab, z0, z1); return z0 * hi + lo; }
+  if (t == P_POLAR) return draw_polar(u01(o.v0), lo, hi);
+  if (t == P_COPOLAR) return draw_copolar(u01(o.v0), lo, hi);
+  if (t == P_LOG) return draw_log(u01(o.v0), lo, hi);
+  return __builtin_nan("");
+}
+// the whole state on one lane (general kernel): a real loop over the dimensions whose result lands in xn by a compare per entry, so xn
+// keeps its registers and the five draws are in the code once
+template <int DP>
+__device__ __forceinline__ void prior_draw(const Dev& p, uint32_t stream, uint64_t step, const double* bmtab, double (&xn)[DP]) {
+#pragma unroll
+  for (int i = 0; i < DP; ++i) xn[i] = 0.0;
+#pragma unroll 1
+  for (int d = 0; d < p.D; ++d) {
+    const double v = prior_draw_dim(p, stream, step, d, bmtab);
+#pragma unroll
+    for (int i = 0; i < DP; ++i) xn[i] = i == d ? v : xn[i];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Adaptive proposal set (ptm_set_proposal_adaptive): proposal_distribution_set::draw / accept / reject / reset_bins
 // (proposal_distribution.cc:37-59, 99-166; Tpow = 0) with each chain's shares, thresholds, last outcomes and outcome counts in
 // device arrays [member][Nc].  Only the ADA builds of the lanes and general kernels carry this code.
@@ -659,6 +692,7 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   // -- gaussian_prop::draw: D normals, optional one-dimensional move, offset = factor * z
   int type = 0, axis = -1, kmix = 0;
   double mix_scale = 1.0;
+  bool pr_move = false;   // the picked member draws from the prior (ptm_set_proposal_prior_draw)
   AdaPick apk = {0, -1, 0};
   if (!SIMPLE) {
     double f = as_c(p.onedfrac)[rl];
@@ -680,9 +714,10 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
       mix_scale = mx[3 * kmix + 1];
       f = mx[3 * kmix + 2];
     }
+    if (p.prior_k && kmix == p.prior_k - 1) { pr_move = true; f = 0.0; }   // a draw from the prior: no one-dimensional moves
     if (p.any_oned && !tc && f > 0 && u01(o0.v1) < f) { axis = (int)(p.D * u01(o0.v2)); type = 1; }
   }
-  const bool de_move = !SIMPLE && p.de_on && mix_scale < 0;
+  const bool de_move = !SIMPLE && p.de_on && mix_scale < 0 && !pr_move;
   double de_hast = 0.0;
   double xn[DP];  // accumulates the offset, then becomes the proposed state
 #pragma unroll
@@ -723,7 +758,16 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   //    proposal.  The row is written back only if the move is accepted.
   const double ll = p.ll[c], lp = p.lp[c];
   double* __restrict__ row = p.x + (size_t)c * DP;
-  if (de_move) {
+  if (!SIMPLE && __builtin_amdgcn_ballot_w64(pr_move) != 0ull) {
+    // the member draws from the prior: the Gaussian offset of this lane is dropped (the wave's other lanes needed the loops).  The accept
+    // pass of a host-callback likelihood finds the state in xprop and makes the ratio anew from lprior_new
+    if (pr_move) {
+      if (mode != 2) prior_draw<DP>(p, stream, p.step, lds_all, xn);
+      type = kmix;               // member + 10 * 0 (proposal_distribution.cc:117)
+    }
+  }
+  if (pr_move) {
+  } else if (de_move) {
     // the member is differential evolution: the proposed state and its log-Hastings ratio from the chain's saved history (the accept
     // pass of a host-callback likelihood takes ratio and type from the propose pass)
     int dt;
@@ -740,7 +784,7 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
       for (int d = 0; d < DP; ++d) xn[d] = mix_scale * xn[d];   // the member is scale_k times the rung's factor
     }
   }
-  if (mode != 2 && !de_move) {
+  if (mode != 2 && !de_move && !pr_move) {
 #pragma unroll
     for (int d = 0; d < DP; ++d) xn[d] = row[row_pos<DP>(d)] + xn[d];  // state::add (states.cc:205-214)
   }
@@ -772,7 +816,7 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
 #pragma unroll
     for (int d = 0; d < DP; ++d) xn[d] = p.xprop[(size_t)c * DP + row_pos<DP>(d)];
   } else {
-    valid = p.origin_valid != 0;  // Q9: the sum is built on an enforced zero state
+    valid = pr_move || p.origin_valid != 0;  // Q9: the sum is built on an enforced zero state; a draw from the prior is a state of its own
     newlprior = enforce_and_lprior<DP>(p, xn, valid);
   }
   const bool want_like = valid && (newlprior > -1e200 || newlprior - oldlprior > p.min_prior);  // chain.cc:980 (Q1)
@@ -799,6 +843,11 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   if (de_move) {                       // chain.cc:989-994: prop.log_hastings_ratio(), NaN => reject
     if (de_hast != de_hast) accept = false;
     logH = de_hast + logH;
+  }
+  if (!SIMPLE && pr_move) {            // draw_from_dist: log_hastings = lprior(current) - lprior(proposed)
+    const double hast = lp - newlprior;
+    if (hast != hast) accept = false;
+    logH = hast + logH;
   }
   if (accept && logH < 0) accept = dlog_u01(o0.v0) < logH;  // chain.cc:998-1001 (NaN stays accepted)
 

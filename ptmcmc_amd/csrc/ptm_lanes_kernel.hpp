@@ -113,6 +113,7 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
   const u32x4 o0 = draw_block(p.seed, TAG_MH, stream, step, 0);
   int type = 0, axis = -1, kmix = 0;
   double mix_scale = 1.0;
+  bool pr_pick = false;   // the picked member draws from the prior (ptm_set_proposal_prior_draw)
   AdaPick apk = {0, -1, 0};
   if (GEN && !hp) {
     double f = p.onedfrac[rl];
@@ -133,6 +134,7 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
       mix_scale = mx[3 * kmix + 1];
       f = mx[3 * kmix + 2];
     }
+    if (p.prior_k && kmix == p.prior_k - 1) { pr_pick = true; f = 0.0; }   // a draw from the prior: no one-dimensional moves
     if (p.any_oned && !tc && f > 0 && u01(o0.v1) < f) { axis = (int)(p.D * u01(o0.v2)); type = 1; }
   }
   // normal d: slot d & 3 of Philox block 1 + d / 4 (two Box-Muller pairs per block)
@@ -210,7 +212,8 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
   // -- differential_evolution::draw (proposal_distribution.cc:476-592) for the chains whose member is the one with a negative scale:
   //    de_draw of the general kernel with dimension d on lane d.  Every number is made by the same operations: products rounded
   //    before their sums, the three inner products summed in index order (each lane of the chain walks the chain's terms in LDS).
-  const bool de_move = GEN && !hp && !tc && p.de_on && mix_scale < 0;
+  const bool pr_move = GEN && pr_pick && !tc;
+  const bool de_move = GEN && !hp && !tc && p.de_on && mix_scale < 0 && !pr_pick;
   double de_hast = 0.0;
   double xde[E];
 #pragma unroll
@@ -320,13 +323,24 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
       }
     }
   }
+  // -- draw_from_dist::draw (proposal_distribution.hh:119-132) for the chains whose member draws from the prior: prior_draw of the general
+  //    kernel with dimension d on lane d (in xde, which such a chain does not use otherwise).  A wave without such a chain skips it.
+  if constexpr (GEN) {
+    if (p.prior_k && mode != 2 && __builtin_amdgcn_ballot_w64(pr_move) != 0ull) {
+      if (pr_move) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) xde[e] = d + 64 * e < p.D ? prior_draw_dim(p, stream, step, d + 64 * e, lds_all) : 0.0;
+      }
+    }
+    if (pr_move) type = kmix;     // member + 10 * 0 (proposal_distribution.cc:117)
+  }
   double xn[E];
 #pragma unroll
   for (int e = 0; e < E; ++e)
-    xn[e] = (mode == 2 || hp) ? p.xprop[(size_t)c * DP + pos + 64 * e] : de_move ? xde[e] : row[pos + 64 * e] + off[e];   // state::add (states.cc:205-214)
+    xn[e] = (mode == 2 || hp) ? p.xprop[(size_t)c * DP + pos + 64 * e] : (de_move || pr_move) ? xde[e] : row[pos + 64 * e] + off[e];   // state::add (states.cc:205-214)
   // what the state is worth before enforcing: Q9 for a sum built by state::add (on an enforced zero state); a host-side
-  // proposal brings its own validity (state::invalid())
-  const bool valid0 = hp ? p.hvalid[c] != 0 : p.origin_valid != 0;
+  // proposal brings its own validity (state::invalid()); a draw from the prior is a state of its own
+  const bool valid0 = hp ? p.hvalid[c] != 0 : (pr_move || p.origin_valid != 0);
   const double beta = (GEN && p.betaC) ? p.betaC[c] : p.beta[rg];
   const double bl = beta * ll;
   const double cur_lpost = lp + bl;
@@ -433,6 +447,11 @@ __device__ __forceinline__ void lanes_body(const Dev& p, double* lds_all, const 
   if (GEN && de_move) {                // the same for differential evolution's own ratio
     if (de_hast != de_hast) accept = false;
     logH = de_hast + logH;
+  }
+  if (GEN && pr_move) {                // draw_from_dist: log_hastings = lprior(current) - lprior(proposed)
+    const double hast = lp - newlprior;
+    if (hast != hast) accept = false;
+    logH = hast + logH;
   }
   if (accept && logH < 0) accept = dlog_u01(o0.v0) < logH;  // chain.cc:998-1001 (NaN stays accepted)
   (void)tbuf;

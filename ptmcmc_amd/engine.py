@@ -24,7 +24,7 @@ PRIOR_NAMES = {"uni": 1, "uniform": 1, "gauss": 2, "gaussian": 2, "pol": 3, "pol
 EXPORTS = [
     "ptm_last_error", "ptm_abi_version", "ptm_device_count", "ptm_engine_create", "ptm_engine_destroy",
     "ptm_set_bounds", "ptm_set_prior", "ptm_set_target_gaussian", "ptm_set_target_callback", "ptm_set_prior_callback", "ptm_set_ladder", "ptm_set_evolve_temps", "ptm_get_invtemps", "ptm_set_invtemps",
-    "ptm_set_proposals", "ptm_set_proposal_rung", "ptm_set_proposal_mixture", "ptm_set_proposal_callback", "ptm_set_proposal_de", "ptm_set_states", "ptm_init_from_prior", "ptm_init_from_prior_k", "ptm_draw_prior_rows", "ptm_get_history_chains", "ptm_sweep", "ptm_step", "ptm_sync",
+    "ptm_set_proposals", "ptm_set_proposal_rung", "ptm_set_proposal_mixture", "ptm_set_proposal_callback", "ptm_set_proposal_de", "ptm_set_proposal_prior_draw", "ptm_set_states", "ptm_init_from_prior", "ptm_init_from_prior_k", "ptm_draw_prior_rows", "ptm_get_history_chains", "ptm_sweep", "ptm_step", "ptm_sync",
     "ptm_copy_llike", "ptm_copy_lprior", "ptm_llike_device_ptr", "ptm_exchange_decide", "ptm_exchange_decide_gathered", "ptm_set_shard_map", "ptm_exchange_redo_count", "ptm_exchange_redo", "ptm_exchange_finish_and_sweep", "ptm_exchange_install", "ptm_sweep_rungs", "ptm_exchange_buffer_doubles", "ptm_exchange_row_capacity", "ptm_shard_unique_id", "ptm_shard_init", "ptm_shard_step", "ptm_shard_finalize", "ptm_get_states", "ptm_batch_begin", "ptm_batch_end",
     "ptm_get_array", "ptm_get_swap_counts", "ptm_get_last_swaps", "ptm_max_swaps_per_step", "ptm_get_history", "ptm_get_history_invtemps", "ptm_set_history", "ptm_set_map", "ptm_get_map", "ptm_restore", "ptm_step_count",
     "ptm_timer_start", "ptm_timer_stop", "ptm_get_kernel_times", "ptm_calibrate", "ptm_get_counter_sums", "ptm_get_ladder_stats", "ptm_sweep_kernel_name", "ptm_step_kernel_name", "ptm_debug_eval",
@@ -161,6 +161,7 @@ def load():
     L.ptm_set_proposal_rung.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double]
     L.ptm_set_proposal_mixture.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     L.ptm_set_proposal_de.argtypes = [C.c_void_p, C.POINTER(PtmDeParams), C.c_int, _dp]
+    L.ptm_set_proposal_prior_draw.argtypes = [C.c_void_p, C.c_int]
     L.ptm_set_proposal_callback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptm_shard_unique_id.argtypes = [C.c_void_p]
     L.ptm_shard_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int]
@@ -634,6 +635,11 @@ class Engine:
         q = PtmDeParams(snooker, gamma_one_frac, reduce_gamma, ignore_frac)
         ir = None if init_rows is None else np.ascontiguousarray(init_rows, dtype=np.float64).reshape(-1, self.Nc, self.D)
         _chk(self.L.ptm_set_proposal_de(self.h, C.byref(q), 0 if ir is None else ir.shape[0], None if ir is None else ir.ctypes.data_as(_dp)))
+
+    def set_proposal_prior_draw(self, member):
+        """the member of the current proposal set (mixture, or top level of the adaptive set) that draws whole states from the prior
+        on the device (ptm_set_proposal_prior_draw); -1 switches it off"""
+        _chk(self.L.ptm_set_proposal_prior_draw(self.h, int(member)))
 
     def set_proposal_adaptive(self, K, scales, one_d_fracs, weights, thresholds, repeat_bits=None, outcomes=None, nested=-1, K_inner=0,
                               rate=0.0, rate_inner=0.0):

@@ -742,6 +742,9 @@ class proposal_distribution {
   // differential evolution the device can draw itself (ptm_set_proposal_de): no temperature mixing, unlikely_alpha = 0; a set answers
   // for its differential-evolution member
   virtual bool device_describe_de(ptm_de_params& q) const { return false; }
+  // independent draws from a distribution (draw_from_dist): the distribution, for the ladder to compare with the prior it gave the
+  // engine -- the device draws from that one only (ptm_set_proposal_prior_draw); a set answers for its member; nullptr: no such draws
+  virtual const sampleable_probability_function* device_draw_source() const { return nullptr; }
 };
 
 namespace detail {
@@ -863,6 +866,13 @@ class draw_from_dist : public proposal_distribution {
   }
   draw_from_dist* clone() const override { return new draw_from_dist(*this); }
   std::string show() override { return "DrawFrom[" + dist.show() + "]()"; }
+  // the device draws from the engine's own prior: whether `dist` is that one is the ladder's to say (set_proposal)
+  const sampleable_probability_function* device_draw_source() const override { return &dist; }
+  // PTM_HOST_PRIOR_DRAW=1 keeps every such member on the host-proposal path (A/B timing)
+  static bool kept_on_host() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_PRIOR_DRAW"); return v && *v && *v != '0'; }();
+    return off;
+  }
 };
 
 // user_gaussian_prop (proposal_distribution.hh:236-304, .cc:259-474): a Gaussian step on a named sub-space whose covariance a
@@ -1184,17 +1194,45 @@ class proposal_distribution_set : public proposal_distribution {
     }
     return at;
   }
+  // the member that draws from a distribution (draw_from_dist; -1: none, -2: more than one or PTM_HOST_PRIOR_DRAW).  The device draws
+  // it if the distribution is the engine's prior (ptm_set_proposal_prior_draw), which the ladder checks (device_draw_source)
+  int device_prior_member() const {
+    int at = -1;
+    for (size_t i = 0; i < slots.size(); i++) {
+      if (dynamic_cast<const proposal_distribution_set*>(slots[i].prop) || !slots[i].prop->device_draw_source()) continue;
+      if (at >= 0 || draw_from_dist::kept_on_host()) return -2;
+      at = (int)i;
+    }
+    return at;
+  }
+  const sampleable_probability_function* device_draw_source() const override {
+    const int pm = device_prior_member();
+    return pm >= 0 ? slots[pm].prop->device_draw_source() : nullptr;
+  }
+  // a draw_from_dist anywhere the device cannot take it: inside a nested set, two of them, or kept on the host by the environment
+  bool prior_draws_need_host() const {
+    if (device_prior_member() == -2) return true;
+    for (size_t i = 0; i < slots.size(); i++) {
+      const proposal_distribution_set* in = dynamic_cast<const proposal_distribution_set*>(slots[i].prop);
+      if (in && (in->device_prior_member() != -1 || in->prior_draws_need_host())) return true;
+    }
+    return false;
+  }
   int first_gaussian_member() const {
-    const int de = device_de_member();
-    for (size_t i = 0; i < slots.size(); i++) if ((int)i != de) return (int)i;
+    const int de = device_de_member(), pm = device_prior_member();
+    for (size_t i = 0; i < slots.size(); i++) if ((int)i != de && (int)i != pm) return (int)i;
     return -1;
   }
+  // temperature-dependent shares (Tpow > 0): the device takes them from a set whose TOP shares do not adapt -- every rung's clone hands
+  // over the thresholds it built at set_chain, and nothing rebuilds them; an adapting thermal set stays on the host
+  bool thermal_on_host() const { return thermal_power > 0 && adapt_rate != 0; }
+  bool thermal() const { return thermal_power > 0; }
   bool device_describe_de(ptm_de_params& q) const override {
     const int de = device_de_member();
-    return de >= 0 && (adapt_rate == 0 || adaptive()) && !(thermal_power > 0) && slots[de].prop->device_describe_de(q);
+    return de >= 0 && (adapt_rate == 0 || adaptive()) && !thermal_on_host() && slots[de].prop->device_describe_de(q);
   }
   bool device_describe(int dim, int& kind, std::vector<double>& f, double& odf) const override {
-    if (thermal_power > 0) return false;   // temperature-dependent shares are the host's business
+    if (thermal_on_host() || prior_draws_need_host()) return false;
     if (adaptive()) {                      // shares that move: the device's adaptive set (device_describe_adaptive)
       ptm_adaptive_set a;
       std::vector<double> sc, od;
@@ -1211,8 +1249,8 @@ class proposal_distribution_set : public proposal_distribution {
   }
   // Gaussian members that are scalar multiples of one factor, and at most one differential evolution (scale -1: ptm_set_proposal_de)
   bool device_describe_mixture(int dim, std::vector<double>& cum, std::vector<double>& scales, std::vector<double>& odfs) const override {
-    if (adapt_rate != 0 || thermal_power > 0 || adaptive()) return false;
-    const int de = device_de_member(), g0 = first_gaussian_member();
+    if (adapt_rate != 0 || adaptive() || prior_draws_need_host()) return false;
+    const int de = device_de_member(), g0 = first_gaussian_member(), pm = device_prior_member();
     if (de == -2 || g0 < 0) return false;
     int kind0; double odf0; std::vector<double> f0;
     if (!slots[g0].prop->device_describe(dim, kind0, f0, odf0)) return false;
@@ -1220,6 +1258,7 @@ class proposal_distribution_set : public proposal_distribution {
     for (size_t i = 0; i < slots.size(); i++) {
       cum.push_back(i + 1 == slots.size() ? 1.0 : upper[i]);
       if ((int)i == de) { scales.push_back(-1.0); odfs.push_back(0.0); continue; }
+      if ((int)i == pm) { scales.push_back(1.0); odfs.push_back(0.0); continue; }   // (neither is read: ptm_set_proposal_prior_draw)
       int kind; double odf; std::vector<double> f;
       if (!slots[i].prop->device_describe(dim, kind, f, odf) || kind != kind0 || f.size() != f0.size()) return false;
       double sc = 0;
@@ -1248,19 +1287,19 @@ class proposal_distribution_set : public proposal_distribution {
     const int n = nested_member();
     return n >= 0 && ((const proposal_distribution_set*)slots[n].prop)->adapt_rate != 0;
   }
-  // The adaptive set the device draws: Tpow = 0, up to eight top members -- at most one differential evolution that is not the last
+  // The adaptive set the device draws: Tpow = 0 unless the top shares stay fixed, up to eight top members -- at most one differential evolution that is not the last
   // (scale -1), at most one nested adaptive set of Gaussians, and single Gaussians --, every Gaussian a scalar multiple of one factor
   // (kind, f: the first Gaussian's).  Leaves: the top members, then the nested set's; the nested member's own entry is 1.
   bool device_describe_adaptive(int dim, int& kind, std::vector<double>& f, ptm_adaptive_set& a, std::vector<double>& scales,
                                 std::vector<double>& odfs) const {
-    if (thermal_power > 0 || !adaptive() || slots.size() > 8) return false;
-    const int nest = nested_member(), de = device_de_member();
+    if (thermal_on_host() || prior_draws_need_host() || !adaptive() || slots.size() > 8) return false;
+    const int nest = nested_member(), de = device_de_member(), pm = device_prior_member();
     if (nest == -2 || de == -2 || (nest >= 0 && nest == de)) return false;
     const proposal_distribution_set* in = nest >= 0 ? (const proposal_distribution_set*)slots[nest].prop : nullptr;
     if (in && (in->thermal_power > 0 || in->slots.size() > 8 || in->nested_member() != -1 || in->device_de_member() != -1)) return false;
     std::vector<const proposal_distribution*> gauss;   // every Gaussian leaf, in leaf order
     for (size_t i = 0; i < slots.size(); i++)
-      if ((int)i != de && (int)i != nest) gauss.push_back(slots[i].prop);
+      if ((int)i != de && (int)i != nest && (int)i != pm) gauss.push_back(slots[i].prop);
     if (in)
       for (size_t j = 0; j < in->slots.size(); j++) gauss.push_back(in->slots[j].prop);
     if (gauss.empty()) return false;
@@ -1280,7 +1319,7 @@ class proposal_distribution_set : public proposal_distribution {
     for (size_t i = 0; i < slots.size(); i++) {
       double sc = 1.0, odf = 0.0;
       if ((int)i == de) sc = -1.0;
-      else if ((int)i != nest && !scale_of(slots[i].prop, sc, odf)) return false;
+      else if ((int)i != nest && (int)i != pm && !scale_of(slots[i].prop, sc, odf)) return false;
       scales.push_back(sc); odfs.push_back(odf);
     }
     if (in)
@@ -2208,6 +2247,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   bool host_mode = false, want_host = false;
   bool want_de = false, de_built = false;   // differential evolution drawn on the device from the device's history
   bool adaptive_dev = false;                // the proposal is an adaptive set drawn and adapted on the device (ptm_set_proposal_adaptive)
+  bool prior_dev = false;                   // a member of the set draws from the prior on the device (ptm_set_proposal_prior_draw)
   int ring_rows = 0, ring_rungs = 0;   // the device history ring as the engine was created with it
   uint64_t eng_seed = 0;
   struct mirror_t {   // one chain's saved history, raw indexing as MH_chain::states / lposts / llikes (chain.hh:155-163)
@@ -2876,6 +2916,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       all.insert(all.end(), f.begin(), f.end());
       odfs[i] = odf;
     }
+    if (on_device && !prior_draws_fit_device(proposal, init_prior, prior_on_host)) on_device = false;
     {
       ptm_de_params q;
       if (on_device && proposal.device_describe_de(q)) {
@@ -2891,6 +2932,10 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       ptm_check(ptm_set_proposals(eng, kind, all.data(), odfs.data()), "set_proposals");
       std::vector<double> cum, sc, od;
       proposal_distribution_set* ps = dynamic_cast<proposal_distribution_set*>(&proposal);
+      // temperature-dependent shares: every rung's clone builds its thresholds from the rung's temperature as it is now (set_chain,
+      // proposal_distribution.hh:336) and hands them over below; nothing rebuilds them later (the top shares do not adapt)
+      if (ps && ps->thermal())
+        for (int i = 0; i < Ntemps; i++) props[i]->set_chain(&views[i]);
       ptm_adaptive_set as;
       int kind_a;
       std::vector<double> f_a;
@@ -2918,13 +2963,18 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       } else if (proposal.device_describe_mixture(dim, cum, sc, od)) {   // a proposal_distribution_set of scaled Gaussians
         const int K = (int)cum.size();
         std::vector<double> C((size_t)Ntemps * K), S(C.size()), O(C.size());
-        for (int i = 0; i < Ntemps; i++)
+        for (int i = 0; i < Ntemps; i++) {
+          if (!props[i]->device_describe_mixture(dim, cum, sc, od) || (int)cum.size() != K) { std::cout << "parallel_tempering_chains::set_proposal: rung " << i << "'s clone describes another set" << std::endl; exit(1); }
           for (int k = 0; k < K; k++) { C[(size_t)i * K + k] = cum[k]; S[(size_t)i * K + k] = sc[k]; O[(size_t)i * K + k] = od[k]; }
+        }
         ptm_check(ptm_set_proposal_mixture(eng, K, C.data(), S.data(), O.data()), "set_proposal_mixture");
       } else {
         ptm_check(ptm_set_proposal_mixture(eng, 0, nullptr, nullptr, nullptr), "set_proposal_mixture");
       }
       ptm_check(ptm_set_proposal_callback(eng, nullptr, nullptr, nullptr), "set_proposal_callback");
+      const int pm = ps ? ps->device_prior_member() : -1;
+      prior_dev = pm >= 0;
+      if (prior_dev) ptm_check(ptm_set_proposal_prior_draw(eng, pm), "set_proposal_prior_draw");
       ptm_de_params q;
       if (proposal.device_describe_de(q)) {
         // the set's differential evolution is drawn on the device from the device's own history: the extra draws of initialize(n),
@@ -2938,6 +2988,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       }
       return;
     }
+    prior_dev = false;
     if (!host_mode) build_engine(true);   // (initialize() did not know: the engine is set up again, with the same draws)
     for (int w = 0; w < W; w++)
       for (int i = 0; i < Ntemps; i++) {
@@ -2950,6 +3001,22 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
               "set_proposal_callback");
   }
   bool proposals_on_host() const { return host_mode; }
+  bool draws_prior_on_device() const { return prior_dev; }
+  // Can the device make this proposal's draws from a distribution (draw_from_dist members, device_draw_source)?  Only from the very
+  // prior the engine was given as a per-dimension product without a flat dimension (ptm_set_proposal_prior_draw); true without such members
+  static bool prior_draws_fit_device(const proposal_distribution& proposal, const sampleable_probability_function* prior, bool prior_on_host) {
+    const proposal_distribution_set* ps = dynamic_cast<const proposal_distribution_set*>(&proposal);
+    if (!ps) return proposal.device_draw_source() == nullptr;   // (a draw_from_dist on its own: the host's)
+    if (ps->prior_draws_need_host()) return false;
+    const sampleable_probability_function* src = ps->device_draw_source();
+    if (!src) return true;
+    if (src != prior || prior_on_host) return false;
+    std::vector<int> types;
+    std::vector<double> centers, halfwidths;
+    if (!prior->describe(types, centers, halfwidths)) return false;
+    for (size_t d = 0; d < types.size(); d++) if (types[d] == PTM_PRIOR_FLAT) return false;
+    return true;
+  }
   bool prior_evaluated_on_host() const { return prior_on_host; }   // the prior is not a per-dimension product (describe() == false)
   // chain::report_prop (chain.cc:2096-2109 flavour): every rung's proposal report, replica 0
   std::string report_prop(int style = 0) override {
@@ -3617,6 +3684,10 @@ class ptmcmc_sampler : public bayes_sampler {
     int kind; double odf; std::vector<double> f;
     const int dim = chain_prior->getDim();
     bool host = !cprop->device_describe(dim, kind, f, odf) && !dynamic_cast<user_gaussian_prop*>(cprop);
+    {
+      std::vector<int> ty; std::vector<double> ce, hw;
+      if (!host && !parallel_tempering_chains::prior_draws_fit_device(*cprop, chain_prior, !chain_prior->describe(ty, ce, hw))) host = true;
+    }
     // A set with a differential evolution the device can draw (the default recipe): the device keeps EVERY rung's saved history of
     // the whole run -- up to two add_state calls per step, every save_every-th saved -- if that fits (16 GB here); else the host draws
     ptm_de_params deq;
@@ -3636,6 +3707,9 @@ class ptmcmc_sampler : public bayes_sampler {
     cc->use_host_proposals(host);
     cc->initialize(chain_llike, chain_prior, (host || de_dev) ? Ninit : 1, ProbabilityDist::nextLadderSeed());
     cc->set_proposal(*cprop);
+    if (cprop->device_draw_source() || cc->draws_prior_on_device() || draw_from_dist::kept_on_host())
+      std::cout << "ptmcmc_sampler::initialize: draws from the prior are made on the " << (cc->draws_prior_on_device() ? "device (ptm_set_proposal_prior_draw)" : "host (the host-proposal step)")
+                << "; proposals are drawn on the " << (cc->proposals_on_host() ? "host" : "device") << std::endl;
     return 0;
   }
 
@@ -3726,6 +3800,7 @@ class ptmcmc_sampler : public bayes_sampler {
     return 0;
   }
   parallel_tempering_chains* chains() { return cc.get(); }
+  proposal_distribution* selected_proposal() { return have_cprop ? cprop : nullptr; }   // what select_proposal chose or built
 };
 
 }  // namespace ptmgpu
