@@ -459,6 +459,15 @@ int ptm_get_ladder_stats(ptm_engine* e, int64_t out[4]);
  * that wants "Metropolis moves made so far" reads 16 bytes instead of two arrays (and leaves the GPU no idle gap to drop
  * its clocks in).  Waits for the engine's stream. */
 int ptm_get_counter_sums(ptm_engine* e, int64_t* ntries_sum, int64_t* naccept_sum);
+/* The box pre-pass of big-population steps: before the compacted 32-dimension sweep a kernel of its own draws the first 16
+ * coordinates of each proposal on the rungs flagged for it and settles the chains whose proposal has left the uniform prior's box
+ * there already (a rejection: Ntries + 1); the sweep sees the others.  Results do not depend on it.  out[0] chains it has seen so
+ * far, out[1] chains it settled, out[2] local rungs flagged at the last such sweep (out[0..2] are zero until the first sweep that
+ * launches the pass, whatever out[3] says: the flags are made then), out[3] 1 if a whole step's sweep of this engine
+ * is eligible (all-uniform prior, open bounds, lower-triangular or diagonal factor, fixed ladder, no history).  PTM_BOX_PREFILTER=0
+ * in the environment switches the pass off, =1 flags every rung of an eligible sweep.  Waits for the engine's stream.  No reference
+ * counterpart. */
+int ptm_get_prefilter_counts(ptm_engine* e, int64_t out[4]);
 /* What this device gives a plain streaming copy and an f64 fma issue loop right now, on the engine's stream (bench.py prints it
  * beside its roofline: devices of one pool differ by several per cent in the clock they hold under load, and a line without it
  * cannot tell a slow box from a slow kernel).  copy_GBs: bytes read + written by a 16-byte-per-lane copy of copy_bytes / 2 bytes,

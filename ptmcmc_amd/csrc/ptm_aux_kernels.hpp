@@ -19,11 +19,16 @@ constexpr int PART_CHUNK = 16384;   // walkers per block: 1024 threads x 16 touc
 // somebody needs the array (nhist_flush_kernel).  Only a rung exchanged twice in the step gets its extra add at once.
 __global__ __launch_bounds__(1024) void partition_kernel(int W, int rung0, int nchunk, unsigned char* __restrict__ touch,
                                                          unsigned int* __restrict__ nhist, int* __restrict__ cidx, int* __restrict__ ccnt,
-                                                         const unsigned short* __restrict__ rowof) {
+                                                         const unsigned short* __restrict__ rowof, const unsigned char* __restrict__ pflag,
+                                                         int* __restrict__ pidx, int* __restrict__ pcnt) {
   extern __shared__ int plist[];   // [PART_CHUNK] the block's listed walkers, then written out in one coalesced sweep
   __shared__ int wsum[16];
   __shared__ int sbase, stotal;
   const int rl = rung0 + blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
+  // a rung flagged for the box pre-pass (ptm_box_prefilter.hpp; pflag null: none): its list goes there first
+  const bool pre = pflag && pflag[rl];
+  int* const lidx = pre ? pidx : cidx;
+  int* const lcnt = pre ? pcnt : ccnt;
   const int w0 = ch * PART_CHUNK + threadIdx.x * 16;      // this thread's 16 walkers (W is a multiple of 64: all or none)
   const size_t c0 = (size_t)rl * W + w0;
   uint4 v = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);   // past the end: "touched", nothing to list
@@ -52,7 +57,7 @@ __global__ __launch_bounds__(1024) void partition_kernel(int W, int rung0, int n
     int run = 0;
     for (int k = 0; k < 16; ++k) { const int t = wsum[k]; wsum[k] = run; run += t; }
     stotal = run;
-    sbase = run ? atomicAdd(&ccnt[rl], run) : 0;    // (several chunks of a long rung share the rung's list)
+    sbase = run ? atomicAdd(&lcnt[rl], run) : 0;    // (several chunks of a long rung share the rung's list)
   }
   __syncthreads();
   if (in) {
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(1024) void partition_kernel(int W, int rung0, int n
     }
   }
   __syncthreads();
-  int* out = cidx + (size_t)rl * W + sbase;
+  int* out = lidx + (size_t)rl * W + sbase;
   for (int i = threadIdx.x; i < stotal; i += 1024) out[i] = plist[i];
 }
 // Row labels back to the identity, the rows back to their own rungs (flush_rows of the engine): in place, one block per walker.  The

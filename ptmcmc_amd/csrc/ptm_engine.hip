@@ -18,6 +18,7 @@
 
 #include "../../include/ptm_engine.h"
 #include "ptm_aux_kernels.hpp"
+#include "ptm_box_prefilter.hpp"
 #include "ptm_devlike_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
@@ -135,6 +136,15 @@ struct ptm_engine {
   // compacted sweep (partition_kernel): per-rung lists of the walkers that move, their counts; touched = an exchange phase
   // ran since the last sweep
   int *cidx = nullptr, *ccnt = nullptr;
+  // box pre-pass (ptm_box_prefilter.hpp): the lists of the flagged rungs (partition_kernel writes them there instead), the rungs'
+  // flags, {chains seen, chains settled}; on the host the standard deviations of the first 16 coordinates of each rung's proposal,
+  // from which -- with the prior box -- the flags are made when any of the two has changed (pf_dirty)
+  int *pidx = nullptr, *pcnt = nullptr;
+  unsigned char *pf_flag = nullptr, *h_pf_flag = nullptr;   // (h_pf_flag: pinned, so that the flags' upload waits for nothing)
+  unsigned long long* pf_counts = nullptr;
+  std::vector<double> pf_sigma;
+  bool pf_dirty = true;
+  int pf_flagged = 0, pf_grid = 0;
   bool touched = false;
   bool compact_step = false;   // this step's (partial) sweeps are compacted
   // row labels (ptm_decide.hpp): [Nc] the rung slot of xdev that holds each chain's row.  Only the exchange kernel and the compacted
@@ -502,13 +512,14 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
   for (auto& b : e->host_blocks) (void)hipHostFree(b.first);
   void* ptrs[] = {e->xdev, e->rowof, e->ll, e->lp, e->ntries, e->naccept, e->last_type, e->arr_below, e->arr_above, e->mv_src, e->mv_dst, e->mv_n,
                   e->err, e->nhist, e->swap_cnt, e->touch, e->swap_log, e->hist.x, e->hist.ll, e->hist.lp, e->hist.meta, e->map.lpost, e->map.ll, e->map.lp, e->map.x, e->blo,
-                  e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt,
+                  e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt, e->pidx, e->pcnt, e->pf_flag, e->pf_counts,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
                   e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
                   e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (e->h_sums) (void)hipHostFree(e->h_sums);
+  if (e->h_pf_flag) (void)hipHostFree(e->h_pf_flag);
   for (hipEvent_t ev : e->kev) (void)hipEventDestroy(ev);
   if (e->t0) (void)hipEventDestroy(e->t0);
   if (e->t1) (void)hipEventDestroy(e->t1);
@@ -592,6 +603,7 @@ extern "C" int ptm_set_prior(ptm_engine* e, const int32_t* types, const double* 
     }
   }
   e->lprior_const = std::log(prod);  // the reference takes libm log of the product of these constants on every call
+  e->pf_dirty = true;
   e->lp_is_const = false;            // (re-established when states are set)
   for (int d = 0; d < D; ++d) { e->h_ptype[d] = ty[d]; e->h_plo[d] = lo[d]; e->h_phi[d] = hi[d]; }
   int rc;
@@ -943,6 +955,9 @@ extern "C" int ptm_set_proposals(ptm_engine* e, int kind, const double* factors,
     }
   if ((rc = upload(e->onedfrac, f.data(), (size_t)nloc, e->stream))) return rc;
   e->prop_kind = kind; e->prop_stride = stride; e->have_prop = 1;
+  e->pf_sigma.assign((size_t)nloc * PREFILTER_DIMS, 0.0);
+  for (int r = 0; r < nloc; ++r) prefilter_sigmas(kind == PTM_PROP_DIAG, factors + (size_t)r * (kind == PTM_PROP_DIAG ? D : D * D), D, &e->pf_sigma[(size_t)r * PREFILTER_DIMS]);
+  e->pf_dirty = true;
   return PTM_OK;
 }
 
@@ -1249,6 +1264,8 @@ extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double
     }
     if ((rc = upload(e->prop_tiles + (size_t)local_rung * ntile * 64, tiles.data(), tiles.size(), e->stream))) return rc;
   }
+  prefilter_sigmas(kind == PTM_PROP_DIAG, factor, D, &e->pf_sigma[(size_t)local_rung * PREFILTER_DIMS]);
+  e->pf_dirty = true;
   if (one_d_frac >= 0) {
     if (one_d_frac > 1) return fail(PTM_ERR_INVALID, "oneDfrac must be in [0,1]");
     if ((rc = upload(e->onedfrac + local_rung, &one_d_frac, 1, e->stream))) return rc;
@@ -1517,6 +1534,26 @@ static int devlike_debug(ptm_engine* e, const double* X, int n, double* llike) {
 // a shard's exchange phases and partial sweeps: not with a device likelihood
 #define NO_DEVLIKE(e, name) do { if ((e) && (e)->dfn) return fail(PTM_ERR_UNSUPPORTED, name " with a device likelihood is not built (rung-sharded steps)"); } while (0)
 
+// box pre-pass: which local rungs it takes (ptm_sweep_plan.hpp: prefilter_flag), from the proposals' spread and the prior box.
+// pf_sigma follows every writer of prop_tiles (ptm_set_proposals, ptm_set_proposal_rung: there is no other -- mixtures, adaptive sets and
+// differential evolution keep a sweep off this kernel family or off its lean build); a setter that marks pf_dirty has waited for the
+// stream, so the pinned staging buffer is free when it is rewritten here and the upload is queued without a host wait.
+static int prefilter_flags(ptm_engine* e) {
+  const int nd = e->D < PREFILTER_DIMS ? e->D : PREFILTER_DIMS;
+  double width[PREFILTER_DIMS];
+  for (int d = 0; d < nd; ++d) width[d] = e->h_phi[d] - e->h_plo[d];
+  if (!e->h_pf_flag) HIPCHK(hipHostMalloc((void**)&e->h_pf_flag, (size_t)e->nloc, hipHostMallocDefault));
+  unsigned char* fl = e->h_pf_flag;
+  e->pf_flagged = 0;
+  for (int r = 0; r < e->nloc; ++r) {
+    fl[r] = (e->pf_sigma.size() == (size_t)e->nloc * PREFILTER_DIMS && prefilter_flag(&e->pf_sigma[(size_t)r * PREFILTER_DIMS], width, nd, sweep_env().prefilter)) ? 1 : 0;
+    e->pf_flagged += fl[r];
+  }
+  HIPCHK(hipMemcpyAsync(e->pf_flag, fl, (size_t)e->nloc, hipMemcpyHostToDevice, e->stream));
+  e->pf_dirty = false;
+  return PTM_OK;
+}
+
 static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = true) {
   const bool labelled = e->label_step;   // (set by this step's exchange phase under the very conditions of the compacted sweep below)
   e->label_step = false;
@@ -1548,11 +1585,44 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   if (compact) {
     if (!e->cidx) { int rc; if ((rc = dalloc(&e->cidx, (size_t)e->Nc)) || (rc = dalloc(&e->ccnt, (size_t)e->nloc))) return rc; }
     HIPCHK(hipMemsetAsync(e->ccnt + rung0, 0, (size_t)nr * sizeof(int), e->stream));
+    // box pre-pass (ptm_box_prefilter.hpp): the flagged rungs' lists go to it first, and it hands their survivors on to the sweep
+    bool pre = plan.prefilter;
+    if (pre) {
+      if (!e->pidx) {
+        int rc;
+        if ((rc = dalloc(&e->pidx, (size_t)e->Nc)) || (rc = dalloc(&e->pcnt, (size_t)e->nloc)) || (rc = dalloc(&e->pf_flag, (size_t)e->nloc)) || (rc = dalloc(&e->pf_counts, 2))) return rc;
+        HIPCHK(hipMemsetAsync(e->pf_counts, 0, 16, e->stream));
+        e->pf_dirty = true;
+      }
+      if (e->pf_dirty) { int rc = prefilter_flags(e); if (rc) return rc; }
+      pre = e->pf_flagged > 0;
+      if (pre) HIPCHK(hipMemsetAsync(e->pcnt + rung0, 0, (size_t)nr * sizeof(int), e->stream));
+    }
     const int nchunk = (e->W + PART_CHUNK - 1) / PART_CHUNK;
     hipLaunchKernelGGL(partition_kernel, dim3((unsigned)((size_t)nr * nchunk)), dim3(1024), (size_t)PART_CHUNK * sizeof(int), e->stream, e->W, rung0, nchunk, e->touch, e->nhist,
-                       e->cidx, e->ccnt, labelled ? (const unsigned short*)e->rowof : nullptr);
+                       e->cidx, e->ccnt, labelled ? (const unsigned short*)e->rowof : nullptr, pre ? (const unsigned char*)e->pf_flag : nullptr, e->pidx, e->pcnt);
     e->compact_step = true;   // (every partial sweep of this step goes the same way: the step is counted once, at its end)
     HIPCHK(hipGetLastError());
+    if (pre) {
+      BoxPre b;
+      memset(&b, 0, sizeof b);
+      b.W = e->W; b.Nt = e->Nt; b.r0 = e->r0; b.w_off = e->cfg.walker_begin; b.rung0 = rung0; b.nrung = nr; b.labelled = labelled ? 1 : 0;
+      b.seed = e->cfg.seed; b.step = e->step;
+      b.x = p.x; b.ll = e->ll; b.lp = e->lp; b.beta = e->beta; b.prop_tiles = e->prop_tiles; b.box_row = e->box_row; b.ntries = e->ntries;
+      b.pidx = e->pidx; b.pcnt = e->pcnt; b.cidx = e->cidx; b.ccnt = e->ccnt; b.counts = e->pf_counts;
+      const size_t lds = box_prefilter_lds(nr);
+      if (!e->pf_grid) {   // a persistent grid: the blocks the device holds at once
+        int per_cu = 0, dev = 0;
+        hipDeviceProp_t pr;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_kernel, 256, box_prefilter_lds(e->nloc)) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
+        HIPCHK(hipGetDevice(&dev));
+        HIPCHK(hipGetDeviceProperties(&pr, dev));
+        e->pf_grid = per_cu * (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
+      }
+      const long long tiles = (long long)nr * ((e->W + 255) / 256);
+      hipLaunchKernelGGL(box_prefilter_kernel, dim3((unsigned)(tiles < e->pf_grid ? tiles : e->pf_grid)), dim3(256), lds, e->stream, b);
+      HIPCHK(hipGetLastError());
+    }
     p.cidx = e->cidx; p.ccnt = e->ccnt; p.cidx_slot = labelled ? 1 : 0;
   }
   // the timed bracket holds the sweep kernel alone (its name: ptm_sweep_kernel_name): the list fill and partition_kernel of a
@@ -3026,6 +3096,21 @@ extern "C" int ptm_get_counter_sums(ptm_engine* e, int64_t* ntries_sum, int64_t*
   HIPCHK(hipStreamSynchronize(e->stream));
   if (ntries_sum) *ntries_sum = (int64_t)e->h_sums[0];
   if (naccept_sum) *naccept_sum = (int64_t)e->h_sums[1];
+  return PTM_OK;
+}
+
+extern "C" int ptm_get_prefilter_counts(ptm_engine* e, int64_t out[4]) {
+  if (!e || !out) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_get_prefilter_counts");
+  int rc = ladder_settle(e);
+  if (rc) return rc;
+  out[0] = out[1] = out[2] = 0;
+  out[3] = step_sweep_plan(e).prefilter ? 1 : 0;
+  if (!e->pf_counts) return PTM_OK;
+  unsigned long long h[2];
+  HIPCHK(hipMemcpyAsync(h, e->pf_counts, 16, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  out[0] = (int64_t)h[0]; out[1] = (int64_t)h[1]; out[2] = e->pf_flagged;
   return PTM_OK;
 }
 

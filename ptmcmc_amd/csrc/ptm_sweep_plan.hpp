@@ -1,6 +1,7 @@
 // ptm_sweep_plan.hpp -- which kernel a sweep (and a whole step) runs on: the decision, once, as plain C++ (no HIP: the
 // launches in ptm_sweep_inst.inc, the engine's preparations for them and the names it reports all read the same plan).
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -27,15 +28,19 @@ struct SweepFacts {
 };
 
 // the environment's say: PTM_FORCE_VALU set, non-empty and not "0" keeps every workload off the matrix cores and off the lanes
-// kernel's population rules (A/B measurements, tests); PTM_COMPACT=0 switches the compacted sweep off.  Read once per process.
+// kernel's population rules (A/B measurements, tests); PTM_COMPACT=0 switches the compacted sweep off; PTM_BOX_PREFILTER=0 switches
+// the box pre-pass (ptm_box_prefilter.hpp) off, =1 gives it every rung of a sweep it is eligible for, unset: the estimate decides
+// (prefilter_flag below).  Read once per process.
 struct SweepEnv {
   bool force_valu, compact_ok;
+  int prefilter;   // 0: the estimate decides, 1: every eligible rung, -1: off
 };
 inline const SweepEnv& sweep_env() {
   static const SweepEnv v = [] {
     const char* f = getenv("PTM_FORCE_VALU");
     const char* c = getenv("PTM_COMPACT");
-    return SweepEnv{f && *f && *f != '0', !(c && *c == '0')};
+    const char* b = getenv("PTM_BOX_PREFILTER");
+    return SweepEnv{f && *f && *f != '0', !(c && *c == '0'), (b && *b) ? (*b == '0' ? -1 : 1) : 0};
   }();
   return v;
 }
@@ -53,6 +58,7 @@ struct SweepPlan {
   bool ev;
   bool bnd;              // sweep_mfma{64,128}_kernel<KIND, BND, EV>
   bool compacted;        // the moving chains' lists are to be built (partition_kernel) before the launch
+  bool prefilter;        // the box pre-pass (ptm_box_prefilter.hpp) may take rungs of this sweep: not an argument of the build, and not in its name
 };
 // the lean matrix-core build of evolving ladders reads the ladder-major temperatures, every other build the chain-indexed image
 inline bool reads_ladder_major_beta(const SweepPlan& s) { return s.family == FAM_MFMA32 && s.mgen == 0 && s.ev; }
@@ -86,6 +92,10 @@ inline SweepPlan plan_sweep(const SweepFacts& f, const SweepEnv& env) {
     // 0 lean; 1 uniform priors and box bounds with the recipe's code, 3 without it (built compacted only); 2 everything
     s.mgen = (simple || lean_ev) ? 0 : !box ? 2 : (s.compacted && !recipe) ? 3 : 1;
     s.ev = !simple && box && f.evolving;
+    // The box pre-pass settles proposals that have left an all-uniform prior's box in dimensions 0..15: the compacted lean build of a
+    // fixed ladder (open bounds, no mean, no one-dimensional moves, no mixture -- `simple`), with a lower-triangular or diagonal factor
+    // (a dense factor reaches every row from every column).  Evolving ladders are left out: nothing tests them with it.
+    s.prefilter = env.prefilter >= 0 && s.compacted && s.mgen == 0 && !s.ev && (f.kind == PLAN_LOWER || f.kind == PLAN_DIAG);
     return s;
   }
   if ((f.DP == 64 || f.DP == 128) && mfma_ok && box && !recipe && !f.tracked) {
@@ -112,6 +122,49 @@ inline SweepPlan plan_sweep(const SweepFacts& f, const SweepEnv& env) {
   s.family = FAM_GENERAL;
   s.uni = uni; s.simple = simple; s.ada = ada;
   return s;
+}
+
+// ---- which rungs the box pre-pass takes -------------------------------------------------------------------------------------
+// It pays on a rung where the share of proposals it settles exceeds its own cost per chain relative to the sweep's (both kernels are
+// bound by instruction issue, so cost is per listed chain).  The share is estimated for a state uniform in the box -- which is what
+// the hot rungs of a ladder hold, and the cold ones, deep inside the box, settle next to nothing either way.  A heuristic: a wrong
+// flag changes which kernel does the work and nothing in the results.
+constexpr int PREFILTER_DIMS = 16;
+#ifndef PTM_PREFILTER_THRESHOLD
+#define PTM_PREFILTER_THRESHOLD 0.70   // measured break-even 0.50-0.57 (what a pre-pass chain costs of a sweep chain) + a margin: on the rungs
+                                       // between cold and hot the state is not yet uniform in the box and the estimate reads high
+                                       // (0.60 estimated where a model of the sampler counts 0.22), at 0.70 it is within 0.1
+#endif
+// the standard deviations of the first 16 coordinates of a rung's proposal: sigma_d^2 = sum_k T[d][k]^2 (factor: row-major D x D, or D sigmas)
+inline void prefilter_sigmas(bool diag, const double* factor, int D, double* sigma) {
+  for (int d = 0; d < PREFILTER_DIMS; ++d) {
+    double s2 = 0.0;
+    if (d < D) {
+      if (diag) s2 = factor[d] * factor[d];
+      else for (int k = 0; k < D; ++k) s2 += factor[(size_t)d * D + k] * factor[(size_t)d * D + k];
+    }
+    sigma[d] = std::sqrt(s2);
+  }
+}
+// P(x + sigma z leaves [0, w]) for x uniform in [0, w], z standard normal: 1 - erf(u / sqrt 2) + (2 / u)(phi(0) - phi(u)), u = w / sigma
+// (for a narrow proposal 0.798 sigma / w: a half-normal's mean step out of each of the two faces)
+inline double prefilter_out_1d(double sigma, double w) {
+  if (!(sigma > 0.0) || !(w < INFINITY)) return 0.0;
+  if (!(w > 0.0)) return 1.0;
+  const double u = w / sigma, phi0 = 0.3989422804014327;
+  const double in = std::erf(u * 0.7071067811865476) - (2.0 / u) * (phi0 - phi0 * std::exp(-0.5 * u * u));
+  return in < 0.0 ? 1.0 : (in > 1.0 ? 0.0 : 1.0 - in);
+}
+// the share of a rung's proposals that leave the box in its first nd dimensions (independent faces: 1 - prod (1 - P_d))
+inline double prefilter_out_share(const double* sigma, const double* width, int nd) {
+  double in = 1.0;
+  for (int d = 0; d < nd; ++d) in *= 1.0 - prefilter_out_1d(sigma[d], width[d]);
+  return 1.0 - in;
+}
+inline bool prefilter_flag(const double* sigma, const double* width, int nd, int env_prefilter) {
+  if (env_prefilter < 0) return false;
+  if (env_prefilter > 0) return true;
+  return prefilter_out_share(sigma, width, nd) > PTM_PREFILTER_THRESHOLD;
 }
 
 // the kernel's name as rocprofv3 prints it (sweep_kernel without its last, defaulted argument unless that is set); returns snprintf's count

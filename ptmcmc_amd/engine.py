@@ -34,6 +34,7 @@ EXPORTS = [
     "ptm_set_proposal_adaptive", "ptm_get_proposal_adapt_state", "ptm_set_proposal_adapt_state",
     "ptm_ess_windowed", "ptm_ess_report", "ptm_ess_series_windowed", "ptm_ess_series_report", "ptm_ess_last_on_device",
     "ptm_log_evidence",
+    "ptm_get_prefilter_counts",
 ]
 
 
@@ -147,6 +148,8 @@ def load():
     L.ptm_get_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptm_calibrate.argtypes = [C.c_void_p, C.POINTER(PtmCalibration)]
     L.ptm_get_counter_sums.argtypes = [C.c_void_p, _i64p, _i64p]
+    if hasattr(L, "ptm_get_prefilter_counts"):   # (an older library, PTM_ENGINE_LIB in A/B runs, has no box pre-pass)
+        L.ptm_get_prefilter_counts.argtypes = [C.c_void_p, _i64p]
     L.ptm_get_ladder_stats.argtypes = [C.c_void_p, _i64p]
     L.ptm_debug_eval.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]
     L.ptm_debug_philox.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, _u32p]
@@ -870,6 +873,13 @@ class Engine:
         t, a = C.c_int64(), C.c_int64()
         _chk(self.L.ptm_get_counter_sums(self.h, C.byref(t), C.byref(a)))
         return t.value, a.value
+
+    def prefilter_counts(self):
+        """box pre-pass (ptm_get_prefilter_counts): chains it saw and chains it settled so far, local rungs flagged for it, whether a
+        whole step's sweep of this engine is eligible for it"""
+        o = (C.c_int64 * 4)()
+        _chk(self.L.ptm_get_prefilter_counts(self.h, o))
+        return dict(seen=o[0], settled=o[1], rungs_flagged=o[2], eligible=bool(o[3]))
 
     def calibrate(self):
         """what this device gives a streaming copy and an f64 fma loop right now (ptm_calibrate)"""
