@@ -465,8 +465,8 @@ int ptm_get_counter_sums(ptm_engine* e, int64_t* ntries_sum, int64_t* naccept_su
  * far, out[1] chains it settled, out[2] local rungs flagged at the last such sweep (out[0..2] are zero until the first sweep that
  * launches the pass, whatever out[3] says: the flags are made then), out[3] 1 if a whole step's sweep of this engine
  * is eligible (all-uniform prior, open bounds, lower-triangular or diagonal factor, fixed ladder, no history).  PTM_BOX_PREFILTER=0
- * in the environment switches the pass off, =1 flags every rung of an eligible sweep.  Waits for the engine's stream.  No reference
- * counterpart. */
+ * in the environment switches the pass off, =1 flags every rung of an eligible sweep; PTM_PREFILTER_GRID=n (n >= 1) caps the pass's
+ * grid at n blocks (tests: results and counters do not depend on it).  Waits for the engine's stream.  No reference counterpart. */
 int ptm_get_prefilter_counts(ptm_engine* e, int64_t out[4]);
 /* What this device gives a plain streaming copy and an f64 fma issue loop right now, on the engine's stream (bench.py prints it
  * beside its roofline: devices of one pool differ by several per cent in the clock they hold under load, and a line without it

@@ -16,10 +16,25 @@
 // 16g + j, g = 0..3, on dimensions q + 4m, m < 4 (the 16-byte pieces 0..7 of the row), and owns chain l for the per-chain work.
 // The grid is persistent like the sweep's (the 20 KB of Box-Muller tables are staged once per resident block), and the two
 // counters (chains seen, chains settled) are summed per wave over all its tiles: two atomics per wave and launch.
+//
+// The tile loop is a pipeline over the block's tiles t, t + G, t + 2G, ... (G blocks): a tile's work is a chain of dependent trips to
+// memory -- list length, list entry, the rows / ll / lp / factor tiles it names, the counter's old value, the sweep list's old length
+// -- and a wave that makes them one after the other stands idle most of the time.  So: the list lengths sit in LDS beside the tile
+// prefix (the prologue reads them anyway); the list entry is asked for one tile before its draw (with PTM_BP_ROWS_AHEAD two, and
+// everything the entry names one tile before); ntries is an atomic add nobody waits for; and the append to the sweep's list asks
+// for its place at the end of tile t and stores the survivors at the end of the wave's next tile (after the loop for the last
+// one).  The order of a sweep list is arbitrary: any order gives the same chains.
 #pragma once
 #include "ptm_kernels.hpp"
+#include "ptm_sweep_plan.hpp"
 
 namespace ptm {
+
+#ifndef PTM_BP_ROWS_AHEAD
+#define PTM_BP_ROWS_AHEAD 0    // 1: the rows, ll, lp, beta and factor operands of the next tile are asked for before the current tile's draw too
+                               // (the entries then two tiles ahead): a second row buffer, 168 registers instead of 118, three waves per
+                               // SIMD instead of four.  Measured at the bench size: 0.355 ms against 0.346 with the entry alone
+#endif
 
 struct BoxPre {
   int W, Nt, r0, w_off;
@@ -40,10 +55,20 @@ struct BoxPre {
 typedef double bp_d4 __attribute__((ext_vector_type(4)));
 typedef double bp_d2 __attribute__((ext_vector_type(2)));
 
-// dynamic LDS of a launch over nrung rungs: tables | box | the rungs' tile prefix and the scan's chunk totals
-inline size_t box_prefilter_lds(int nrung) { return (size_t)(BM_TABLE_DOUBLES + 64) * sizeof(double) + ((size_t)nrung + 260) * sizeof(int); }
+// scheduling fence (ptm_mfma_kernel.hpp: PTM_STAGE): the loads asked ahead stay in front of the arithmetic they are to hide behind
+#define PTM_BP_STAGE() __builtin_amdgcn_sched_barrier(0)
 
-__global__ __launch_bounds__(256) void box_prefilter_kernel(const BoxPre p) {
+// what a tile reads through its list entries: the row pieces 0..7 of the wave's four groups, chain l's ll / lp, the rung's beta and
+// the four factor operands of the rt == 0 accumulator
+struct BpRows {
+  bp_d2 v0[4], v1[4];
+  double ll, lp, beta, ta[4];
+};
+
+// dynamic LDS of a launch over nrung rungs: tables | box | the rungs' tile prefix, their list lengths and the scan's chunk totals
+inline size_t box_prefilter_lds(int nrung) { return (size_t)(BM_TABLE_DOUBLES + 64) * sizeof(double) + (2 * (size_t)nrung + 260) * sizeof(int); }
+
+__global__ __launch_bounds__(256, PTM_BP_ROWS_AHEAD ? 3 : 4) void box_prefilter_kernel(const BoxPre p) {
   extern __shared__ __attribute__((aligned(16))) double bp_lds[];
   double* lbox = bp_lds + BM_TABLE_DOUBLES;
   int* tpre = reinterpret_cast<int*>(lbox + 64);   // [nrung] inclusive prefix of the rungs' 256-walker tiles
@@ -52,14 +77,15 @@ __global__ __launch_bounds__(256) void box_prefilter_kernel(const BoxPre p) {
   for (int t = 0; t < BM_TABLE_DOUBLES / 512; ++t)
     reinterpret_cast<bm_d2*>(bp_lds)[threadIdx.x + 256 * t] = reinterpret_cast<const bm_d2*>(BM_TABLE)[threadIdx.x + 256 * t];
   if (threadIdx.x < 64) lbox[threadIdx.x] = p.box_row[threadIdx.x];
-  // inclusive scan of ceil(count / 256) over the rungs, as in the compacted sweep
+  // inclusive scan of ceil(count / 256) over the rungs, as in the compacted sweep; the counts stay in LDS for the tile loop
   const int nrung = p.nrung, per = (nrung + 255) / 256;
+  int* pcn = tpre + nrung;    // [nrung] the rungs' list lengths
   int loc = 0;
   for (int k = 0; k < per; ++k) {
     const int r = threadIdx.x * per + k;
-    if (r < nrung) { loc += (p.pcnt[p.rung0 + r] + 255) >> 8; tpre[r] = loc; }
+    if (r < nrung) { const int n = p.pcnt[p.rung0 + r]; pcn[r] = n; loc += (n + 255) >> 8; tpre[r] = loc; }
   }
-  int* tsum = tpre + nrung;   // [257]
+  int* tsum = pcn + nrung;    // [257]
   tsum[threadIdx.x] = loc;
   __syncthreads();
   if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = tsum[t]; tsum[t] = run; run += v; } tsum[256] = run; }
@@ -73,72 +99,130 @@ __global__ __launch_bounds__(256) void box_prefilter_kernel(const BoxPre p) {
   const int ntiles = tsum[256];
   const bp_d2* box = reinterpret_cast<const bp_d2*>(lbox) + q;   // lo piece t at 4t, hi piece t at 16 + 4t (row layout)
   const int wmask = p.labelled ? 0xFFFF : -1;
-  unsigned int seen = 0, settled = 0;   // (wave-uniform)
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    int lo = 0, hi = nrung - 1;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (tpre[mid] > tile) hi = mid; else lo = mid + 1; }
-    const int r = __builtin_amdgcn_readfirstlane(lo);
-    const int kb = tile - (r ? tpre[r - 1] : 0);
-    const int rl = p.rung0 + r, rg = p.r0 + rl;
-    const int start = (kb * 4 + wave) * 64, cnt = p.pcnt[rl];
-    if (start >= cnt) continue;   // (only wave-level work below)
-    const int nact = cnt - start < 64 ? cnt - start : 64;
-    const size_t lbase = (size_t)rl * p.W;
-    // lanes past the list shadow its last entry and write nothing
-    const int mine = p.pidx[lbase + start + (l < nact ? l : nact - 1)];
-    const int c = (int)lbase + (mine & wmask);
-    const double ll = p.ll[c], lp = p.lp[c];
-    const double beta = as_c(p.beta)[rg];
+  const int G = (int)gridDim.x;
+
+  // the wave's slice of a tile (wave-uniform; nact == 0: nothing to load, nothing to do) ...
+  auto slice_of = [&](int tile) {
+    PrefilterSlice s = prefilter_slice(tpre, pcn, nrung, ntiles, tile, wave);
+    s.r = __builtin_amdgcn_readfirstlane(s.r);
+    s.start = __builtin_amdgcn_readfirstlane(s.start);
+    s.nact = __builtin_amdgcn_readfirstlane(s.nact);
+    return s;
+  };
+  // ... its list entries: lanes past the list shadow its last entry and write nothing
+  auto load_entry = [&](const PrefilterSlice& s) {
+    if (s.nact == 0) return 0;
+    return p.pidx[(size_t)(p.rung0 + s.r) * p.W + s.start + (l < s.nact ? l : s.nact - 1)];
+  };
+  // ... and what the entries name
+  auto load_rows = [&](const PrefilterSlice& s, int mine, BpRows& R) {
+    if (s.nact == 0) return;
+    const int rl = p.rung0 + s.r;
+    const int c = (int)((size_t)rl * p.W) + (mine & wmask);
+    R.ll = p.ll[c]; R.lp = p.lp[c];
+    R.beta = as_c(p.beta)[p.r0 + rl];
     const double* timg = p.prop_tiles + (size_t)rl * (16 * 64) + l;
-    double ta[4];
 #pragma unroll
-    for (int sl = 0; sl < 4; ++sl) ta[sl] = timg[((0 * 4 + sl) * 2 + 0) * 64];
-    const bp_d2 lo0 = box[0], lo1 = box[4], hi0 = box[16], hi1 = box[20];
-    bp_d2 v0[4], v1[4];
-    int wk[4];
+    for (int sl = 0; sl < 4; ++sl) R.ta[sl] = timg[((0 * 4 + sl) * 2 + 0) * 64];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int e = __shfl(mine, 16 * g + j, 64);
       const int slot = p.labelled ? (int)((unsigned int)e >> 16) : rl;
-      wk[g] = e & wmask;
-      const bp_d2* rp = reinterpret_cast<const bp_d2*>(p.x + ((size_t)slot * p.W + wk[g]) * 32) + q;
-      v0[g] = rp[0];
-      v1[g] = rp[4];
+      const bp_d2* rp = reinterpret_cast<const bp_d2*>(p.x + ((size_t)slot * p.W + (e & wmask)) * 32) + q;
+      R.v0[g] = rp[0];
+      R.v1[g] = rp[4];
     }
+  };
+
+  constexpr bool RA = PTM_BP_ROWS_AHEAD != 0;
+  constexpr int EA = RA ? 2 : 1;   // how many tiles before its draw a list entry is asked for
+  PrefilterSlice sl[EA + 1] = {};   // sl[k], m[k]: slice and entries of tile + k G
+  int m[EA + 1] = {};
+  BpRows R[2] = {};                 // R[0]: the current tile's, R[1]: the next tile's (RA)
+#pragma unroll
+  for (int k = 0; k < EA; ++k) { sl[k] = slice_of((int)blockIdx.x + k * G); m[k] = load_entry(sl[k]); }
+  if (RA) load_rows(sl[0], m[0], R[0]);
+  // the append whose place in the sweep's list is still on its way: survivors pbits of the entries pmine, rung list at plbase
+  uint64_t pbits = 0;
+  int pmine = 0, pbase = 0;
+  size_t plbase = 0;
+  auto flush = [&]() {
+    if (pbits == 0) return;
+    const int base = __builtin_amdgcn_readfirstlane(pbase);
+    if ((pbits >> l) & 1ull) p.cidx[plbase + base + __builtin_popcountll(pbits & ((1ull << l) - 1ull))] = pmine;
+    pbits = 0;
+  };
+  // The memory counter retires in order, and the compiler can only wait for "everything up to" a load.  So the one wait of a tile
+  // stands where everything outstanding is old: behind the draw (PTM_BP_ARRIVED) -- the loads asked at the tile's top and the
+  // previous tile's append have had the whole draw to arrive -- and in front of this tile's own atomics, which nobody waits for
+  // before the same place of the next tile.  (s_waitcnt vmcnt(0), the other counters untouched.)
+#define PTM_BP_ARRIVED() __builtin_amdgcn_s_waitcnt(0x0F70)
+  PTM_BP_ARRIVED();   // (the loop starts with nothing on its way but what it asks for itself)
+  unsigned int seen = 0, settled = 0;   // (wave-uniform)
+  for (int tile = blockIdx.x; tile < ntiles; tile += G) {
+    // ask ahead: a tile past the end and an empty slice load nothing
+    sl[EA] = slice_of(tile + EA * G);
+    m[EA] = load_entry(sl[EA]);
+    if (RA) load_rows(sl[1], m[1], R[1]);
+    else load_rows(sl[0], m[0], R[0]);
+    PTM_BP_STAGE();
+    const PrefilterSlice s = sl[0];   // (wave-uniform: only wave-level branches below)
+    const int mine = m[0], nact = s.nact;
+    const int rl = p.rung0 + s.r, rg = p.r0 + rl;
+    const size_t lbase = (size_t)rl * p.W;
+    const BpRows& T = R[0];
     uint64_t inbox = 0;   // bit 16 g + j: chain (g, j) is inside the box in dimensions 0..15
+    if (nact) {
+      const bp_d2 lo0 = box[0], lo1 = box[4], hi0 = box[16], hi1 = box[20];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const uint32_t stream = (uint32_t)(wk[g] + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg;
-      const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + q));
-      double z[4];
-      boxmuller(o.v0, o.v1, (const double*)bp_lds, z[0], z[1]);
-      boxmuller(o.v2, o.v3, (const double*)bp_lds, z[2], z[3]);
-      bp_d4 acc = bp_d4{0.0, 0.0, 0.0, 0.0};
+      for (int g = 0; g < 4; ++g) {
+        const int wk = __shfl(mine, 16 * g + j, 64) & wmask;
+        const uint32_t stream = (uint32_t)(wk + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg;
+        const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + q));
+        double z[4];
+        boxmuller(o.v0, o.v1, (const double*)bp_lds, z[0], z[1]);
+        boxmuller(o.v2, o.v3, (const double*)bp_lds, z[2], z[3]);
+        bp_d4 acc = bp_d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int sl = 0; sl < 4; ++sl) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[sl], z[sl], acc, 0, 0, 0);
-      const double x0 = v0[g].x + acc[0], x1 = v0[g].y + acc[1], x2 = v1[g].x + acc[2], x3 = v1[g].y + acc[3];
-      const bool ok = !(x0 < lo0.x) & !(x0 > hi0.x) & !(x1 < lo0.y) & !(x1 > hi0.y) & !(x2 < lo1.x) & !(x2 > hi1.x) & !(x3 < lo1.y) & !(x3 > hi1.y);
-      uint64_t b = __builtin_amdgcn_ballot_w64(ok);
-      b &= b >> 32;
-      b &= b >> 16;   // bit jj: all four lanes (q, jj) of chain (g, jj) are inside
-      inbox |= (b & 0xFFFFull) << (16 * g);
+        for (int k = 0; k < 4; ++k) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(T.ta[k], z[k], acc, 0, 0, 0);
+        const double x0 = T.v0[g].x + acc[0], x1 = T.v0[g].y + acc[1], x2 = T.v1[g].x + acc[2], x3 = T.v1[g].y + acc[3];
+        const bool ok = !(x0 < lo0.x) & !(x0 > hi0.x) & !(x1 < lo0.y) & !(x1 > hi0.y) & !(x2 < lo1.x) & !(x2 > hi1.x) & !(x3 < lo1.y) & !(x3 > hi1.y);
+        uint64_t b = __builtin_amdgcn_ballot_w64(ok);
+        b &= b >> 32;
+        b &= b >> 16;   // bit jj: all four lanes (q, jj) of chain (g, jj) are inside
+        inbox |= (b & 0xFFFFull) << (16 * g);
+      }
     }
-    // chain l of the wave: the sweep's cur_lpost, rounded as the sweep rounds it
-    const double cur_lpost = lp + beta * ll;
-    const bool live = l < nact;
-    const bool finite = __builtin_fabs(cur_lpost) < __builtin_inf();   // (false for NaN)
-    const bool settle = live && finite && ((inbox >> l) & 1ull) == 0;
-    if (settle) p.ntries[c] += 1;
-    const bool keep = live && !settle;
-    const uint64_t kbits = __builtin_amdgcn_ballot_w64(keep);
-    const int nk = __builtin_popcountll(kbits);
-    int base = 0;
-    if (l == 0 && nk) base = atomicAdd(&p.ccnt[rl], nk);
-    base = __builtin_amdgcn_readfirstlane(base);
-    if (keep) p.cidx[lbase + base + __builtin_popcountll(kbits & ((1ull << l) - 1ull))] = mine;
-    seen += (unsigned int)nact;
-    settled += (unsigned int)(nact - nk);
+    PTM_BP_STAGE();
+    PTM_BP_ARRIVED();
+    if (nact) {
+      // chain l of the wave: the sweep's cur_lpost, rounded as the sweep rounds it
+      const int c = (int)lbase + (mine & wmask);
+      const double cur_lpost = T.lp + T.beta * T.ll;
+      const bool live = l < nact;
+      const bool finite = __builtin_fabs(cur_lpost) < __builtin_inf();   // (false for NaN)
+      const bool settle = live && finite && ((inbox >> l) & 1ull) == 0;
+      const bool keep = live && !settle;
+      const uint64_t kbits = __builtin_amdgcn_ballot_w64(keep);
+      const int nk = __builtin_popcountll(kbits);
+      flush();   // the wave's previous append: its place has arrived
+      // (this kernel's only writer of the chain's counter: the add needs no return and no wait)
+      if (settle) (void)__hip_atomic_fetch_add(&p.ntries[c], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (nk) {
+        pbits = kbits; pmine = mine; plbase = lbase;
+        // the rung through a lane-wise move: on a wave-uniform address the compiler rewrites the add for the whole wave and
+        // broadcasts its return on the spot, which is the wait this append is built to avoid
+        const int rlv = __builtin_amdgcn_mov_dpp(rl, 0xE4, 0xF, 0xF, true);
+        if (l == 0) pbase = atomicAdd(&p.ccnt[rlv], nk);
+      }
+      seen += (unsigned int)nact;
+      settled += (unsigned int)(nact - nk);
+    }
+#pragma unroll
+    for (int k = 0; k < EA; ++k) { sl[k] = sl[k + 1]; m[k] = m[k + 1]; }
+    if (RA) R[0] = R[1];
   }
+  flush();
   if (l == 0 && seen) {
     atomicAdd(p.counts, (unsigned long long)seen);
     if (settled) atomicAdd(p.counts + 1, (unsigned long long)settled);

@@ -1618,6 +1618,8 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
         HIPCHK(hipGetDevice(&dev));
         HIPCHK(hipGetDeviceProperties(&pr, dev));
         e->pf_grid = per_cu * (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
+        const int cap = sweep_env().prefilter_grid;   // PTM_PREFILTER_GRID: many tiles per block on a small population (tests)
+        if (cap > 0 && cap < e->pf_grid) e->pf_grid = cap;
       }
       const long long tiles = (long long)nr * ((e->W + 255) / 256);
       hipLaunchKernelGGL(box_prefilter_kernel, dim3((unsigned)(tiles < e->pf_grid ? tiles : e->pf_grid)), dim3(256), lds, e->stream, b);

@@ -30,17 +30,21 @@ struct SweepFacts {
 // the environment's say: PTM_FORCE_VALU set, non-empty and not "0" keeps every workload off the matrix cores and off the lanes
 // kernel's population rules (A/B measurements, tests); PTM_COMPACT=0 switches the compacted sweep off; PTM_BOX_PREFILTER=0 switches
 // the box pre-pass (ptm_box_prefilter.hpp) off, =1 gives it every rung of a sweep it is eligible for, unset: the estimate decides
-// (prefilter_flag below).  Read once per process.
+// (prefilter_flag below); PTM_PREFILTER_GRID=n (n >= 1) caps the pre-pass's grid at n blocks, so that a small population walks many
+// tiles per block as a big one does (tests; the results do not depend on it).  Read once per process.
 struct SweepEnv {
   bool force_valu, compact_ok;
-  int prefilter;   // 0: the estimate decides, 1: every eligible rung, -1: off
+  int prefilter;        // 0: the estimate decides, 1: every eligible rung, -1: off
+  int prefilter_grid;   // 0: the blocks the device holds at once, n >= 1: at most n blocks
 };
 inline const SweepEnv& sweep_env() {
   static const SweepEnv v = [] {
     const char* f = getenv("PTM_FORCE_VALU");
     const char* c = getenv("PTM_COMPACT");
     const char* b = getenv("PTM_BOX_PREFILTER");
-    return SweepEnv{f && *f && *f != '0', !(c && *c == '0'), (b && *b) ? (*b == '0' ? -1 : 1) : 0};
+    const char* g = getenv("PTM_PREFILTER_GRID");
+    const long gn = (g && *g) ? strtol(g, nullptr, 10) : 0;
+    return SweepEnv{f && *f && *f != '0', !(c && *c == '0'), (b && *b) ? (*b == '0' ? -1 : 1) : 0, gn >= 1 ? (int)(gn < (1 << 20) ? gn : (1 << 20)) : 0};
   }();
   return v;
 }
@@ -131,9 +135,11 @@ inline SweepPlan plan_sweep(const SweepFacts& f, const SweepEnv& env) {
 // flag changes which kernel does the work and nothing in the results.
 constexpr int PREFILTER_DIMS = 16;
 #ifndef PTM_PREFILTER_THRESHOLD
-#define PTM_PREFILTER_THRESHOLD 0.70   // measured break-even 0.50-0.57 (what a pre-pass chain costs of a sweep chain) + a margin: on the rungs
-                                       // between cold and hot the state is not yet uniform in the box and the estimate reads high
-                                       // (0.60 estimated where a model of the sampler counts 0.22), at 0.70 it is within 0.1
+#define PTM_PREFILTER_THRESHOLD 0.70   // measured break-even 0.40-0.43 with the pipelined pass (what a pre-pass chain costs of a sweep chain, DESIGN 3.1;
+                                       // 0.50-0.57 before it) + a margin: on the rungs between cold and hot the state is not yet uniform in
+                                       // the box and the estimate reads high (0.60 estimated where a model of the sampler counts 0.22), at
+                                       // 0.70 it is within 0.1.  Re-measured with the cheaper pass: 0.50 / 0.57 / 0.63 / 0.70 give the same
+                                       // step within the noise (the rungs in between sit at the break-even): it stays
 #endif
 // the standard deviations of the first 16 coordinates of a rung's proposal: sigma_d^2 = sum_k T[d][k]^2 (factor: row-major D x D, or D sigmas)
 inline void prefilter_sigmas(bool diag, const double* factor, int D, double* sigma) {
@@ -165,6 +171,31 @@ inline bool prefilter_flag(const double* sigma, const double* width, int nd, int
   if (env_prefilter < 0) return false;
   if (env_prefilter > 0) return true;
   return prefilter_out_share(sigma, width, nd) > PTM_PREFILTER_THRESHOLD;
+}
+
+// The pre-pass's tiles (256 listed walkers of one rung, four waves of 64) are enumerated rung by rung.  tpre[0..nrung): the inclusive
+// prefix of the rungs' tile counts ceil(cnt[r] / 256), cnt[0..nrung): the rungs' list lengths, ntiles = tpre[nrung - 1].  Which rung
+// and which slice of its list wave `wave` of tile `tile` works on: a binary search for the first rung whose prefix exceeds the tile
+// (an empty rung never does), the tile's number kb within the rung, the first entry of the wave's 64 and how many of them exist.
+// nact == 0: nothing to do -- the tile is past the end, or the wave's slice of a rung's last tile is empty.  The kernel asks this
+// one function for the tile it works on and for every tile it loads ahead (ptm_box_prefilter.hpp), so the two cannot disagree.
+#ifdef __HIPCC__
+#define PTM_PLAN_HD __host__ __device__
+#else
+#define PTM_PLAN_HD
+#endif
+struct PrefilterSlice { int r, kb, start, nact; };
+PTM_PLAN_HD inline PrefilterSlice prefilter_slice(const int* tpre, const int* cnt, int nrung, int ntiles, int tile, int wave) {
+  PrefilterSlice s = {0, 0, 0, 0};
+  if (tile < 0 || tile >= ntiles) return s;
+  int lo = 0, hi = nrung - 1;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (tpre[mid] > tile) hi = mid; else lo = mid + 1; }
+  s.r = lo;
+  s.kb = tile - (lo ? tpre[lo - 1] : 0);
+  s.start = (s.kb * 4 + wave) * 64;
+  const int left = cnt[lo] - s.start;
+  s.nact = left <= 0 ? 0 : (left < 64 ? left : 64);
+  return s;
 }
 
 // the kernel's name as rocprofv3 prints it (sweep_kernel without its last, defaulted argument unless that is set); returns snprintf's count
