@@ -65,45 +65,39 @@ struct BpRows {
   double ll, lp, beta, ta[4];
 };
 
-// dynamic LDS of a launch over nrung rungs: tables | box | the rungs' tile prefix, their list lengths and the scan's chunk totals
-inline size_t box_prefilter_lds(int nrung) { return (size_t)(BM_TABLE_DOUBLES + 64) * sizeof(double) + (2 * (size_t)nrung + 260) * sizeof(int); }
-
 __global__ __launch_bounds__(256, PTM_BP_ROWS_AHEAD ? 3 : 4) void box_prefilter_kernel(const BoxPre p) {
   extern __shared__ __attribute__((aligned(16))) double bp_lds[];
-  double* lbox = bp_lds + BM_TABLE_DOUBLES;
-  int* tpre = reinterpret_cast<int*>(lbox + 64);   // [nrung] inclusive prefix of the rungs' 256-walker tiles
+  const int nrung = p.nrung, per = (nrung + 255) / 256;
+  const BoxPreLds L(bp_lds, nrung);
   const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, q = l >> 4, j = l & 15;
 #pragma unroll
   for (int t = 0; t < BM_TABLE_DOUBLES / 512; ++t)
-    reinterpret_cast<bm_d2*>(bp_lds)[threadIdx.x + 256 * t] = reinterpret_cast<const bm_d2*>(BM_TABLE)[threadIdx.x + 256 * t];
-  if (threadIdx.x < 64) lbox[threadIdx.x] = p.box_row[threadIdx.x];
+    reinterpret_cast<bm_d2*>(L.bm)[threadIdx.x + 256 * t] = reinterpret_cast<const bm_d2*>(BM_TABLE)[threadIdx.x + 256 * t];
+  if (threadIdx.x < 64) L.lbox[threadIdx.x] = p.box_row[threadIdx.x];
   // inclusive scan of ceil(count / 256) over the rungs, as in the compacted sweep; the counts stay in LDS for the tile loop
-  const int nrung = p.nrung, per = (nrung + 255) / 256;
-  int* pcn = tpre + nrung;    // [nrung] the rungs' list lengths
   int loc = 0;
   for (int k = 0; k < per; ++k) {
     const int r = threadIdx.x * per + k;
-    if (r < nrung) { const int n = p.pcnt[p.rung0 + r]; pcn[r] = n; loc += (n + 255) >> 8; tpre[r] = loc; }
+    if (r < nrung) { const int n = p.pcnt[p.rung0 + r]; L.pcn[r] = n; loc += (n + 255) >> 8; L.tpre[r] = loc; }
   }
-  int* tsum = pcn + nrung;    // [257]
-  tsum[threadIdx.x] = loc;
+  L.tsum[threadIdx.x] = loc;
   __syncthreads();
-  if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = tsum[t]; tsum[t] = run; run += v; } tsum[256] = run; }
+  if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = L.tsum[t]; L.tsum[t] = run; run += v; } L.tsum[256] = run; }
   __syncthreads();
-  const int off = tsum[threadIdx.x];
+  const int off = L.tsum[threadIdx.x];
   for (int k = 0; k < per; ++k) {
     const int r = threadIdx.x * per + k;
-    if (r < nrung) tpre[r] += off;
+    if (r < nrung) L.tpre[r] += off;
   }
   __syncthreads();
-  const int ntiles = tsum[256];
-  const bp_d2* box = reinterpret_cast<const bp_d2*>(lbox) + q;   // lo piece t at 4t, hi piece t at 16 + 4t (row layout)
+  const int ntiles = L.tsum[256];
+  const bp_d2* box = reinterpret_cast<const bp_d2*>(L.lbox) + q;   // lo piece t at 4t, hi piece t at 16 + 4t (row layout)
   const int wmask = p.labelled ? 0xFFFF : -1;
   const int G = (int)gridDim.x;
 
   // the wave's slice of a tile (wave-uniform; nact == 0: nothing to load, nothing to do) ...
   auto slice_of = [&](int tile) {
-    PrefilterSlice s = prefilter_slice(tpre, pcn, nrung, ntiles, tile, wave);
+    PrefilterSlice s = prefilter_slice(L.tpre, L.pcn, nrung, ntiles, tile, wave);
     s.r = __builtin_amdgcn_readfirstlane(s.r);
     s.start = __builtin_amdgcn_readfirstlane(s.start);
     s.nact = __builtin_amdgcn_readfirstlane(s.nact);
@@ -180,8 +174,8 @@ __global__ __launch_bounds__(256, PTM_BP_ROWS_AHEAD ? 3 : 4) void box_prefilter_
         const uint32_t stream = (uint32_t)(wk + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg;
         const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + q));
         double z[4];
-        boxmuller(o.v0, o.v1, (const double*)bp_lds, z[0], z[1]);
-        boxmuller(o.v2, o.v3, (const double*)bp_lds, z[2], z[3]);
+        boxmuller(o.v0, o.v1, L.bm, z[0], z[1]);
+        boxmuller(o.v2, o.v3, L.bm, z[2], z[3]);
         bp_d4 acc = bp_d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(T.ta[k], z[k], acc, 0, 0, 0);

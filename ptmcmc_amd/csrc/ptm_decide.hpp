@@ -101,13 +101,8 @@ __device__ __forceinline__ int xcd_walker(int b, int W) {
 }
 
 constexpr int PTM_LOG_RING = 16;   // steps of candidate logs kept before they are folded into the swap counters
-constexpr int MVCAP = 256;  // rows one ladder can move per step on the register path (move_kernel)
 typedef double d2_t __attribute__((ext_vector_type(2)));  // (HIP's double2 struct does not stay in registers as an array)
 
-// do perm / inv / the move list share the space of an evolving ladder's trial operands (decide_body's carve)?  Host and device agree.
-__host__ __device__ inline bool decide_aliased(int ms, int WN, bool evolve) {
-  return evolve && (size_t)2 * ((WN + 3) & ~3) * 2 + (size_t)2 * MVCAP * 4 <= (size_t)4 * ((ms + 3) & ~3) * 8;
-}
 // atomic minimum of a 16-bit LDS entry (ds_cmpst on the word that holds it; contention: two picks of one rung pair, rare)
 __device__ __forceinline__ void lds_min_u16(unsigned short* a, int idx, unsigned int v) {
   unsigned int* wd = reinterpret_cast<unsigned int*>(a) + (idx >> 1);
@@ -166,69 +161,18 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   // window of rungs whose llike this shard knows: its own, one below, H above
   const int wlo = p.ll_all ? 0 : p.r0 - (p.ll_below ? 1 : 0), whi = p.ll_all ? Nt - 1 : r1 - 1 + p.H;
   const int WN = whi - wlo + 1;
-  // LDS carve (mirrored by decide_lds_bytes on the host; all offsets multiples of 8)
-  double* llc_ = reinterpret_cast<double*>(smem);                             // [WN]  llike view of the touched rungs
-  unsigned short* first = reinterpret_cast<unsigned short*>(llc_ + WN);       // [Nt]  first pick of each rung value (NONE: not picked)
-  int* cand = reinterpret_cast<int*>(first + ((Nt + 3) & ~3));                // [ms]  rung of the pick / -2 none or dropped
-  uint32_t* ua = reinterpret_cast<uint32_t*>(cand + ((ms + 1) & ~1));         // [ms]  accept uniform of the pick (raw)
-  int* cnt = reinterpret_cast<int*>(ua + ((ms + 1) & ~1));                    // [4]   list length, move count, ambiguous trial seen, pries
-  // perm [WN] (source rung of the row now at a rung), inv [WN] (its inverse) and the move list [2][MVCAP] are not needed before
-  // the trials of an evolving ladder are over, whose operand arrays (tlu .. tllb below) are dead by then: they share that space
-  // when it is big enough (decide_aliased) -- 6 KB less per block, a fifth block per CU for 1024-rung ladders
-  const bool al = decide_aliased(ms, WN, p.evolve_rate > 0);
-  const int WNp = (WN + 3) & ~3;
-  unsigned short* perm_ = reinterpret_cast<unsigned short*>(cnt + 4);         // [WN]
-  unsigned short* inv_ = perm_ + (al ? 0 : WNp);                              // [WN]
-  unsigned short* list = inv_ + (al ? 0 : WNp);                               // [ms]  surviving picks that are ours
-  unsigned short* midk = list + ((ms + 3) & ~3);                              // [ms]  (by pick) row the pick's lower rung held before a later pick
-                                                                              //       on the pair below exchanged it again
-  unsigned char* alive = reinterpret_cast<unsigned char*>(midk + ((ms + 3) & ~3));  // [ms] 0 dropped, 1 survives and is
-                                                                                    //      ours, 2 survives, not ours
-  unsigned char* accf = alive + ((ms + 7) & ~7);                              // [ms]
+  const DecideLds L(smem, Nt, ms, WN, p.evolve_rate > 0, p.beta_add != nullptr, CUT);   // (ptm_lds_layout.hpp)
   // The block applies the ladder's row moves itself (below) from a list kept in LDS, up to FCAP rows (16 rounds of one
   // row per 16-lane group); a longer list (64-thread form only) goes to move_kernel through global memory.
   constexpr int FCAP = DECIDE_THREADS < MVCAP ? DECIDE_THREADS : MVCAP;   // (the list itself holds MVCAP moves)
-  int* lmv = reinterpret_cast<int*>(accf + ((ms + 7) & ~7));                  // [2][MVCAP]
-  // evolving ladders only: gaps (in the end their local prefix sums), chunk totals / offsets, {normaliser, pries}, and the
-  // surviving picks in PICK ORDER (position t): what the chain of dependent trials needs, laid out for one lane to stream
-  const int msp = (ms + 3) & ~3;
-  double* gap = reinterpret_cast<double*>(lmv + (al ? 0 : 2 * MVCAP));        // [Nt]
-  double* ct = gap + Nt;                                                      // [2][(Nt + 31) / 32]
-  double* ev = ct + 2 * ((Nt + 31) / 32);                                     // [2]
-  double* tlu = ev + 2;                                                       // [ms]  log of the pick's accept uniform
-  double* tgap = tlu + msp;                                                   // [ms]  the pick's gap (a pair is tried once: never pried before)
-  double* tlla = tgap + msp;                                                  // [ms]  llike of the lower rung (nothing earlier can change it)
-  double* tllb = tlla + msp;                                                  // [ms]  llike of the upper rung (an earlier pick above may change it)
-  unsigned short* olist = reinterpret_cast<unsigned short*>(tllb + msp);      // [ms]  position -> pick
-  unsigned short* opos = olist + msp;                                         // [ms]  pick -> position
-  unsigned short* ti = opos + msp;                                            // [ms]  the pick's lower rung
-  short* tdep = reinterpret_cast<short*>(ti + msp);                           // [ms]  position of the (later) pick on the pair below, or -1
-  unsigned char* tacc = reinterpret_cast<unsigned char*>(tdep + msp);         // [ms]  accepted
-  // ... with history / MAP tracking on top (an add_state of the phase sees the temperature BETWEEN two pries of the step):
-  double* p0 = reinterpret_cast<double*>(tacc + ((ms + 7) & ~7));             // [max(Nt, MVCAP)]  prefix sums of the step's first gaps
-  double* tS = p0 + (Nt > MVCAP ? Nt : MVCAP);                                // [ms]  sum of the gaps the pick saw (0: nothing pried yet)
-  double* tdl = tS + msp;                                                     // [ms]  what the pick added to its gap
-  double* bklo = tdl + msp;                                                   // [ms]  (by pick) temperature of the pick's lower rung then
-  double* tbl = bklo + msp;                                                   // [ms]  stored temperature of the pick's lower rung (asked for with the other operands:
-  double* tbh = tbl + msp;                                                    // [ms]  ... and of its upper rung     a trip to memory off the phase's critical path)
-  double* gb = p0;                                                            // [MVCAP] temperature for a HIST / MAP move (p0 is done by then)
-  // ... with a posterior-ordering cut (evolve_cut >= 0; the carve above is then taken as with history): the current llike and
-  // lprior of EVERY rung, exchanged as the picks are decided
-  double* llv = tbh + msp;                                                    // [Nt]
-  double* lpv = llv + Nt;                                                     // [Nt]
-  if (al) {
-    inv_ = reinterpret_cast<unsigned short*>(tlu);
-    perm_ = inv_ + WNp;
-    lmv = reinterpret_cast<int*>(perm_ + WNp);
-  }
-  double* llc = llc_ - wlo;                // indexed by global rung
-  unsigned short* perm = perm_ - wlo;
-  unsigned short* inv = inv_ - wlo;
+  double* llc = L.llc - wlo;                // indexed by global rung
+  unsigned short* perm = L.perm - wlo;
+  unsigned short* inv = L.inv - wlo;
   cdp beta = as_c(p.beta);
 
   if (p.redo_only && !p.redo_flag[w]) return;          // the second pass works for the ladders the halo pass left alone
-  for (int i = lane; i < ((Nt + 3) & ~3) / 2; i += DECIDE_THREADS) reinterpret_cast<uint32_t*>(first)[i] = 0xffffffffu;
-  if (lane == 0) { cnt[0] = 0; cnt[1] = 0; p.arr_below[w] = -1; p.arr_above[w] = -1; }
+  for (int i = lane; i < ((Nt + 3) & ~3) / 2; i += DECIDE_THREADS) reinterpret_cast<uint32_t*>(L.first)[i] = 0xffffffffu;
+  if (lane == 0) { L.cnt[0] = 0; L.cnt[1] = 0; p.arr_below[w] = -1; p.arr_above[w] = -1; }
   __syncthreads();
   // -- candidate draws (chain.cc:1410-1416): block k of the ladder stream gives {u_try, u_pick, u_accept}
   const uint64_t try_below = u01_below_bound(p.thresh);
@@ -236,11 +180,11 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
     const u32x4 o = draw_block(p.seed, TAG_PT, (uint32_t)(w + p.w_off), step, (uint32_t)k);
     int n = -2;
     if (Nt > 1 && (uint64_t)o.v0 < try_below) n = u01_times(o.v1, Nt - 1);   // u01(v0) < thresh, (int)(u01(v1) (Nt - 1)): ptm_device_math.hpp
-    cand[k] = n;
-    ua[k] = o.v2;  // the accept uniform's slot is reserved whether or not it is needed (cf. Q5)
-    alive[k] = 0;
-    accf[k] = 0;
-    if (n >= 0) lds_min_u16(first, n, (unsigned int)k);
+    L.cand[k] = n;
+    L.ua[k] = o.v2;  // the accept uniform's slot is reserved whether or not it is needed (cf. Q5)
+    L.alive[k] = 0;
+    L.accf[k] = 0;
+    if (n >= 0) lds_min_u16(L.first, n, (unsigned int)k);
   }
   const bool evolve = p.evolve_rate > 0 && Nt > 1;
   const bool evb = evolve && p.beta_add != nullptr;   // history / MAP tracking of evolving ladders
@@ -249,29 +193,29 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   if (evolve) {
     const double* bw = p.beta_w + (size_t)w * Nt;
     blast = bw[Nt - 1];
-    for (int k = lane; k < Nt - 1; k += DECIDE_THREADS) gap[k] = bw[k] - bw[k + 1];   // chain.cc:1816
+    for (int k = lane; k < Nt - 1; k += DECIDE_THREADS) L.gap[k] = bw[k] - bw[k + 1];   // chain.cc:1816
   }
   __syncthreads();
   // -- filter (1): run heads walk their run upwards
   for (int k = lane; k < ms; k += DECIDE_THREADS) {
-    const int n = cand[k];
-    if (n < 0 || first[n] != k) continue;                      // repeated rung value: dropped
-    if (n > 0 && first[n - 1] != NONE) continue;               // not a run head
+    const int n = L.cand[k];
+    if (n < 0 || L.first[n] != k) continue;                      // repeated rung value: dropped
+    if (n > 0 && L.first[n - 1] != NONE) continue;               // not a run head
     bool a = true;
     for (int m = n;; ++m) {
-      alive[first[m]] = a ? 1 : 0;
-      if (m + 1 > Nt - 2 || first[m + 1] == NONE) break;
-      a = !(a && first[m] < first[m + 1]);
+      L.alive[L.first[m]] = a ? 1 : 0;
+      if (m + 1 > Nt - 2 || L.first[m + 1] == NONE) break;
+      a = !(a && L.first[m] < L.first[m + 1]);
     }
   }
   __syncthreads();
-#define PTM_ALIVE_RUNG(r) ((r) >= 0 && (r) <= Nt - 2 && first[(r)] != NONE && alive[first[(r)]])
+#define PTM_ALIVE_RUNG(r) ((r) >= 0 && (r) <= Nt - 2 && L.first[(r)] != NONE && L.alive[L.first[(r)]])
   if (p.redo_only) {
     if (lane == 0) p.redo_flag[w] = 0;
   } else if (p.shard_ends && !p.ll_all) {
     // is some shard of this ladder blind this step?  Shard k (ending at rung B) sees the llikes of h = min(halo, size of shard
     // k + 1) rungs above it; it cannot decide its top pairs iff the picks B - 1 .. B - 1 + h all survive (see the trials below)
-    if (lane == 0) cnt[2] = 0;
+    if (lane == 0) L.cnt[2] = 0;
     __syncthreads();
     for (int k = lane; k + 1 < p.nshards; k += DECIDE_THREADS) {
       const int B = p.shard_ends[k];
@@ -279,10 +223,10 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       const int h = p.halo_nominal < above ? p.halo_nominal : above;
       bool all = true;
       for (int t = 0; t <= h && all; ++t) all = PTM_ALIVE_RUNG(B - 1 + t);
-      if (all) cnt[2] = 1;
+      if (all) L.cnt[2] = 1;
     }
     __syncthreads();
-    if (cnt[2]) {                                      // every shard leaves this ladder to the gathered pass
+    if (L.cnt[2]) {                                      // every shard leaves this ladder to the gathered pass
       if (lane == 0) { p.redo_flag[w] = 1; atomicAdd(p.redo_count, 1); }
       for (int k = lane; k < ms; k += DECIDE_THREADS) swap_log[(size_t)w * ms + k] = -2;   // (nothing of this ladder is logged by this pass)
       return;
@@ -290,26 +234,26 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   }
   // -- compaction: the surviving picks whose pair lies inside the window
   for (int k = lane; k < ms; k += DECIDE_THREADS) {
-    const int n = cand[k];
+    const int n = L.cand[k];
     if (n < 0) continue;
-    if (!alive[k]) { cand[k] = -2; continue; }
-    if (n < wlo || n + 1 > whi) { alive[k] = 2; continue; }     // survives, but is not this shard's to decide
-    list[atomicAdd(&cnt[0], 1)] = (unsigned short)k;
+    if (!L.alive[k]) { L.cand[k] = -2; continue; }
+    if (n < wlo || n + 1 > whi) { L.alive[k] = 2; continue; }     // survives, but is not this shard's to decide
+    L.list[atomicAdd(&L.cnt[0], 1)] = (unsigned short)k;
   }
   __syncthreads();
-  const int nl = cnt[0];
+  const int nl = L.cnt[0];
   // -- working copy of the touched rungs (gather_llikes, chain.cc:1434); each touched rung is set up by exactly one
   //    lane: the pick whose lower rung it is, or -- for the top of a run -- the pick just below it
   for (int j = lane; j < nl; j += DECIDE_THREADS) {
-    const int n = cand[list[j]];
+    const int n = L.cand[L.list[j]];
     const bool top = !PTM_ALIVE_RUNG(n + 1) || n + 2 > whi;    // (an alive pick above that lies outside the window sets up nothing)
     const double a = win_llike(p, n, w);
     const double b = top ? win_llike(p, n + 1, w) : 0.0;
     llc[n] = a;
-    if (!al) perm[n] = (unsigned short)n;                      // (sharing the trial operands' space: set up after the trials)
+    if (!L.aliased) perm[n] = (unsigned short)n;                      // (sharing the trial operands' space: set up after the trials)
     if (top) {
       llc[n + 1] = b;
-      if (!al) perm[n + 1] = (unsigned short)(n + 1);
+      if (!L.aliased) perm[n + 1] = (unsigned short)(n + 1);
     }
   }
   __syncthreads();
@@ -325,12 +269,12 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       int base = 0;
       for (int k0 = 0; k0 < ms; k0 += 64) {
         const int k = k0 + lane;
-        const bool f = k < ms && alive[k] == 1;
+        const bool f = k < ms && L.alive[k] == 1;
         const unsigned long long m = __ballot(f);
         if (f) {
           const int t = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-          olist[t] = (unsigned short)k;
-          opos[k] = (unsigned short)t;
+          L.olist[t] = (unsigned short)k;
+          L.opos[k] = (unsigned short)t;
         }
         base += __builtin_popcountll(m);
       }
@@ -342,27 +286,27 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       for (int j0 = 0; j0 < 32; j0 += 8) {
         double r8[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const int k = 32 * q + j0 + j; r8[j] = k < Nt - 1 ? gap[k] : 0.0; }
+        for (int j = 0; j < 8; ++j) { const int k = 32 * q + j0 + j; r8[j] = k < Nt - 1 ? L.gap[k] : 0.0; }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int k = 32 * q + j0 + j;
-          if (k < Nt - 1) { if (evb || cutmode) p0[k] = loc; loc = loc + r8[j]; }
+          if (k < Nt - 1) { if (evb || cutmode) L.p0[k] = loc; loc = loc + r8[j]; }
         }
       }
-      ct[q] = loc;
+      L.ct[q] = loc;
     }
     __syncthreads();
     for (int t = lane; t < nl; t += DECIDE_THREADS) {
-      const int k = olist[t];
-      const int i = cand[k];
-      ti[t] = (unsigned short)i;
-      tlu[t] = dlog_u01(ua[k]);
-      tgap[t] = gap[i];
-      tlla[t] = llc[i];
-      tllb[t] = llc[i + 1];
-      tdep[t] = PTM_ALIVE_RUNG(i - 1) ? (short)opos[first[i - 1]] : (short)-1;
-      tacc[t] = 0;
-      if (evb && !cutmode) { const double* bw = p.beta_w + (size_t)w * Nt; tbl[t] = bw[i]; tbh[t] = bw[i + 1]; }
+      const int k = L.olist[t];
+      const int i = L.cand[k];
+      L.ti[t] = (unsigned short)i;
+      L.tlu[t] = dlog_u01(L.ua[k]);
+      L.tgap[t] = L.gap[i];
+      L.tlla[t] = llc[i];
+      L.tllb[t] = llc[i + 1];
+      L.tdep[t] = PTM_ALIVE_RUNG(i - 1) ? (short)L.opos[L.first[i - 1]] : (short)-1;
+      L.tacc[t] = 0;
+      if (evb && !cutmode) { const double* bw = p.beta_w + (size_t)w * Nt; L.tbl[t] = bw[i]; L.tbh[t] = bw[i + 1]; }
     }
     __syncthreads();
     if (cutmode) {
@@ -375,81 +319,81 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       {
         const double* lla = p.ll_all ? p.ll_all : p.ll;   // (a whole-ladder engine's own arrays ARE the whole ladder's)
         const double* lpa = p.ll_all ? p.lp_all : p.lp;
-        for (int r = lane; r < Nt; r += DECIDE_THREADS) { llv[r] = lla[(size_t)r * p.W + w]; lpv[r] = lpa[(size_t)r * p.W + w]; }
+        for (int r = lane; r < Nt; r += DECIDE_THREADS) { L.llv[r] = lla[(size_t)r * p.W + w]; L.lpv[r] = lpa[(size_t)r * p.W + w]; }
       }
       if (lane == 0) {
-        const double S = decide_totals_scan(ct, ct + nch, nch);
-        ev[0] = S; ev[1] = 0.0;
+        const double S = decide_totals_scan(L.ct, L.ct + nch, nch);
+        L.ev[0] = S; L.ev[1] = 0.0;
       }
       __syncthreads();
-      for (int k = lane; k < Nt - 1; k += DECIDE_THREADS) p0[k] = ct[nch + (k >> 5)] + p0[k];
+      for (int k = lane; k < Nt - 1; k += DECIDE_THREADS) L.p0[k] = L.ct[nch + (k >> 5)] + L.p0[k];
       __syncthreads();
       const double c1 = 1 - blast;   // chain.cc:1833
       const double grow = 1.0 + p.evolve_rate;
       for (int t = 0; t < nl; ++t) {
-        const int k = olist[t], i = ti[t];
+        const int k = L.olist[t], i = L.ti[t];
         if (lane == 0) {
-          const double S = ev[0];
-          const bool pried = ev[1] > 0;
+          const double S = L.ev[0];
+          const bool pried = L.ev[1] > 0;
           const double nrm = S / c1;
-          double lla = llv[i];
+          double lla = L.llv[i];
           if (!(lla > -1e200)) lla = -1e200;
-          double llb = llv[i + 1];
+          double llb = L.llv[i + 1];
           if (!(llb > -1e200)) llb = -1e200;
-          const double g = gap[i];
+          const double g = L.gap[i];
           bool acc = true;
           if (pried) {
             const double tt = (g * c1) * (llb - lla);
-            if (tt < 0) acc = tlu[t] * S < tt;
+            if (tt < 0) acc = L.tlu[t] * S < tt;
           } else {
             const double logH = g * (llb - lla);
-            if (logH < 0) acc = tlu[t] < logH;
+            if (logH < 0) acc = L.tlu[t] < logH;
           }
-          tacc[t] = acc ? 1 : 0;
+          L.tacc[t] = acc ? 1 : 0;
           if (evb) {   // the two rungs' temperatures as this pick's add_state calls see them (before its own pry)
             double ba = bw[i], bb = bw[i + 1];
             if (pried) {
-              if (i > 0) ba = 1 - p0[i] / nrm;
-              if (i + 1 < Nt - 1) bb = 1 - p0[i + 1] / nrm;
+              if (i > 0) ba = 1 - L.p0[i] / nrm;
+              if (i + 1 < Nt - 1) bb = 1 - L.p0[i + 1] / nrm;
             }
-            bklo[k] = ba;
+            L.bklo[k] = ba;
             // (chain-indexed: the shard's own rungs -- a rung shard replays the whole ladder's picks, ptm_exchange_decide_gathered)
             if (i + 1 >= p.r0 && i + 1 < r1) p.beta_add[(size_t)(i + 1 - p.r0) * p.W + w] = bb;
             if (!PTM_ALIVE_RUNG(i - 1) && i >= p.r0 && i < r1) p.beta_add[(size_t)(i - p.r0) * p.W + w] = ba;
           }
           if (acc) {
-            const double a = llv[i]; llv[i] = llv[i + 1]; llv[i + 1] = a;
-            const double b = lpv[i]; lpv[i] = lpv[i + 1]; lpv[i + 1] = b;
+            const double a = L.llv[i]; L.llv[i] = L.llv[i + 1]; L.llv[i + 1] = a;
+            const double b = L.lpv[i]; L.lpv[i] = L.lpv[i + 1]; L.lpv[i + 1] = b;
           }
         }
         __syncthreads();
-        if (tacc[t]) {   // pry_temps({i}, rate, invtemps, gather_lposts()): chain.cc:1516-1517,1809-1846
-          const double S = ev[0];
-          const bool pried = ev[1] > 0;
+        if (L.tacc[t]) {   // pry_temps({i}, rate, invtemps, gather_lposts()): chain.cc:1516-1517,1809-1846
+          const double S = L.ev[0];
+          const bool pried = L.ev[1] > 0;
           const double nrm = S / c1;
           for (int kk = lane; kk < Nt - 1; kk += DECIDE_THREADS) {
-            const double b0 = (kk == 0 || !pried) ? bw[kk] : 1 - p0[kk] / nrm;
-            const double b1 = (kk + 1 == Nt - 1 || !pried) ? bw[kk + 1] : 1 - p0[kk + 1] / nrm;
-            const double t0 = b0 * llv[kk], t1 = b1 * llv[kk + 1];
-            const double l0 = lpv[kk] + t0, l1 = lpv[kk + 1] + t1;   // the chains' current log-posteriors (MH_chain::resetTemp, chain.cc:1088-1091)
-            double gk = gap[kk];
+            const double b0 = (kk == 0 || !pried) ? bw[kk] : 1 - L.p0[kk] / nrm;
+            const double b1 = (kk + 1 == Nt - 1 || !pried) ? bw[kk + 1] : 1 - L.p0[kk + 1] / nrm;
+            const double t0 = b0 * L.llv[kk], t1 = b1 * L.llv[kk + 1];
+            const double l0 = L.lpv[kk] + t0, l1 = L.lpv[kk + 1] + t1;   // the chains' current log-posteriors (MH_chain::resetTemp, chain.cc:1088-1091)
+            double gk = L.gap[kk];
             if (l0 - l1 > p.evolve_cut * b0) gk = gk * grow;          // :1819-1827
             if (kk == i) gk = gk * grow;                              // :1829
-            gap[kk] = gk;
+            L.gap[kk] = gk;
           }
           __syncthreads();
           for (int q = lane; q < nch; q += DECIDE_THREADS) {
             double loc = 0.0;
-            for (int kk = 32 * q; kk < Nt - 1 && kk < 32 * q + 32; ++kk) { p0[kk] = loc; loc = loc + gap[kk]; }
-            ct[q] = loc;
+            for (int kk = 32 * q; kk < Nt - 1 && kk < 32 * q + 32; ++kk) { L.p0[kk] = loc; loc = loc + L.gap[kk]; }
+            L.ct[q] = loc;
           }
           __syncthreads();
           if (lane == 0) {
-            const double S2 = decide_totals_scan(ct, ct + nch, nch);
-            ev[0] = S2; ev[1] = ev[1] + 1.0;
+            const double S2 = decide_totals_scan(L.ct, L.ct + nch, nch);
+            L.ev[0] = S2; L.ev[1] = L.ev[1] + 1.0;
           }
           __syncthreads();
-          for (int kk = lane; kk < Nt - 1; kk += DECIDE_THREADS) p0[kk] = ct[nch + (kk >> 5)] + p0[kk];
+          for (int kk = lane; kk < Nt - 1; kk += DECIDE_THREADS) L.p0[kk] = L.ct[nch + (kk >> 5)] + L.p0[kk];
           __syncthreads();
         }
       }
@@ -467,28 +411,28 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       const double c1 = 1 - blast;   // chain.cc:1833
       const double grow = 1.0 + p.evolve_rate;
       if (lane == 0) {
-        const double S = decide_totals_scan(ct, ct + nch, nch);
-        ev[0] = S; ev[1] = 0.0;
-        cnt[2] = 0; cnt[3] = 0;
+        const double S = decide_totals_scan(L.ct, L.ct + nch, nch);
+        L.ev[0] = S; L.ev[1] = 0.0;
+        L.cnt[2] = 0; L.cnt[3] = 0;
       }
       __syncthreads();
       {   // an upper bound of every increment together (any order: it is a bound, taken with a margin)
         double part = 0.0;
-        for (int t = lane; t < nl; t += DECIDE_THREADS) part += tgap[t] * grow - tgap[t];
-        if (part != 0.0) atomicAdd(&ev[1], part);
+        for (int t = lane; t < nl; t += DECIDE_THREADS) part += L.tgap[t] * grow - L.tgap[t];
+        if (part != 0.0) atomicAdd(&L.ev[1], part);
       }
       __syncthreads();
-      const double S_lo = ev[0], S_hi = (ev[0] + ev[1]) * (1.0 + 1e-12);
+      const double S_lo = L.ev[0], S_hi = (L.ev[0] + L.ev[1]) * (1.0 + 1e-12);
       for (int j = lane; j < nl; j += DECIDE_THREADS) {
-        const int n = cand[list[j]];
+        const int n = L.cand[L.list[j]];
         if (PTM_ALIVE_RUNG(n + 1)) continue;                       // not the top of a run
         bool carried = false;
         double carry = 0.0;
         for (int i = n;; --i) {
-          const int t = opos[first[i]];
-          const double lu = tlu[t], g = tgap[t];
-          const double llb_raw = carried ? carry : tllb[t];
-          double lla = tlla[t];
+          const int t = L.opos[L.first[i]];
+          const double lu = L.tlu[t], g = L.tgap[t];
+          const double llb_raw = carried ? carry : L.tllb[t];
+          double lla = L.tlla[t];
           if (!(lla > -1e200)) lla = -1e200;
           double llb = llb_raw;
           if (!(llb > -1e200)) llb = -1e200;
@@ -497,57 +441,57 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
           const bool accA = !(logH < 0) || lu < logH;               // nothing pried yet (chain.cc:1463-1467 on the stored temperatures)
           const bool acc_lo = !(tt < 0) || lu * S_lo < tt;          // the hardest S to pass
           const bool acc_hi = !(tt < 0) || lu * S_hi < tt;          // the easiest
-          if (accA != acc_lo || accA != acc_hi) { cnt[2] = 1; break; }   // inside the window: this ladder walks in order
-          tacc[t] = accA ? 1 : 0;
+          if (accA != acc_lo || accA != acc_hi) { L.cnt[2] = 1; break; }   // inside the window: this ladder walks in order
+          L.tacc[t] = accA ? 1 : 0;
           carried = accA;
           carry = llb_raw;                                          // the row now on rung i came from rung i + 1
           if (!PTM_ALIVE_RUNG(i - 1)) break;
         }
       }
       __syncthreads();
-      if (cnt[2] == 0) {
+      if (L.cnt[2] == 0) {
         for (int t = lane; t < nl; t += DECIDE_THREADS)
-          if (tacc[t]) { gap[ti[t]] = tgap[t] * grow; atomicAdd(&cnt[3], 1); }   // chain.cc:1829
+          if (L.tacc[t]) { L.gap[L.ti[t]] = L.tgap[t] * grow; atomicAdd(&L.cnt[3], 1); }   // chain.cc:1829
         __syncthreads();
-        if (lane == 0) ev[1] = (double)cnt[3];
+        if (lane == 0) L.ev[1] = (double)L.cnt[3];
         if (evb && lane == 0) {
           // what the sequential walk would have noted per pick: the normaliser it saw (0: nothing pried yet), what it added
-          double S = ev[0];
+          double S = L.ev[0];
           int npry = 0;
           for (int t0 = 0; t0 < nl; t0 += 8) {   // (operands first: a lone lane pays ~100 cycles per dependent LDS read)
             double g8[8];
             bool a8[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { g8[j] = t0 + j < nl ? tgap[t0 + j] : 0.0; a8[j] = t0 + j < nl && tacc[t0 + j] != 0; }
+            for (int j = 0; j < 8; ++j) { g8[j] = t0 + j < nl ? L.tgap[t0 + j] : 0.0; a8[j] = t0 + j < nl && L.tacc[t0 + j] != 0; }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               if (t0 + j >= nl) break;
-              tS[t0 + j] = npry ? S : 0.0;
+              L.tS[t0 + j] = npry ? S : 0.0;
               double inc = 0.0;
               if (a8[j]) { const double sn = g8[j] * grow; inc = sn - g8[j]; S = S + inc; ++npry; }   // chain.cc:1829
-              tdl[t0 + j] = inc;
+              L.tdl[t0 + j] = inc;
             }
           }
         }
         walked = true;
       } else {
-        for (int t = lane; t < nl; t += DECIDE_THREADS) tacc[t] = 0;
+        for (int t = lane; t < nl; t += DECIDE_THREADS) L.tacc[t] = 0;
       }
       __syncthreads();
     }
     if (!cutmode && !walked && lane == 0) {
-      double S = decide_totals_scan(ct, ct + nch, nch);
+      double S = decide_totals_scan(L.ct, L.ct + nch, nch);
       const double c1 = 1 - blast;   // chain.cc:1833
       const double grow = 1.0 + p.evolve_rate;
       int npry = 0;
       // one lane streams the picks; the next pick's operands are asked for before this one is decided
       double n_lu = 0, n_gap = 0, n_lla = 0, n_llb = 0, fwd = 0;
       int n_dep = -1, n_i = 0, fwd_to = -1;
-      if (nl > 0) { n_lu = tlu[0]; n_gap = tgap[0]; n_lla = tlla[0]; n_llb = tllb[0]; n_dep = tdep[0]; n_i = ti[0]; }
+      if (nl > 0) { n_lu = L.tlu[0]; n_gap = L.tgap[0]; n_lla = L.tlla[0]; n_llb = L.tllb[0]; n_dep = L.tdep[0]; n_i = L.ti[0]; }
       for (int t = 0; t < nl; ++t) {
         const double lu = n_lu, g = n_gap, lla_raw = n_lla, llb_raw = (fwd_to == t) ? fwd : n_llb;
         const int dep = n_dep, i = n_i;
-        if (t + 1 < nl) { n_lu = tlu[t + 1]; n_gap = tgap[t + 1]; n_lla = tlla[t + 1]; n_llb = tllb[t + 1]; n_dep = tdep[t + 1]; n_i = ti[t + 1]; }
+        if (t + 1 < nl) { n_lu = L.tlu[t + 1]; n_gap = L.tgap[t + 1]; n_lla = L.tlla[t + 1]; n_llb = L.tllb[t + 1]; n_dep = L.tdep[t + 1]; n_i = L.ti[t + 1]; }
         double lla = lla_raw;
         if (!(lla > -1e200)) lla = -1e200;
         double llb = llb_raw;
@@ -562,24 +506,24 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
           const double logH = g * (llb - lla);
           if (logH < 0) acc = lu < logH;
         }
-        if (evb) { tS[t] = npry ? S : 0.0; tdl[t] = 0.0; }
+        if (evb) { L.tS[t] = npry ? S : 0.0; L.tdl[t] = 0.0; }
         if (acc) {
-          tacc[t] = 1;
+          L.tacc[t] = 1;
           const double sn = g * grow;   // chain.cc:1829
           const double inc = sn - g;
           S = S + inc;
-          gap[i] = sn;
+          L.gap[i] = sn;
           ++npry;
-          if (evb) tdl[t] = inc;
-          if (dep >= 0) { tllb[dep] = llb_raw; fwd = llb_raw; fwd_to = dep; }   // the row now on rung i came from rung i + 1
+          if (evb) L.tdl[t] = inc;
+          if (dep >= 0) { L.tllb[dep] = llb_raw; fwd = llb_raw; fwd_to = dep; }   // the row now on rung i came from rung i + 1
         }
       }
-      ev[1] = (double)npry;
+      L.ev[1] = (double)npry;
     }
     __syncthreads();
-    if (al) {   // the trial operands are dead: perm moves in
+    if (L.aliased) {   // the trial operands are dead: perm moves in
       for (int j = lane; j < nl; j += DECIDE_THREADS) {
-        const int n = cand[list[j]];
+        const int n = L.cand[L.list[j]];
         perm[n] = (unsigned short)n;
         if (!PTM_ALIVE_RUNG(n + 1) || n + 2 > whi) perm[n + 1] = (unsigned short)(n + 1);
       }
@@ -589,7 +533,7 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   // -- trials (2): the top pick of each run of surviving rungs walks the run downwards (chain.cc:1436-1537); with an
   //    evolving ladder the decisions are the ones just taken
   for (int j = lane; j < nl; j += DECIDE_THREADS) {
-    const int n = cand[list[j]];
+    const int n = L.cand[L.list[j]];
     const bool up = PTM_ALIVE_RUNG(n + 1);
     if (up && n + 1 < whi) continue;                             // not the top of a run (the pick above is in the list)
     if (up) {
@@ -597,33 +541,33 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       // every rung of this run is then unknown here.  Harmless as long as the run ends above the shard's own rungs.
       for (int i = n; i >= wlo; --i) {
         if (i + 1 <= r1) atomicOr(p.err, 2);                     // would decide a local / straddling exchange blindly
-        alive[first[i]] = 2;
+        L.alive[L.first[i]] = 2;
         if (!PTM_ALIVE_RUNG(i - 1)) break;
       }
       continue;
     }
     for (int i = n; i >= wlo; --i) {                             // below the window nothing concerns us
-      const int kk = first[i];
+      const int kk = L.first[i];
       bool acc = true;
       if (evolve) {
-        acc = tacc[opos[kk]] != 0;
+        acc = L.tacc[L.opos[kk]] != 0;
       } else {
         double lla = llc[i];
         if (!(lla > -1e200)) lla = -1e200;
         double llb = llc[i + 1];
         if (!(llb > -1e200)) llb = -1e200;
         const double logH = -(beta[i + 1] - beta[i]) * (llb - lla);
-        if (logH < 0) acc = dlog_u01(ua[kk]) < logH;
+        if (logH < 0) acc = dlog_u01(L.ua[kk]) < logH;
       }
       if (acc) {
         // the row that leaves this shard downwards must be one of ours (else it crossed two boundaries in one step)
         if (i + 1 == p.r0 && (perm[i + 1] < p.r0 || perm[i + 1] >= r1)) atomicOr(p.err, 1);
         const double t = llc[i]; llc[i] = llc[i + 1]; llc[i + 1] = t;
         const unsigned short s = perm[i]; perm[i] = perm[i + 1]; perm[i + 1] = s;
-        accf[kk] = 1;
+        L.accf[kk] = 1;
       }
       if (!PTM_ALIVE_RUNG(i - 1)) break;
-      midk[kk] = perm[i];   // the pick below exchanges rung i again: this is what it held in between
+      L.midk[kk] = perm[i];   // the pick below exchanges rung i again: this is what it held in between
     }
   }
   __syncthreads();
@@ -634,20 +578,20 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       // pry; chain.cc:1487-1490,1531-1534): 1 - (P0 + D) / normaliser, P0 = prefix of the step's first gaps, D = what
       // the earlier accepted picks added to the gaps below the rung, in pick order.  No gap between the pair's two rungs
       // has been pried yet (a pair is tried once), so D is the same for both.
-      for (int k = lane; k < Nt - 1; k += DECIDE_THREADS) p0[k] = ct[nch + (k >> 5)] + p0[k];
+      for (int k = lane; k < Nt - 1; k += DECIDE_THREADS) L.p0[k] = L.ct[nch + (k >> 5)] + L.p0[k];
       __syncthreads();
       for (int j = lane; j < nl; j += DECIDE_THREADS) {
-        const int k = list[j];
-        const int i = cand[k];
-        const int t = opos[k];
+        const int k = L.list[j];
+        const int i = L.cand[k];
+        const int t = L.opos[k];
         double D = 0.0;
         for (int t2 = 0; t2 < t; ++t2)
-          if (tacc[t2] && ti[t2] < i) D = D + tdl[t2];
-        const double Sk = tS[t];
+          if (L.tacc[t2] && L.ti[t2] < i) D = D + L.tdl[t2];
+        const double Sk = L.tS[t];
         const double nk = Sk / (1 - blast);   // the normaliser then (chain.cc:1833)
-        const double blo = (Sk == 0.0 || i == 0) ? tbl[t] : 1 - (p0[i] + D) / nk;
-        const double bhi = (Sk == 0.0 || i + 1 == Nt - 1) ? tbh[t] : 1 - (p0[i + 1] + D) / nk;
-        bklo[k] = blo;
+        const double blo = (Sk == 0.0 || i == 0) ? L.tbl[t] : 1 - (L.p0[i] + D) / nk;
+        const double bhi = (Sk == 0.0 || i + 1 == Nt - 1) ? L.tbh[t] : 1 - (L.p0[i + 1] + D) / nk;
+        L.bklo[k] = blo;
         // last add of the phase: always for the upper rung (a pick on the pair above came earlier), for the lower rung
         // unless a later pick exchanges it again
         if (i + 1 >= p.r0 && i + 1 < r1) p.beta_add[(size_t)(i + 1 - p.r0) * p.W + w] = bhi;
@@ -655,31 +599,31 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       }
       __syncthreads();
     }
-    if (ev[1] > 0) {   // the new temperatures (chain.cc:1834-1844): beta_k = 1 - P_k / (total / (1 - beta_last))
+    if (L.ev[1] > 0) {   // the new temperatures (chain.cc:1834-1844): beta_k = 1 - P_k / (total / (1 - beta_last))
       for (int q = lane; q < nch; q += DECIDE_THREADS) {
         double loc = 0.0;
 #pragma unroll 1
         for (int j0 = 0; j0 < 32; j0 += 8) {
           double r8[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { const int k = 32 * q + j0 + j; r8[j] = k < Nt - 1 ? gap[k] : 0.0; }
+          for (int j = 0; j < 8; ++j) { const int k = 32 * q + j0 + j; r8[j] = k < Nt - 1 ? L.gap[k] : 0.0; }
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const int k = 32 * q + j0 + j;
-            if (k < Nt - 1) { gap[k] = loc; loc = loc + r8[j]; }
+            if (k < Nt - 1) { L.gap[k] = loc; loc = loc + r8[j]; }
           }
         }
-        ct[q] = loc;
+        L.ct[q] = loc;
       }
       __syncthreads();
       if (lane == 0) {
-        const double off = decide_totals_scan(ct, ct + nch, nch);
-        ev[0] = off / (1 - blast);
+        const double off = decide_totals_scan(L.ct, L.ct + nch, nch);
+        L.ev[0] = off / (1 - blast);
       }
       __syncthreads();
-      const double nn = ev[0];
+      const double nn = L.ev[0];
       for (int k = 1 + lane; k < Nt - 1; k += DECIDE_THREADS) {
-        const double bk = 1 - (ct[nch + (k >> 5)] + gap[k]) / nn;
+        const double bk = 1 - (L.ct[nch + (k >> 5)] + L.gap[k]) / nn;
         p.beta_w[(size_t)w * Nt + k] = bk;
         if (p.betaC_direct && k >= p.r0 && k < r1) p.betaC_direct[(size_t)(k - p.r0) * p.W + w] = bk;
       }
@@ -687,18 +631,18 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   }
   // -- the step's log
   for (int k = lane; k < ms; k += DECIDE_THREADS)
-    swap_log[(size_t)w * ms + k] = alive[k] == 1 ? (cand[k] | (accf[k] ? 0x40000000 : 0)) : (alive[k] == 2 ? -3 : -2);
+    swap_log[(size_t)w * ms + k] = L.alive[k] == 1 ? (L.cand[k] | (L.accf[k] ? 0x40000000 : 0)) : (L.alive[k] == 2 ? -3 : -2);
   // -- counters, the touch counts of the local rungs and the inverse permutation
   for (int j = lane; j < nl; j += DECIDE_THREADS) {
-    const int k = list[j];
-    if (alive[k] != 1) continue;
-    const int i = cand[k];
+    const int k = L.list[j];
+    if (L.alive[k] != 1) continue;
+    const int i = L.cand[k];
     // (swap_count / swap_accept_count, chain.cc:1498,1536, are not touched here: 185 scattered read-modify-writes per
     //  ladder and step.  fold_swap_log_kernel adds the logged steps to them every PTM_LOG_RING steps and on demand.)
-    const int rtop = (PTM_ALIVE_RUNG(i + 1) && alive[first[i + 1]] == 1) ? i : i + 1;  // rung i+1 belongs to the pick above, if ours
+    const int rtop = (PTM_ALIVE_RUNG(i + 1) && L.alive[L.first[i + 1]] == 1) ? i : i + 1;  // rung i+1 belongs to the pick above, if ours
     for (int r = i; r <= rtop; ++r) {
       if (r >= p.r0 && r < r1) {
-        const int below_alive = (r > 0 && PTM_ALIVE_RUNG(r - 1) && alive[first[r - 1]] == 1) ? 1 : 0;
+        const int below_alive = (r > 0 && PTM_ALIVE_RUNG(r - 1) && L.alive[L.first[r - 1]] == 1) ? 1 : 0;
         const int self_alive = (r == i) ? 1 : 0;
         p.touch[(r - p.r0) * p.W + w] = (unsigned char)(below_alive + self_alive);
       }
@@ -709,15 +653,15 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   // -- the row moves.  The phase's net effect on the touched rungs is a permutation of rows: new row[r] =
   //    old row[perm[r]].  List every move (source slot -> destination slot, or -> boundary message for a row that
   //    leaves the shard) for move_kernel; the hole an arrival will fill is named in arr_above / arr_below.
-  int* gs = lmv;
-  int* gd = lmv + MVCAP;
+  int* gs = L.lmv;
+  int* gd = L.lmv + MVCAP;
   // source slot of the in-between row of rung r if its FIRST add_state of this step is one that saves, else -1
   auto hist_mid_src = [&](int r) -> int {
     if (r - p.r0 >= p.hist.rungs || r < p.r0 || r >= r1) return -1;
-    if (!(r > 0 && PTM_ALIVE_RUNG(r - 1) && alive[first[r - 1]] == 1)) return -1;   // touched once only
+    if (!(r > 0 && PTM_ALIVE_RUNG(r - 1) && L.alive[L.first[r - 1]] == 1)) return -1;   // touched once only
     const int c = (r - p.r0) * p.W + w;
     if (p.nhist[c] % (unsigned int)p.add_every_n != 0u) return -1;
-    const int s1 = midk[first[r]];
+    const int s1 = L.midk[L.first[r]];
     if (s1 < p.r0 || s1 >= r1) { atomicOr(p.err, 16); return -1; }   // (the host keeps recorded rungs away from shard tops)
     return (s1 - p.r0) * p.W + w;
   };
@@ -725,31 +669,31 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   // beats the rung's MAP (the first of the two add_state calls sees it, chain.cc:931-934), else -1
   auto map_mid_src = [&](int r, double bmid) -> int {
     if (r - p.r0 >= p.map.rungs || r < p.r0 || r >= r1) return -1;
-    if (!(r > 0 && PTM_ALIVE_RUNG(r - 1) && alive[first[r - 1]] == 1)) return -1;   // touched once only
-    const int s1 = midk[first[r]];
+    if (!(r > 0 && PTM_ALIVE_RUNG(r - 1) && L.alive[L.first[r - 1]] == 1)) return -1;   // touched once only
+    const int s1 = L.midk[L.first[r]];
     if (s1 < p.r0 || s1 >= r1) { atomicOr(p.err, 16); return -1; }
     const int cs = (s1 - p.r0) * p.W + w;
     const double t = bmid * p.ll[cs];
     return (p.lp[cs] + t > p.map.lpost[(r - p.r0) * p.W + w]) ? cs : -1;
   };
   for (int j = lane; j < nl; j += DECIDE_THREADS) {
-    const int k = list[j];
-    if (alive[k] != 1) continue;
-    const int i = cand[k];
-    const int rtop = (PTM_ALIVE_RUNG(i + 1) && alive[first[i + 1]] == 1) ? i : i + 1;
-    const double bmid = evb ? bklo[k] : beta[i];   // rung i's temperature at this pick's add_state
+    const int k = L.list[j];
+    if (L.alive[k] != 1) continue;
+    const int i = L.cand[k];
+    const int rtop = (PTM_ALIVE_RUNG(i + 1) && L.alive[L.first[i + 1]] == 1) ? i : i + 1;
+    const double bmid = evb ? L.bklo[k] : beta[i];   // rung i's temperature at this pick's add_state
     if (p.hist.rungs) {
       const int hs = hist_mid_src(i);
       if (hs >= 0) {
-        const int m = atomicAdd(&cnt[1], 1);
-        if (m < MVCAP) { gs[m] = hs; gd[m] = HIST_DST - ((i - p.r0) * p.W + w); if (evb) gb[m] = bmid; }
+        const int m = atomicAdd(&L.cnt[1], 1);
+        if (m < MVCAP) { gs[m] = hs; gd[m] = HIST_DST - ((i - p.r0) * p.W + w); if (evb) L.gb[m] = bmid; }
       }
     }
     if (p.map.rungs) {
       const int ms_ = map_mid_src(i, bmid);
       if (ms_ >= 0) {
-        const int m = atomicAdd(&cnt[1], 1);
-        if (m < MVCAP) { gs[m] = ms_; gd[m] = MAP_DST - ((i - p.r0) * p.W + w); if (evb) gb[m] = bmid; }
+        const int m = atomicAdd(&L.cnt[1], 1);
+        if (m < MVCAP) { gs[m] = ms_; gd[m] = MAP_DST - ((i - p.r0) * p.W + w); if (evb) L.gb[m] = bmid; }
       }
     }
     for (int r = i; r <= rtop; ++r) {
@@ -757,20 +701,20 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
       const int s = perm[r], to = inv[r];
       const int cr = (r - p.r0) * p.W + w;
       if (s >= p.r0 && s < r1) {                            // local -> local
-        const int m = atomicAdd(&cnt[1], 1);
+        const int m = atomicAdd(&L.cnt[1], 1);
         if (m < MVCAP) { gs[m] = (s - p.r0) * p.W + w; gd[m] = cr; }
       } else {
         (s >= r1 ? p.arr_above : p.arr_below)[w] = cr;       // the hole: an arrival from the adjacent shard lands here
       }
       if (to < p.r0 || to >= r1) {                           // rung r's old row leaves the shard
-        const int m = atomicAdd(&cnt[1], 1);
+        const int m = atomicAdd(&L.cnt[1], 1);
         if (m < MVCAP) { gs[m] = cr; gd[m] = (to >= r1) ? -1 : -2; }
         if (!((to >= r1) ? p.send_up : p.send_down)) atomicOr(p.err, 1);
       }
     }
   }
   __syncthreads();
-  const int nmv = cnt[1];
+  const int nmv = L.cnt[1];
   if (p.rowof && nmv <= MVCAP) {
     // ---- labelled rows: every listed move is local -> local (the whole ladder is here, nothing is recorded); the rungs exchange
     //      their labels and scalars, the rows stay where they are.  Same discipline as below: every read of every thread has
@@ -871,10 +815,10 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
         const int c = HIST_DST - d;
         const long long hrow = 1 + (long long)(p.nhist[c] / (unsigned int)p.add_every_n);
         hist_scalars(p.hist, hist_slot(p.hist, hrow, c), hrow, sl, sp, p.naccept[c], p.ntries[c], p.last_type[c],
-                     evb ? gb[lane] : beta[p.r0 + c / p.W]);
+                     evb ? L.gb[lane] : beta[p.r0 + c / p.W]);
       } else if (d <= MAP_DST) {
         const int c = MAP_DST - d;
-        const double t = (evb ? gb[lane] : beta[p.r0 + c / p.W]) * sl;
+        const double t = (evb ? L.gb[lane] : beta[p.r0 + c / p.W]) * sl;
         p.map.lpost[c] = sp + t; p.map.ll[c] = sl; p.map.lp[c] = sp;
       } else if (d != -3) {
         const int e = -d - 4;
@@ -890,25 +834,25 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
   const int DP = p.DP;
   if (p.hist.rungs) {   // in-between rows first: they are read from rows nobody has moved yet
     for (int j = lane; j < nl; j += DECIDE_THREADS) {
-      const int k = list[j];
-      if (alive[k] != 1) continue;
-      const int i = cand[k];
+      const int k = L.list[j];
+      if (L.alive[k] != 1) continue;
+      const int i = L.cand[k];
       const int hs = hist_mid_src(i);
       if (hs < 0) continue;
       const int c = (i - p.r0) * p.W + w;
       const long long hrow = 1 + (long long)(p.nhist[c] / (unsigned int)p.add_every_n);
       const size_t o = hist_slot(p.hist, hrow, c);
       for (int d = 0; d < DP; ++d) p.hist.x[o * DP + d] = p.x[(size_t)hs * DP + d];
-      hist_scalars(p.hist, o, hrow, p.ll[hs], p.lp[hs], p.naccept[c], p.ntries[c], p.last_type[c], evb ? bklo[k] : beta[i]);
+      hist_scalars(p.hist, o, hrow, p.ll[hs], p.lp[hs], p.naccept[c], p.ntries[c], p.last_type[c], evb ? L.bklo[k] : beta[i]);
     }
     __syncthreads();
   }
   if (p.map.rungs) {
     for (int j = lane; j < nl; j += DECIDE_THREADS) {
-      const int k = list[j];
-      if (alive[k] != 1) continue;
-      const int i = cand[k];
-      const double bmid = evb ? bklo[k] : beta[i];
+      const int k = L.list[j];
+      if (L.alive[k] != 1) continue;
+      const int i = L.cand[k];
+      const double bmid = evb ? L.bklo[k] : beta[i];
       const int cs = map_mid_src(i, bmid);
       if (cs < 0) continue;
       const int c = (i - p.r0) * p.W + w;
@@ -919,10 +863,10 @@ __device__ __forceinline__ void decide_body(const Decide& p, unsigned char* smem
     __syncthreads();
   }
   for (int j = lane; j < nl; j += DECIDE_THREADS) {
-    const int k = list[j];
-    if (alive[k] != 1) continue;
-    const int i = cand[k];
-    const int rtop = (PTM_ALIVE_RUNG(i + 1) && alive[first[i + 1]] == 1) ? i : i + 1;
+    const int k = L.list[j];
+    if (L.alive[k] != 1) continue;
+    const int i = L.cand[k];
+    const int rtop = (PTM_ALIVE_RUNG(i + 1) && L.alive[L.first[i + 1]] == 1) ? i : i + 1;
     for (int r = i; r <= rtop; ++r) {
       if (r < p.r0 || r >= r1 || perm[r] == r) continue;
       const int to = inv[r];
@@ -993,18 +937,5 @@ __global__ __launch_bounds__(DECIDE_THREADS) void decide_kernel(const Decide p) 
   // walkers keeps the ladders that share those lines on one L2.
   decide_body<DECIDE_THREADS, CUT>(p, smem, xcd_walker(blockIdx.x, p.W), p.step, p.swap_log);
 }
-
-// dynamic LDS of decide_body (host side)
-inline size_t decide_lds_bytes(int Nt, int ms, int WN, bool evolve, bool evb, bool cut = false) {
-  if (cut) return decide_lds_bytes(Nt, ms, WN, evolve, true) + (size_t)2 * Nt * 8;   // (the history carve + every rung's llike, lprior)
-  // mirrors the carve at the top of decide_body
-  const bool al = decide_aliased(ms, WN, evolve);
-  const size_t msp = (size_t)((ms + 3) & ~3), WNp = (size_t)((WN + 3) & ~3);
-  return (size_t)WN * 8 + (size_t)((Nt + 3) & ~3) * 2 + (size_t)((ms + 1) & ~1) * 4 * 2 + 16 + (al ? 0 : 2 * WNp * 2) + 2 * msp * 2 +
-         (size_t)((ms + 7) & ~7) * 2 + (al ? 0 : (size_t)2 * MVCAP * 4) + 32 +
-         (evolve ? ((size_t)Nt + 2 * ((Nt + 31) / 32) + 2 + 4 * msp) * 8 + 4 * msp * 2 + ((ms + 7) & ~7) : 0) +
-         (evb ? ((size_t)(Nt > MVCAP ? Nt : MVCAP) + 5 * msp) * 8 : 0);
-}
-
 
 }  // namespace ptm

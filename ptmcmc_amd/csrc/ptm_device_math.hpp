@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ptm_lds_layout.hpp"
+
 namespace ptm {
 
 // ------------------------------------------------------------------------------------------------
@@ -277,7 +279,6 @@ __device__ __forceinline__ double dsqrt(double a) {
 #include "ptm_tables.inc"
 // One table image, staged whole into LDS by the sweep kernels: [0, 512) the radius table, [512, 2560) the angle table
 // {sin a_i, cos a_i}, a_i = (i + 0.5) pi / 1024.
-constexpr int BM_TABLE_DOUBLES = 512 + 2048;
 __device__ __attribute__((aligned(16))) const double BM_TABLE[BM_TABLE_DOUBLES] = {PTM_BMTAB_VALUES, PTM_TRIGTAB_VALUES};
 
 typedef double bm_d2 __attribute__((ext_vector_type(2)));

@@ -1610,11 +1610,11 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
       b.seed = e->cfg.seed; b.step = e->step;
       b.x = p.x; b.ll = e->ll; b.lp = e->lp; b.beta = e->beta; b.prop_tiles = e->prop_tiles; b.box_row = e->box_row; b.ntries = e->ntries;
       b.pidx = e->pidx; b.pcnt = e->pcnt; b.cidx = e->cidx; b.ccnt = e->ccnt; b.counts = e->pf_counts;
-      const size_t lds = box_prefilter_lds(nr);
+      const size_t lds = BoxPreLds(nullptr, nr).bytes;
       if (!e->pf_grid) {   // a persistent grid: the blocks the device holds at once
         int per_cu = 0, dev = 0;
         hipDeviceProp_t pr;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_kernel, 256, box_prefilter_lds(e->nloc)) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_kernel, 256, BoxPreLds(nullptr, e->nloc).bytes) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
         HIPCHK(hipGetDevice(&dev));
         HIPCHK(hipGetDeviceProperties(&pr, dev));
         e->pf_grid = per_cu * (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
@@ -1785,7 +1785,7 @@ static int launch_decide(ptm_engine* e, const double* ll_below, const double* ll
   const int WN = ll_all ? e->Nt : e->nloc + (ll_below ? 1 : 0) + p.H;
   const bool evb = e->evolve_rate > 0 && e->beta_add;
   const bool cut = e->evolve_rate > 0 && e->evolve_cut >= 0;
-  const size_t lds = decide_lds_bytes(e->Nt, e->ms, WN, e->evolve_rate > 0, evb, cut);
+  const size_t lds = DecideLds(nullptr, e->Nt, e->ms, WN, e->evolve_rate > 0, evb, cut).bytes;
   if (lds > 160 * 1024) return fail(PTM_ERR_UNSUPPORTED, "ladder too long for the LDS-resident exchange kernel (%zu B)", lds);
   if (e->ms >= 65535) return fail(PTM_ERR_UNSUPPORTED, "more than 65534 exchange candidates per step (the exchange kernel numbers them in 16 bits)");
   // expected candidates inside the window; evolving ladders with history / MAP tracking: the wide form alone carries the
@@ -2153,7 +2153,7 @@ extern "C" int ptm_sweep(ptm_engine* e, int n) {
 // Small ladders (rungs x padded dimensions <= the 1024 lanes of one workgroup, device target and proposals): whole PT steps in
 // ONE launch per batch, a block per walker-ladder looping over the steps (ptm_fused_kernel.hpp).  PTM_FUSED=0 keeps the
 // two-launch path.  Returns the steps taken (0: not this engine's case), or a negative status.
-static size_t fused_decide_lds(const ptm_engine* e) { return decide_lds_bytes(e->Nt, e->ms, e->Nt, e->evolve_rate > 0, e->evolve_rate > 0 && e->beta_add); }
+static size_t fused_decide_lds(const ptm_engine* e) { return DecideLds(nullptr, e->Nt, e->ms, e->Nt, e->evolve_rate > 0, e->evolve_rate > 0 && e->beta_add, false).bytes; }
 static bool fused_applies(const ptm_engine* e) {
   static const bool fused_ok = [] { const char* v = getenv("PTM_FUSED"); return !(v && *v == '0'); }();
   StepFacts f;

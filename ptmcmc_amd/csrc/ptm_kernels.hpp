@@ -641,16 +641,16 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   // wave, then wave-uniform (broadcast) LDS reads feed the mat-vec.  Same-wave LDS traffic only: no barrier.
   // The first 20 KB of the block's LDS hold the Box-Muller tables (per-lane gathers, one 16-byte entry per draw each).
   extern __shared__ __attribute__((aligned(16))) double lds_all[];
-  double* lds_fac = lds_all + BM_TABLE_DOUBLES;
+  const GeneralLds L(lds_all, UNI && KIND != KIND_DIAG, p.prop_stride);
 #pragma unroll
   for (int t = 0; t < BM_TABLE_DOUBLES / 512; ++t)
-    reinterpret_cast<bm_d2*>(lds_all)[threadIdx.x + 256 * t] = reinterpret_cast<const bm_d2*>(BM_TABLE)[threadIdx.x + 256 * t];
+    reinterpret_cast<bm_d2*>(L.bm)[threadIdx.x + 256 * t] = reinterpret_cast<const bm_d2*>(BM_TABLE)[threadIdx.x + 256 * t];
   const int c = p.c_begin + blockIdx.x * 256 + threadIdx.x;
   int rl = (c < p.c_end ? c : p.c_end - 1) / p.W;
   if (UNI) rl = __builtin_amdgcn_readfirstlane(rl);
   // (DP == 32: the DPP product wants the dense column-major image, which the host keeps beside the packed one)
   const int fstride = p.prop_stride;
-  double* myfac = lds_fac + (threadIdx.x >> 6) * fstride;
+  double* myfac = L.fac + (threadIdx.x >> 6) * fstride;
   if (UNI && KIND != KIND_DIAG) {
     const double* g = p.prop + (size_t)rl * fstride;
     for (int k = threadIdx.x & 63; k < fstride; k += 64) myfac[k] = g[k];
@@ -722,7 +722,7 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
   double xn[DP];  // accumulates the offset, then becomes the proposed state
 #pragma unroll
   for (int i = 0; i < DP; ++i) xn[i] = 0.0;
-  const DrawCtx dc{p.seed, p.step, stream, (!SIMPLE) ? axis : -1, lds_all};
+  const DrawCtx dc{p.seed, p.step, stream, (!SIMPLE) ? axis : -1, L.bm};
   const int mode = SIMPLE ? 0 : p.mode;
 
   // (touched lanes run the draw too: the DPP product needs every lane of the wave active, and they would idle anyway)
@@ -762,7 +762,7 @@ __global__ __launch_bounds__(256, PTM_SWEEP_WAVES) void sweep_kernel(const Dev p
     // the member draws from the prior: the Gaussian offset of this lane is dropped (the wave's other lanes needed the loops).  The accept
     // pass of a host-callback likelihood finds the state in xprop and makes the ratio anew from lprior_new
     if (pr_move) {
-      if (mode != 2) prior_draw<DP>(p, stream, p.step, lds_all, xn);
+      if (mode != 2) prior_draw<DP>(p, stream, p.step, L.bm, xn);
       type = kmix;               // member + 10 * 0 (proposal_distribution.cc:117)
     }
   }

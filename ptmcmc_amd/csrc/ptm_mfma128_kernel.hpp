@@ -36,11 +36,7 @@ typedef double m128_d2 __attribute__((ext_vector_type(2)));
 
 constexpr int M128_NT = 8;           // row tiles of 16
 constexpr int M128_KS = 32;          // k-steps of 4 columns
-constexpr int M128_P2_TILES = 144;   // (row tile rt, step m) with m <= 4 rt + 3: at m128_p2_base(rt) + m
 __host__ __device__ constexpr int m128_p2_base(int rt) { return 2 * rt * (rt + 1); }
-// LDS in doubles: Box-Muller tables | precision tiles | prior box lo | hi (row layout) | 64 reduction slots per wave
-constexpr int M128_THREADS = 512;     // eight waves share the block's tables: two per SIMD at 256 registers each
-constexpr int m128_lds_doubles() { return BM_TABLE_DOUBLES + M128_P2_TILES * 64 + 256 + (M128_THREADS / 64) * 64 + 256; }   // (... | boundary box lo | hi)
 
 #define PTM_M128_STAGE() __builtin_amdgcn_sched_barrier(0)
 
@@ -51,24 +47,22 @@ __global__ __launch_bounds__(M128_THREADS, 1) void sweep_mfma128_kernel(const De
   constexpr bool LOW = KIND == KIND_LOWER;
   constexpr int RING = 3;   // k-step slots of factor tiles in flight
   extern __shared__ __attribute__((aligned(16))) double lds_all[];
-  double* ptile = lds_all + BM_TABLE_DOUBLES;
-  double* lbox = ptile + M128_P2_TILES * 64;
+  const Mfma128Lds L(lds_all);
   const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
-  double* red = lbox + 256 + wave * 64;
-  double* lebox = lbox + 256 + (M128_THREADS / 64) * 64;   // [2][128] boundary::enforce for open / limit sides (states.cc:53-55) as a box, row layout
+  double* red = L.red + wave * 64;
   const int q = l >> 4, j = l & 15;
-  const double* pimg = ptile + l;
-  const m128_d2* box = reinterpret_cast<const m128_d2*>(lbox) + q;   // lo piece t at [4t], hi piece t at [64 + 4t]
-  const m128_d2* ebx = reinterpret_cast<const m128_d2*>(lebox) + q;
+  const double* pimg = L.ptile + l;
+  const m128_d2* box = reinterpret_cast<const m128_d2*>(L.lbox) + q;   // lo piece t at [4t], hi piece t at [64 + 4t]
+  const m128_d2* ebx = reinterpret_cast<const m128_d2*>(L.lebox) + q;
 
   // the block's tables, once: the grid is persistent (a block per CU walks the launch's 512-chain tiles)
-  for (int i = threadIdx.x; i < BM_TABLE_DOUBLES / 2; i += M128_THREADS) reinterpret_cast<bm_d2*>(lds_all)[i] = reinterpret_cast<const bm_d2*>(BM_TABLE)[i];
-  for (int i = threadIdx.x; i < M128_P2_TILES * 64; i += M128_THREADS) ptile[i] = p.P2_tiles[i];
-  if (threadIdx.x < 256) lbox[threadIdx.x] = p.box_row[threadIdx.x];
+  for (int i = threadIdx.x; i < BM_TABLE_DOUBLES / 2; i += M128_THREADS) reinterpret_cast<bm_d2*>(L.bm)[i] = reinterpret_cast<const bm_d2*>(BM_TABLE)[i];
+  for (int i = threadIdx.x; i < M128_P2_TILES * 64; i += M128_THREADS) L.ptile[i] = p.P2_tiles[i];
+  if (threadIdx.x < 256) L.lbox[threadIdx.x] = p.box_row[threadIdx.x];
   if (BND && threadIdx.x < 128) {
     const int d = threadIdx.x, pos = row_pos<128>(d);
-    lebox[pos] = p.blo[d] == B_LIMIT ? p.bmin[d] : -__builtin_inf();
-    lebox[128 + pos] = p.bhi[d] == B_LIMIT ? p.bmax[d] : __builtin_inf();
+    L.lebox[pos] = p.blo[d] == B_LIMIT ? p.bmin[d] : -__builtin_inf();
+    L.lebox[128 + pos] = p.bhi[d] == B_LIMIT ? p.bmax[d] : __builtin_inf();
   }
   __syncthreads();
 
@@ -121,8 +115,8 @@ __global__ __launch_bounds__(M128_THREADS, 1) void sweep_mfma128_kernel(const De
         double z[4];
         {
           const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + 4 * hb + qd));
-          boxmuller(o.v0, o.v1, (const double*)lds_all, z[0], z[1]);
-          boxmuller(o.v2, o.v3, (const double*)lds_all, z[2], z[3]);
+          boxmuller(o.v0, o.v1, L.bm, z[0], z[1]);
+          boxmuller(o.v2, o.v3, L.bm, z[2], z[3]);
         }
         PTM_M128_STAGE();
         if (hb == 6) {   // the rows: needed after the last half (two halves of arithmetic away)

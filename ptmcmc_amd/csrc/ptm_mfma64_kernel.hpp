@@ -33,10 +33,7 @@ namespace ptm {
 typedef double m64_d4 __attribute__((ext_vector_type(4)));
 typedef double m64_d2 __attribute__((ext_vector_type(2)));
 
-constexpr int M64_P2_TILES = 40;   // (row tile rt, step m) with m <= 4 rt + 3: at m64_p2_base(rt) + m
 __host__ __device__ constexpr int m64_p2_base(int rt) { return rt == 0 ? 0 : (rt == 1 ? 4 : (rt == 2 ? 12 : 24)); }
-// LDS in doubles: Box-Muller tables | precision tiles | prior box lo | hi (row layout) | 64 reduction slots per wave
-constexpr int m64_lds_doubles() { return BM_TABLE_DOUBLES + M64_P2_TILES * 64 + 128 + 4 * 64 + 128; }   // (... | boundary box lo | hi)
 
 #define PTM_M64_STAGE() __builtin_amdgcn_sched_barrier(0)
 
@@ -45,24 +42,22 @@ __global__ __launch_bounds__(256, 2) void sweep_mfma64_kernel(const Dev p) {
   constexpr int DP = 64;
   constexpr bool LOW = KIND == KIND_LOWER;
   extern __shared__ __attribute__((aligned(16))) double lds_all[];
-  double* ptile = lds_all + BM_TABLE_DOUBLES;
-  double* lbox = ptile + M64_P2_TILES * 64;
+  const Mfma64Lds L(lds_all);
   const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
-  double* red = lbox + 128 + wave * 64;
-  double* lebox = lbox + 128 + 4 * 64;   // [2][64] boundary::enforce for open / limit sides (states.cc:53-55) as a box, row layout
+  double* red = L.red + wave * 64;
   const int q = l >> 4, j = l & 15;
-  const double* pimg = ptile + l;
-  const m64_d2* box = reinterpret_cast<const m64_d2*>(lbox) + q;   // lo piece t at [4t], hi piece t at [32 + 4t]
-  const m64_d2* ebx = reinterpret_cast<const m64_d2*>(lebox) + q;
+  const double* pimg = L.ptile + l;
+  const m64_d2* box = reinterpret_cast<const m64_d2*>(L.lbox) + q;   // lo piece t at [4t], hi piece t at [32 + 4t]
+  const m64_d2* ebx = reinterpret_cast<const m64_d2*>(L.lebox) + q;
 
   // the block's tables, once: the grid is persistent (a block per resident slot walks the launch's 256-chain tiles)
-  for (int i = threadIdx.x; i < BM_TABLE_DOUBLES / 2; i += 256) reinterpret_cast<bm_d2*>(lds_all)[i] = reinterpret_cast<const bm_d2*>(BM_TABLE)[i];
-  for (int i = threadIdx.x; i < M64_P2_TILES * 64; i += 256) ptile[i] = p.P2_tiles[i];
-  if (threadIdx.x < 128) lbox[threadIdx.x] = p.box_row[threadIdx.x];
+  for (int i = threadIdx.x; i < BM_TABLE_DOUBLES / 2; i += 256) reinterpret_cast<bm_d2*>(L.bm)[i] = reinterpret_cast<const bm_d2*>(BM_TABLE)[i];
+  for (int i = threadIdx.x; i < M64_P2_TILES * 64; i += 256) L.ptile[i] = p.P2_tiles[i];
+  if (threadIdx.x < 128) L.lbox[threadIdx.x] = p.box_row[threadIdx.x];
   if (BND && threadIdx.x < 64) {
     const int d = threadIdx.x, pos = row_pos<64>(d);
-    lebox[pos] = p.blo[d] == B_LIMIT ? p.bmin[d] : -__builtin_inf();
-    lebox[64 + pos] = p.bhi[d] == B_LIMIT ? p.bmax[d] : __builtin_inf();
+    L.lebox[pos] = p.blo[d] == B_LIMIT ? p.bmin[d] : -__builtin_inf();
+    L.lebox[64 + pos] = p.bhi[d] == B_LIMIT ? p.bmax[d] : __builtin_inf();
   }
   __syncthreads();
 
@@ -113,8 +108,8 @@ __global__ __launch_bounds__(256, 2) void sweep_mfma64_kernel(const Dev p) {
         double z[4];
         {
           const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + 4 * hb + qd));
-          boxmuller(o.v0, o.v1, (const double*)lds_all, z[0], z[1]);
-          boxmuller(o.v2, o.v3, (const double*)lds_all, z[2], z[3]);
+          boxmuller(o.v0, o.v1, L.bm, z[0], z[1]);
+          boxmuller(o.v2, o.v3, L.bm, z[2], z[3]);
         }
         PTM_M64_STAGE();
         if (hb == 2) {   // the rows: needed after the last half (two halves of arithmetic away)

@@ -78,26 +78,19 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   constexpr int GG = PTM_MFMA_GG ? PTM_MFMA_GG : (GEN == 2 ? 1 : (((GEN == 1 || GEN == 3) && CPT) ? PTM_MFMA_G1C_GG : 2)), NP = 4 / GG, PL = 16 * GG;   // groups per pass, passes per tile, chains (= stage-5 lanes) per pass
   constexpr bool LOW = KIND == KIND_LOWER;
   static_assert(GEN != 2 || GG == 1, "the mixture scales share the GEN 2 build's red2 slots: its prior products must stay below index 64");
-  // LDS: [2560] Box-Muller tables | [12][64] precision tiles | [64] prior box (all shared by the block's waves) |
-  //      128 doubles per wave
   extern __shared__ __attribute__((aligned(16))) double lds_all[];
-  double* ptile = lds_all + BM_TABLE_DOUBLES;   // tile (row tile 1, step m) at m*64, m = 0..7; (row tile 0, step m) at (8+m)*64, m = 0..3
-  double* lbox = ptile + 12 * 64;
+  const int nrung = (p.c_end - p.c_begin) / p.W;   // (CPT: the launch's rungs)
+  const Mfma32Lds L(lds_all, GEN != 0, CPT, nrung);
   const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
-  double* red = lbox + 64 + wave * 128;
-  // GEN: per-dimension tables of the state space and the prior, natural index (after the waves' reduction slots)
-  double* gtab = lbox + 64 + 4 * 128;                   // bmin | bmax | plo | phi | pcoef | mean, 32 each
-  int* gint = reinterpret_cast<int*>(gtab + 6 * 32);    // blo | bhi | ptype, 32 each
-  double* red2 = reinterpret_cast<double*>(gint + 3 * 32) + wave * 128;   // the prior's partial products
+  double* red = L.red + wave * 128;
+  double* red2 = L.red2 + wave * 128;   // the prior's partial products
   // the scales of the rung's mixture members (at most 64), this wave's copy: in the half of red2 the prior's products never reach (they are
   // GEN 2's, which works one group per pass: indices below 64), or all of it in the builds without them
   double* mixs = red2 + (GEN == 2 ? 64 : 0);
-  // all boundaries open or `limit` (the usual case): enforcing is a box test -- lower | upper limits in row layout
-  double* ebox = reinterpret_cast<double*>(gint + 3 * 32) + 4 * 128;
   const int q = l >> 4, j = l & 15;
-  const double* pimg = ptile + l;
-  const mf_d2* box = reinterpret_cast<const mf_d2*>(lbox) + q;   // lo piece t at 4t, hi piece t at 16 + 4t (row layout)
-  const mf_d2* ebx = reinterpret_cast<const mf_d2*>(ebox) + q;
+  const double* pimg = L.ptile + l;
+  const mf_d2* box = reinterpret_cast<const mf_d2*>(L.lbox) + q;   // lo piece t at 4t, hi piece t at 16 + 4t (row layout)
+  const mf_d2* ebx = reinterpret_cast<const mf_d2*>(L.ebox) + q;
 
   // ---- the block's tables: staged ONCE.  The grid is persistent -- a block per resident slot of the chip, each walking
   //      the launch's 256-chain tiles with stride gridDim.x -- so the 26 KB of tables (Box-Muller, precision tiles, box) are
@@ -125,26 +118,25 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   }
   auto stage_tables = [&]() {
 #pragma unroll
-    for (int t = 0; t < BM_TABLE_DOUBLES / 512; ++t) reinterpret_cast<bm_d2*>(lds_all)[threadIdx.x + 256 * t] = st_bm[t];
+    for (int t = 0; t < BM_TABLE_DOUBLES / 512; ++t) reinterpret_cast<bm_d2*>(L.bm)[threadIdx.x + 256 * t] = st_bm[t];
 #pragma unroll
-    for (int t = 0; t < 3; ++t) ptile[threadIdx.x + 256 * t] = st_p[t];
-    if (threadIdx.x < 64) lbox[threadIdx.x] = st_box;
+    for (int t = 0; t < 3; ++t) L.ptile[threadIdx.x + 256 * t] = st_p[t];
+    if (threadIdx.x < 64) L.lbox[threadIdx.x] = st_box;
     if (GEN && threadIdx.x < 32) {
 #pragma unroll
-      for (int t = 0; t < 6; ++t) gtab[32 * t + threadIdx.x] = st_g[t];
+      for (int t = 0; t < 6; ++t) L.gtab[32 * t + threadIdx.x] = st_g[t];
 #pragma unroll
-      for (int t = 0; t < 3; ++t) gint[32 * t + threadIdx.x] = st_i[t];
+      for (int t = 0; t < 3; ++t) L.gint[32 * t + threadIdx.x] = st_i[t];
       const int pos = row_pos<32>(threadIdx.x);
-      ebox[pos] = st_i[0] == B_LIMIT ? st_g[0] : -__builtin_inf();
-      ebox[32 + pos] = st_i[1] == B_LIMIT ? st_g[1] : __builtin_inf();
+      L.ebox[pos] = st_i[0] == B_LIMIT ? st_g[0] : -__builtin_inf();
+      L.ebox[32 + pos] = st_i[1] == B_LIMIT ? st_g[1] : __builtin_inf();
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   };
   if (PERSIST) stage_tables();
 
   // CPT: the launch's rungs, their listed-walker counts as an inclusive prefix of 256-walker tiles (LDS, after everything else)
-  const int rung0 = p.c_begin / p.W, nrung = (p.c_end - p.c_begin) / p.W;
-  int* tpre = reinterpret_cast<int*>(GEN == 0 ? lbox + 64 + 4 * 128 : ebox + 64);   // [nrung] (CPT; the host sizes the LDS for it; the lean build has no general tables)
+  const int rung0 = p.c_begin / p.W;
   int ntiles = (p.c_end - p.c_begin + 255) >> 8;   // 256-chain tiles of this launch (ranges are multiples of 64)
   if constexpr (CPT) {
     // inclusive scan of ceil(count / 256) over the rungs: each thread sums a contiguous chunk, one wave scans the chunk totals
@@ -152,20 +144,19 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
     int loc = 0;
     for (int k = 0; k < per; ++k) {
       const int r = threadIdx.x * per + k;
-      if (r < nrung) { loc += (p.ccnt[rung0 + r] + 255) >> 8; tpre[r] = loc; }
+      if (r < nrung) { loc += (p.ccnt[rung0 + r] + 255) >> 8; L.tpre[r] = loc; }
     }
-    int* tsum = tpre + nrung;                       // [256] chunk totals -> exclusive offsets
-    tsum[threadIdx.x] = loc;
+    L.tsum[threadIdx.x] = loc;
     __syncthreads();
-    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = tsum[t]; tsum[t] = run; run += v; } tsum[256] = run; }
+    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = L.tsum[t]; L.tsum[t] = run; run += v; } L.tsum[256] = run; }
     __syncthreads();
-    const int off = tsum[threadIdx.x];
+    const int off = L.tsum[threadIdx.x];
     for (int k = 0; k < per; ++k) {
       const int r = threadIdx.x * per + k;
-      if (r < nrung) tpre[r] += off;
+      if (r < nrung) L.tpre[r] += off;
     }
     __syncthreads();
-    ntiles = tsum[256];
+    ntiles = L.tsum[256];
   }
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
   int c0, rl, w0, nact = 64, lbase = 0;
@@ -173,9 +164,9 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   if constexpr (CPT) {
     // the rung of compacted tile `tile`: first r with tpre[r] > tile (wave-uniform binary search in LDS)
     int lo = 0, hi = nrung - 1;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (tpre[mid] > tile) hi = mid; else lo = mid + 1; }
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (L.tpre[mid] > tile) hi = mid; else lo = mid + 1; }
     const int r = __builtin_amdgcn_readfirstlane(lo);
-    const int kb = tile - (r ? tpre[r - 1] : 0);
+    const int kb = tile - (r ? L.tpre[r - 1] : 0);
     rl = rung0 + r;
     const int start = (kb * 4 + wave) * 64, cnt = p.ccnt[rl];
     if (start >= cnt) continue;                        // (only wave-level barriers below)
@@ -298,8 +289,8 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
       for (int gg = 0; gg < GG; ++gg) {
         const uint32_t stream = (uint32_t)((wq[GG * gp + gg] & wmask) + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg;
         const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + 4 * hb + qd));
-        boxmuller(o.v0, o.v1, (const double*)lds_all, z[gg][0], z[gg][1]);
-        boxmuller(o.v2, o.v3, (const double*)lds_all, z[gg][2], z[gg][3]);
+        boxmuller(o.v0, o.v1, L.bm, z[gg][0], z[gg][1]);
+        boxmuller(o.v2, o.v3, L.bm, z[gg][2], z[gg][3]);
         if (GENX && (meta[gg] & 0xFF) != 0) {   // one-dimensional move: every other normal is dropped (proposal_distribution.hh:197-205)
 #pragma unroll
           for (int sl = 0; sl < 4; ++sl)
@@ -363,8 +354,8 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
           for (int u = 0; u < 2; ++u) {
             const int d = q + 4 * (m + u);
             if (p.has_bounds && !p.bounds_box)
-              vok = vok & boundary_enforce(gint[d], gint[32 + d], gtab[d], gtab[32 + d], xp[gg][m + u]);
-            if (!boxed) pp *= prior_pdf(gint[64 + d], gtab[64 + d], gtab[96 + d], gtab[128 + d], xp[gg][m + u]);
+              vok = vok & boundary_enforce(L.gint[d], L.gint[32 + d], L.gtab[d], L.gtab[32 + d], xp[gg][m + u]);
+            if (!boxed) pp *= prior_pdf(L.gint[64 + d], L.gtab[64 + d], L.gtab[96 + d], L.gtab[128 + d], xp[gg][m + u]);
           }
         }
         ok = ok & !(xp[gg][m] < lo.x) & !(xp[gg][m] > hi.x) & !(xp[gg][m + 1] < lo.y) & !(xp[gg][m + 1] > hi.y);
@@ -392,7 +383,7 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
     // ---- stage 4: S = P2 x Y, Y = X' (- mean), and the four partial dot products of each chain
     if (PTM_MFMA_PRIO == 1) __builtin_amdgcn_s_setprio(2);
     if (PTM_MFMA_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-    auto yv = [&](int gg, int m) -> double { return (GENX && p.has_mean) ? xp[gg][m] - gtab[160 + q + 4 * m] : xp[gg][m]; };
+    auto yv = [&](int gg, int m) -> double { return (GENX && p.has_mean) ? xp[gg][m] - L.gtab[160 + q + 4 * m] : xp[gg][m]; };
     mf_d4 sacc[GG][2];
 #pragma unroll
     for (int gg = 0; gg < GG; ++gg) {

@@ -99,9 +99,7 @@ static hipError_t launch_kind(const Dev& p, const SweepPlan& s, hipStream_t st, 
   switch (s.family) {
 #if PTM_DP == 32
     case FAM_MFMA32: {
-      // LDS: tables | P2 tiles | box | 4 x 128 reduction slots | (general: 6 x 32 doubles + 3 x 32 ints + 4 x 128 slots) | (compacted: the rungs' list ends)
-      const size_t lds = (BM_TABLE_DOUBLES + 12 * 64 + 64 + 4 * 128) * sizeof(double) + (s.mgen == 0 ? 0 : (6 * 32 + 48 + 4 * 128 + 64) * sizeof(double)) +
-                         (s.compacted ? ((size_t)chains / p.W + 260) * sizeof(int) : 0);
+      const size_t lds = Mfma32Lds(nullptr, s.mgen != 0, s.compacted, chains / p.W).bytes;
       constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // (the plan never names a diagonal build of this family)
       const void* kf = mfma32_kernel_of<MK>(s);
       if (!kf) return hipErrorNotSupported;
@@ -125,10 +123,10 @@ static hipError_t launch_kind(const Dev& p, const SweepPlan& s, hipStream_t st, 
       constexpr int MK = KIND == KIND_DIAG ? KIND_LOWER : KIND;   // (the plan never names a diagonal build of this family)
 #if PTM_DP == 64
       constexpr int threads = 256;
-      const size_t lds = (size_t)m64_lds_doubles() * sizeof(double);
+      const size_t lds = Mfma64Lds(nullptr).bytes;
 #else
       constexpr int threads = M128_THREADS;
-      const size_t lds = (size_t)m128_lds_doubles() * sizeof(double);
+      const size_t lds = Mfma128Lds(nullptr).bytes;
 #endif
       static int resident = 0;   // (per factor kind; of the build with the most registers: the same grid for all four)
       if (!resident) {
@@ -157,8 +155,7 @@ static hipError_t launch_kind(const Dev& p, const SweepPlan& s, hipStream_t st, 
     }
 #if PTM_DP <= 32
     case FAM_GENERAL: {
-      // the 20 KB of Box-Muller tables every variant stages; UNI builds stage one copy of the rung's factor per wave too (4 waves per block)
-      const size_t lds = BM_TABLE_DOUBLES * sizeof(double) + ((s.uni && KIND != KIND_DIAG) ? (size_t)4 * p.prop_stride * sizeof(double) : 0);
+      const size_t lds = GeneralLds(nullptr, s.uni && KIND != KIND_DIAG, p.prop_stride).bytes;
       const AdaArgs none = AdaArgs();
       void* args[] = {(void*)&p, (void*)(s.ada ? &ada : &none)};
       return hipLaunchKernel(general_kernel_of<KIND>(s), dim3((chains + 255) / 256), dim3(256), args, lds, st);

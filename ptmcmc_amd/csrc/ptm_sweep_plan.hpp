@@ -214,7 +214,7 @@ inline int format_sweep_name(const SweepPlan& s, char* b, size_t n) {
 }
 
 // Small ladders (rungs x padded dimensions <= 256 lanes, device target and proposals): whole PT steps in one launch, a block per
-// walker-ladder (ptm_fused_kernel.hpp).  decide_lds: decide_lds_bytes of the engine's exchange phase, which shares the block's LDS.
+// walker-ladder (ptm_fused_kernel.hpp).  decide_lds: DecideLds' bytes of the engine's exchange phase, which shares the block's LDS.
 struct StepFacts {
   int DP, Nt, W;
   bool user_like, host_prop, ada, time_kernels;

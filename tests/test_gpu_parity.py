@@ -340,7 +340,10 @@ def test_add_every_n_history_counters():
                                                  (32, 8, 64, E.PROP_LOWER, 1, 0.45, (0.03, 0.5)),
                                                  (5, 7, 3, E.PROP_DENSE, 2, 0.45, (0.05, 0.0)),
                                                  (18, 8, 5, E.PROP_LOWER, 2, 0.45, (0.03, 1.0)),
-                                                 (4, 900, 64, E.PROP_DIAG, 2, 0.45, (0.01, 0.0))])
+                                                 (4, 900, 64, E.PROP_DIAG, 2, 0.45, (0.01, 0.0)),
+                                                 # the exchange kernel's perm / inv / move list in the space of the trial operands (DecideLds::alias_rule),
+                                                 # with the history tail behind them; 520 ladders of two workgroups: too many for the ladder kernel
+                                                 (4, 72, 520, E.PROP_DIAG, 2, 0.5, 0.02)])
 def test_history_rows_match_the_oracle(D, Nt, W, kind, N, sr, ev):
     """What MH_chain::add_state pushes every add_every_N-th call (chain.cc:935-946): state, llike, lprior, Naccept,
     Ntries, last_type -- including the rows a rung holds BETWEEN two exchanges of one step (quirk Q6)."""
@@ -366,6 +369,8 @@ def test_history_rows_match_the_oracle(D, Nt, W, kind, N, sr, ev):
         steps -= 2
     eng.step(steps); eng.sync()
     lad.pt_step(steps)
+    if W == 520:
+        assert eng.step_kernel_name.startswith("decide_kernel"), eng.step_kernel_name
     if ev:
         steps += 2
         assert np.array_equal(eng.invtemps(), lad.betaw)
@@ -561,7 +566,11 @@ def test_scale_mixture_proposals(D, Nt, W, kind, K):
 @pytest.mark.parametrize("D,Nt,W,kind,sr,rate", [(4, 8, 3, E.PROP_DENSE, 0.3, 0.05), (32, 40, 64, E.PROP_LOWER, 0.45, 0.01),
                                                  (16, 70, 64, E.PROP_DIAG, 0.2, 0.02), (32, 1024, 64, E.PROP_LOWER, 0.1, 0.01),
                                                  (5, 2, 64, E.PROP_DENSE, 0.4, 0.05), (3, 3, 7, E.PROP_DIAG, 0.5, 0.1),
-                                                 (20, 9, 3, E.PROP_DENSE, 0.3, 0.05)])   # lanes kernel
+                                                 (20, 9, 3, E.PROP_DENSE, 0.3, 0.05),    # lanes kernel
+                                                 # either side of the exchange kernel's alias rule (DecideLds::alias_rule: perm / inv / the move list
+                                                 # in the space of the trial operands from 72 rungs on); 520 ladders of two workgroups are more than
+                                                 # the persistent ladder kernel holds, so the steps take the exchange kernel
+                                                 (4, 71, 520, E.PROP_DIAG, 0.5, 0.02), (4, 72, 520, E.PROP_DIAG, 0.5, 0.02)])
 def test_evolving_ladders_match_the_oracle(D, Nt, W, kind, sr, rate):
     """parallel_tempering_chains::evolve_temps (chain.hh:302-307): every accepted exchange pries its temperature gap apart
     and renormalises the ladder (pry_temps, chain.cc:1501-1518,1809-1846), so each walker's ladder owns its temperatures.
@@ -579,6 +588,8 @@ def test_evolving_ladders_match_the_oracle(D, Nt, W, kind, sr, rate):
         be, bo = eng.invtemps(), lad.betaw
         assert np.array_equal(be, bo), (np.abs(be - bo).max(), np.argwhere(be != bo)[:4].tolist())
         assert np.array_equal(eng.lpost, PU.to_engine_order(lad.lpost, Nt, W))
+    if W == 520:
+        assert eng.step_kernel_name.startswith("decide_kernel"), eng.step_kernel_name
     t, a = eng.swap_counts()
     assert np.array_equal(a, np.asarray(lad._arr(lad.s.contents.swap_accept_count, (W, max(Nt - 1, 1)), np.int64)))
     be = eng.invtemps()
@@ -593,7 +604,9 @@ def test_evolving_ladders_match_the_oracle(D, Nt, W, kind, sr, rate):
 
 @pytest.mark.parametrize("D,Nt,W,kind,sr,rate,cut", [(4, 8, 3, E.PROP_DENSE, 0.3, 0.05, 0.0), (32, 40, 64, E.PROP_LOWER, 0.45, 0.01, 2.0),
                                                      (3, 7, 5, E.PROP_DIAG, 0.45, 0.02, 0.0), (20, 9, 3, E.PROP_DENSE, 0.3, 0.05, 1.0),
-                                                     (2, 300, 2, E.PROP_DIAG, 0.3, 0.01, 0.0), (6, 1100, 1, E.PROP_DIAG, 0.1, 0.01, 3.0)])
+                                                     (2, 300, 2, E.PROP_DIAG, 0.3, 0.01, 0.0), (6, 1100, 1, E.PROP_DIAG, 0.1, 0.01, 3.0),
+                                                     # either side of the exchange kernel's alias rule (DecideLds::alias_rule), with the cut's tail
+                                                     (4, 71, 3, E.PROP_DIAG, 0.5, 0.02, 0.0), (4, 72, 3, E.PROP_DIAG, 0.5, 0.02, 0.0)])
 def test_evolving_ladders_with_a_posterior_ordering_cut_match_the_oracle(D, Nt, W, kind, sr, rate, cut):
     """evolve_temps(rate, lpost_cut >= 0) (chain.hh:302-307; pry_temps chain.cc:1809-1846): every pry ALSO widens each gap whose
     two chains' current log-posteriors are out of order by more than cut * invtemp (:1819-1827) -- any gap of the ladder, so
