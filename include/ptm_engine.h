@@ -239,7 +239,12 @@ int ptm_set_proposal_callback(ptm_engine* e, ptm_propose_batch_fn propose, ptm_p
  * r * n_walkers + w: the states MH_chain::initialize(n) saved in FRONT of the start state (chain.cc:846-876: n_init_extra = n - 1,
  * oldest first), or NULL with n_init_extra = 0.  Needs dim <= 128 and the whole ladder on this engine (rung_count == n_rungs; populations
  * split by walkers are fine: PTM_ERR_UNSUPPORTED on a rung shard, whose top rung's history cannot be complete).  q == NULL switches it off.  Host-side draws with temperature
- * mixing or unlikely_alpha stay possible through ptm_set_proposal_callback. */
+ * mixing or unlikely_alpha stay possible through ptm_set_proposal_callback.
+ * Which kernel draws it: the persistent ladder, fused small-ladder, lanes and general kernels, and for 17..32 dimensions with whole
+ * waves per rung, an all-uniform prior and open / `limit` bounds also the matrix cores (de_mfma32_kernel: the Gaussian members' products
+ * on the f64 matrix cores, the evolution's states formed in the same layout) -- by default for populations of more than 2^21 lanes
+ * (chains x 32), where the lanes kernel used to hand over to the general one; PTM_DE_MFMA=1 in the environment gives it every
+ * eligible population, PTM_DE_MFMA=0 none.  The chains are the same bit for bit whichever kernel draws. */
 typedef struct ptm_de_params {
   double snooker;         /* probability of a snooker move (differential_evolution's first constructor argument; sampler: 0.1) */
   double gamma_one_frac;  /* probability of gamma = 1 in a parallel move (de_g1_frac: 0.3) */
@@ -262,7 +267,8 @@ int ptm_set_proposal_de(ptm_engine* e, const ptm_de_params* q, int n_init_extra,
  * Unlike differential evolution it needs no history: rung shards (mixture), walker splits, ptm_sweep_rungs and the propose / accept
  * passes of user likelihoods all carry it (the accept pass makes member and ratio anew).  Steps of such an engine take the exchange
  * kernel and the lanes or the general sweep kernel, as with an adaptive set: never the matrix-core, fused small-ladder or persistent
- * kernels -- a 32-dimensional population of whole waves per rung runs where it runs with differential evolution.
+ * kernels -- a 32-dimensional population of whole waves per rung runs where it ran with differential evolution before that moved to
+ * the matrix cores (de_mfma32_kernel, see ptm_set_proposal_de): on the lanes kernel, past 2^21 lanes on the general one.
  * Every argument is checked before anything changes.  PTM_ERR_INVALID: member out of range, the nested set, or a member of negative
  * scale (differential evolution); host-side proposals are set.  PTM_ERR_UNSUPPORTED: a flat prior dimension, or a prior callback
  * (ptm_set_prior_callback) -- also reported by the next step if the prior changes to one of these afterwards. */

@@ -19,6 +19,7 @@
 #include "../../include/ptm_engine.h"
 #include "ptm_aux_kernels.hpp"
 #include "ptm_box_prefilter.hpp"
+#include "ptm_de_mfma_kernel.hpp"
 #include "ptm_devlike_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
@@ -1334,8 +1335,9 @@ static inline bool user_like(const ptm_engine* e) { return e->cb != nullptr || e
 
 // the build a sweep over `chains` chains runs on (ptm_sweep_plan.hpp); step_sweep_plan: the sweep of a PT step -- every local rung, after an
 // exchange phase -- which is what the engine prepares for (row labels, temperatures) and what it reports by name
-static SweepPlan sweep_plan(const ptm_engine* e, long long chains, bool touched) {
+static SweepFacts sweep_facts(const ptm_engine* e, long long chains, bool touched) {
   SweepFacts f;
+  memset(&f, 0, sizeof f);
   f.DP = e->DP; f.W = e->W; f.chains = chains; f.nloc = e->nloc;
   f.kind = e->prop_kind == PTM_PROP_DIAG ? PLAN_DIAG : (e->prop_kind == PTM_PROP_LOWER ? PLAN_LOWER : PLAN_DENSE);
   f.has_bounds = e->has_bounds; f.bounds_box = e->bounds_box; f.all_uniform = e->all_uniform; f.has_mean = e->has_mean; f.any_oned = e->any_oned;
@@ -1345,9 +1347,15 @@ static SweepPlan sweep_plan(const ptm_engine* e, long long chains, bool touched)
   f.de = e->de_on || e->prior_member >= 0;   // (a prior member routes as differential evolution does: only the lanes and general kernels draw it)
   f.mode = f.user_like ? 1 : 0;   // (the propose and accept passes run on one build)
   f.touched = touched;
-  return plan_sweep(f, sweep_env());
+  f.prior_draw = e->prior_member >= 0; f.history = e->hist.rungs > 0 && e->hist.rungs == e->nloc;
+  return f;
 }
+static SweepPlan sweep_plan(const ptm_engine* e, long long chains, bool touched) { return plan_sweep(sweep_facts(e, chains, touched), sweep_env()); }
 static SweepPlan step_sweep_plan(const ptm_engine* e) { return sweep_plan(e, e->Nc, true); }
+// Differential evolution on the matrix cores: does de_mfma32_kernel (ptm_de_mfma_kernel.hpp) run the sweep over `chains` chains in place of
+// the plan's kernel?  Asked here for PT steps, ptm_sweep and ptm_sweep_rungs alike (launch_sweep) and for the reported name.  The
+// preparations stay the plan's -- a general sweep: chain-indexed temperatures kept current, no row labels, no partition.
+static bool de_mfma_sweep(const ptm_engine* e, long long chains) { return e->de_on && de_mfma_applies(sweep_facts(e, chains, true), sweep_env()); }
 
 static bool lean_ev_sweeps(const ptm_engine* e) { return reads_ladder_major_beta(step_sweep_plan(e)); }
 
@@ -1633,7 +1641,12 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   const AdaArgs ada = make_ada(e);
   const DpLaunch* dl = dp_launch(e->DP);
   if (!dl) return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
-  auto launch = [&](const Dev& q) { return dl->sweep(q, plan, e->stream, ada); };
+  const bool de_mfma = de_mfma_sweep(e, p.c_end - p.c_begin);
+  if (de_mfma && (compact || plan.family == FAM_MFMA32)) return fail(PTM_ERR_HIP, "internal: differential evolution on the matrix cores beside a matrix-core plan");
+  auto launch = [&](const Dev& q) {
+    if (de_mfma) return launch_de_mfma32(q, e->prop_kind == PTM_PROP_DENSE ? KIND_DENSE : KIND_LOWER, e->betaC != nullptr, e->stream);
+    return dl->sweep(q, plan, e->stream, ada);
+  };
 
   size_t npick = 0;
   if (e->pcb) {
@@ -3185,7 +3198,8 @@ extern "C" int ptm_calibrate(ptm_engine* e, ptm_calibration* out) {
 extern "C" const char* ptm_sweep_kernel_name(ptm_engine* e) {
   if (!e) return "";
   char b[96];
-  format_sweep_name(step_sweep_plan(e), b, sizeof b);   // (in PT steps; the plain sweeps of a big population visit every chain)
+  if (de_mfma_sweep(e, e->Nc)) format_de_mfma_name(e->prop_kind == PTM_PROP_DENSE ? KIND_DENSE : KIND_LOWER, e->betaC != nullptr, b, sizeof b);
+  else format_sweep_name(step_sweep_plan(e), b, sizeof b);   // (in PT steps; the plain sweeps of a big population visit every chain)
   e->kname = b;
   if (e->dfn) e->kname += " + device likelihood";   // (propose pass, pack, the user's work, scatter, accept pass)
   return e->kname.c_str();

@@ -68,9 +68,120 @@ typedef double mf_d2 __attribute__((ext_vector_type(2)));
 // CPT (lean and GEN 1 builds without history): the sweep visits the moving chains alone, through the per-rung lists of partition_kernel
 // (ptm_kernels.hpp) -- tiles of 256 LISTED walkers of one rung, enumerated rung by rung; lane l of a wave works for the l-th
 // listed walker of its group instead of walker w0 + l.
-template <int KIND, bool HIST, int GEN, bool EV = false, bool CPT = false>   // GEN: 0 lean, 1 box boundaries + uniform prior (+ mean, 1-D moves, mixtures), 2 everything,
-                                                                            //      3 box boundaries + uniform prior and nothing else (GEN 1 without what it only carries)
-__global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 0 && GEN == 2 && KIND == KIND_LOWER) ? 4 : ((GEN == 1 && CPT) ? PTM_MFMA_G1C_WAVES : PTM_MFMA_GEN_WAVES)))) void sweep_mfma32_kernel(const Dev p) {
+// ---- differential evolution in the 32-D matrix-core kernel (de_mfma32_kernel, ptm_de_mfma_kernel.hpp) ----------------------------
+// What de_draw (ptm_kernels.hpp) does on one lane is split here between the chain's own lane and its four matrix lanes:
+//   the chain's lane (lane l = chain l)  draws the move's uniforms, picks the rows, and -- for a snooker move -- forms axis2, proj, fz2
+//                                        and the log-Hastings ratio.  These are sums over the dimensions IN INDEX ORDER, so one lane adds
+//                                        them up as de_draw does (a 4-lane reduction would add in another order and lose bit-exactness);
+//                                        it reads the rows eight dimensions (64 contiguous bytes) at a time;
+//   the four matrix lanes (q, j)         get the two row indices and the coefficient from it (ds_bpermute, as the axis and the member
+//                                        travel) and form their eight dimensions of the proposed state in the accumulator layout, with
+//                                        de_draw's operations in de_draw's order (every product rounded before its sum).
+// kind: 0 no DE move, 1 parallel (x + z1 gamma) + z2 (-gamma): i0 = z1, i1 = z2, coef = gamma;  2 snooker x + (x + z (-1)) proj: i0 = z,
+// coef = proj.  A row index counts de_init's rows first, then the ring's (de_row).
+struct DeMove { int kind, i0, i1; double coef, hast; };
+
+__device__ __forceinline__ const double* de_row(const Dev& p, int r, int c) {
+  if (r < p.de_init_extra) return p.de_init + ((size_t)r * p.Nc + c) * 32;
+  return p.hist.x + hist_slot(p.hist, (long long)(r - p.de_init_extra), c) * 32;
+}
+// dimensions 8k .. 8k+7 of a stored row: positions 8k .. 8k+7 hold them as (d, d+4) pairs (row_pos)
+__device__ __forceinline__ void de_chunk(const double* row, int k, double (&o)[8]) {
+  const mf_d2* v = reinterpret_cast<const mf_d2*>(row + 8 * k);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { const mf_d2 t = v[s]; o[s] = t.x; o[4 + s] = t.y; }
+}
+// the chain-lane half of de_draw<32>: same uniforms, same row picks, same error bits, same sums
+__device__ __forceinline__ DeMove de_mfma_scalars(const Dev& p, int c, uint32_t stream, unsigned int nh0) {
+  const int D = p.D;
+  const long long saved = 1 + (long long)((nh0 + (unsigned int)p.add_every_n - 1u) / (unsigned int)p.add_every_n);   // rows of the ring so far
+  const long long rows = p.de_init_extra + saved;
+  auto pick = [&](double u) -> int {
+    const long long spare = rows - 100ll * D;
+    const long long first = (spare * (1 - p.de_ignore) > 10ll * D) ? (long long)(spare * p.de_ignore) : 0;
+    const long long r = (long long)(first + (rows - first) * u);
+    if (r >= p.de_init_extra && saved - (r - p.de_init_extra) > p.hist.cap) atomicOr(p.err, 64);   // the ring has lost that row
+    return (int)r;
+  };
+  DeMove mv = {1, 0, 0, 0.0, 0.0};
+  const u32x4 b0 = draw_block(p.seed, TAG_MH, stream, p.step, 0x0DE00000u);
+  if (!(p.de_snooker > u01(b0.v0))) {                  // draw_standard
+    mv.coef = u01(b0.v1) < p.de_gamma_one ? 1.0 : p.de_gamma_std;
+    mv.i0 = pick(u01(b0.v2));
+    mv.i1 = pick(u01(b0.v3));
+    return mv;
+  }
+  mv.kind = 2;                                         // draw_snooker
+  const double gamma = (1.2 + u01(b0.v1)) / p.de_gamma_div;
+  const double* row = p.x + (size_t)c * 32;
+  const int nk = (D + 7) >> 3;
+  double axis2 = 0.0;
+  for (int tries = 0; axis2 == 0.0; ++tries) {         // the history repeats states: z must differ from the current state
+    if (tries > 1000) {                                // (the reference exits here; the engine raises an error bit and rejects the move:
+      atomicOr(p.err, 128);                            //  proj = 0 leaves the matrix lanes with the current state, NaN rejects it)
+      mv.coef = 0.0;
+      mv.hast = __builtin_nan("");
+      return mv;
+    }
+    const u32x4 bt = draw_block(p.seed, TAG_MH, stream, p.step, 0x0DE00001u + (uint32_t)tries);
+    mv.i0 = pick(u01(bt.v0));
+    const double* z = de_row(p, mv.i0, c);
+    axis2 = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < nk; ++k) {
+      double xr[8], zr[8];
+      de_chunk(row, k, xr); de_chunk(z, k, zr);
+#pragma unroll
+      for (int s = 0; s < 8; ++s)
+        if (8 * k + s < D) { const double a = xr[s] + zr[s] * (-1.0); axis2 = axis2 + a * a; }
+    }
+  }
+  const double* z = de_row(p, mv.i0, c);
+  const double* z1 = de_row(p, pick(u01(b0.v2)), c);
+  const double* z2 = de_row(p, pick(u01(b0.v3)), c);
+  double proj = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < nk; ++k) {
+    double xr[8], zr[8], ar[8], br[8];
+    de_chunk(row, k, xr); de_chunk(z, k, zr); de_chunk(z1, k, ar); de_chunk(z2, k, br);
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+      if (8 * k + s < D) {
+        const double a = ar[s] * gamma, b = br[s] * (-gamma);
+        const double diff = a + b;
+        const double ax = xr[s] + zr[s] * (-1.0);
+        proj = proj + diff * ax;
+      }
+  }
+  proj = proj / axis2;
+  double fz2 = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < nk; ++k) {
+    double xr[8], zr[8];
+    de_chunk(row, k, xr); de_chunk(z, k, zr);
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+      if (8 * k + s < D) {
+        const double ax = xr[s] + zr[s] * (-1.0);
+        const double t = ax * proj;
+        const double y = xr[s] + t;
+        const double f = y + zr[s] * (-1.0);
+        fz2 = fz2 + f * f;
+      }
+  }
+  mv.coef = proj;
+  mv.hast = (dlog(fz2) - dlog(axis2)) * (double)(D - 1) / 2.0;
+  return mv;
+}
+
+// DE (the GEN 1 build with history, not compacted: de_mfma32_kernel, ptm_de_mfma_kernel.hpp): a member of the proposal set is differential
+// evolution from the chain's own saved history.  The body is shared -- sweep_mfma32_kernel is mfma32_body with DE = false, and everything
+// differential evolution adds stands under `if constexpr (DE)`.
+// GEN: 0 lean, 1 box boundaries + uniform prior (+ mean, 1-D moves, mixtures), 2 everything,
+//      3 box boundaries + uniform prior and nothing else (GEN 1 without what it only carries)
+template <int KIND, bool HIST, int GEN, bool EV, bool CPT, bool DE>
+__device__ __forceinline__ void mfma32_body(const Dev p) {   // (by value, as a kernel takes it: through a reference nine of the thirty builds came out with other register and spill counts)
+  static_assert(!DE || (GEN == 1 && HIST && !CPT), "differential evolution: the box-bounds build with history, every chain visited");
   constexpr bool PERSIST = GEN == 0 || PTM_MFMA_GEN_PERSIST != 0 || CPT;   // (a compacted sweep walks its tiles: an idle tile must cost nothing)
   static_assert(!CPT || ((GEN <= 1 || GEN == 3) && !HIST), "the compacted sweep exists for the lean and the box-bounds builds, without history");
   constexpr bool GENX = GEN == 1 || GEN == 2;   // the builds that carry a mean, one-dimensional moves and scale mixtures
@@ -233,7 +344,10 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   // ... and its member of a scale mixture (proposal_distribution_set::draw, proposal_distribution.cc:99-129), packed into ONE register:
   // (axis + 1) | member << 8.  The member's scale is looked up where it is used, in this wave's copy of the rung's scales in LDS
   // (as axis / member / scale of "my" chain and of the pass's chains these were ten registers of a kernel at its register cap)
+  // DE: bits 6-7 of the axis byte (an axis + 1 is at most 32) carry the kind of the chain's differential-evolution move (DeMove)
+  constexpr int AXIS_MASK = DE ? 0x3F : 0xFF;
   int my_meta = 0;
+  bool my_de = false;   // DE: the picked member is differential evolution (a negative scale)
   if (GENX) {
     double f = as_c(p.onedfrac)[rl];
     int kmix = 0, axis1 = 0;
@@ -243,6 +357,12 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
       kmix = p.mix_K - 1;
       for (int k = p.mix_K - 2; k >= 0; --k)
         if (xs < mx[3 * k]) kmix = k;
+      if constexpr (DE) {
+        // a differential evolution that is not ready yet (fewer than 10 D saved rows) is passed over, as
+        // proposal_distribution_set::draw passes over it (proposal_distribution.cc:111): the next member's bin is met
+        if (mx[3 * kmix + 1] < 0 && kmix + 1 < p.mix_K && !de_ready(p, nhist0)) kmix += 1;
+        my_de = mx[3 * kmix + 1] < 0;
+      }
       f = mx[3 * kmix + 2];
       if (l < p.mix_K) mixs[l] = mx[3 * l + 1];
     }
@@ -253,6 +373,14 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   if (!PERSIST) {   // the tables go to LDS behind the tile's first loads; the block meets once
     stage_tables();
     if (!live) break;
+  }
+  // DE: the chain's own lane draws its move (de_mfma_scalars).  A chain reads only ITS OWN column of the ring (and of de_init), and only
+  // rows saved before this step; this step's row of the column is written further down by the same wave, after the matrix lanes of the
+  // chain's pass have read theirs -- program order within the wave is all the ordering there is to keep, no other wave touches the column.
+  DeMove my_mv = {0, 0, 0, 0.0, 0.0};
+  if constexpr (DE) {
+    if (my_de && !tc) my_mv = de_mfma_scalars(p, c, (uint32_t)(wl + p.w_off) * (uint32_t)p.Nt + (uint32_t)rg, nhist0);
+    my_meta |= my_mv.kind << 6;
   }
   // (a generic lambda called with compile-time pass numbers: `#pragma unroll` gives up on a body of this size in the
   //  general build, and a pass number known only at run time costs dynamic register indexing)
@@ -282,6 +410,32 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
 #pragma unroll
       for (int gg = 0; gg < GG; ++gg) meta[gg] = __builtin_amdgcn_ds_bpermute(4 * (PL * gp + 16 * gg + j), my_meta);
     }
+    // DE: the move of chain (GG gp + gg, j) from its own lane -- row indices and coefficient -- and this lane's pieces of the rows, asked
+    // for here so that they travel while the normals are drawn
+    double de_cf[GG];
+    mf_d2 de_a[GG][4], de_b[GG][4];
+    if constexpr (DE) {
+#pragma unroll
+      for (int gg = 0; gg < GG; ++gg) {
+        const int src = 4 * (PL * gp + 16 * gg + j);
+        const int i0 = __builtin_amdgcn_ds_bpermute(src, my_mv.i0), i1 = __builtin_amdgcn_ds_bpermute(src, my_mv.i1);
+        de_cf[gg] = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(my_mv.coef)), __builtin_amdgcn_ds_bpermute(src, __double2loint(my_mv.coef)));
+        const int dk = (meta[gg] >> 6) & 3;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) de_a[gg][t] = de_b[gg][t] = mf_d2{0.0, 0.0};
+        if (dk) {
+          const int cg = c0 + PL * gp + 16 * gg + j;
+          const mf_d2* za = reinterpret_cast<const mf_d2*>(de_row(p, i0, cg)) + q;   // piece t at [4t], as a state's row
+#pragma unroll
+          for (int t = 0; t < 4; ++t) de_a[gg][t] = za[4 * t];
+          if (dk == 1) {
+            const mf_d2* zb = reinterpret_cast<const mf_d2*>(de_row(p, i1, cg)) + q;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) de_b[gg][t] = zb[4 * t];
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int hb = 0; hb < 2; ++hb) {
       double z[GG][4];
@@ -291,10 +445,10 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
         const u32x4 o = draw_block(p.seed, TAG_MH, stream, p.step, (uint32_t)(1 + 4 * hb + qd));
         boxmuller(o.v0, o.v1, L.bm, z[gg][0], z[gg][1]);
         boxmuller(o.v2, o.v3, L.bm, z[gg][2], z[gg][3]);
-        if (GENX && (meta[gg] & 0xFF) != 0) {   // one-dimensional move: every other normal is dropped (proposal_distribution.hh:197-205)
+        if (GENX && (meta[gg] & AXIS_MASK) != 0) {   // one-dimensional move: every other normal is dropped (proposal_distribution.hh:197-205)
 #pragma unroll
           for (int sl = 0; sl < 4; ++sl)
-            if (16 * hb + 4 * q + sl + 1 != (meta[gg] & 0xFF)) z[gg][sl] = 0.0;
+            if (16 * hb + 4 * q + sl + 1 != (meta[gg] & AXIS_MASK)) z[gg][sl] = 0.0;
         }
         PTM_STAGE();   // one chain's draw at a time: the temporaries of two interleaved draws cost 40 registers
       }
@@ -344,6 +498,28 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
         } else {
           xp[gg][m] = v.x + acc[gg][m >> 2][m & 3];
           xp[gg][m + 1] = v.y + acc[gg][(m + 1) >> 2][(m + 1) & 3];
+        }
+        if constexpr (DE) {
+          // a differential-evolution move: the T Z product of this chain is dropped (the wave's Gaussian chains needed those MFMA
+          // instructions), the proposed state comes from the history rows -- state::scalar_mult then state::add, as de_draw has them
+          const int dk = (meta[gg] >> 6) & 3;
+          if (dk) {
+            const double cf = de_cf[gg];
+            const mf_d2 a = de_a[gg][t], b = de_b[gg][t];
+            double y0, y1;
+            if (dk == 1) {
+              const double t0 = a.x * cf, t1 = a.y * cf;
+              const double s0 = v.x + t0, s1 = v.y + t1;
+              const double u0 = b.x * (-cf), u1 = b.y * (-cf);
+              y0 = s0 + u0; y1 = s1 + u1;
+            } else {
+              const double ax0 = v.x + a.x * (-1.0), ax1 = v.y + a.y * (-1.0);
+              const double t0 = ax0 * cf, t1 = ax1 * cf;
+              y0 = v.x + t0; y1 = v.y + t1;
+            }
+            xp[gg][m] = q + 4 * m < p.D ? y0 : 0.0;           // (pad dimensions stay 0)
+            xp[gg][m + 1] = q + 4 * (m + 1) < p.D ? y1 : 0.0;
+          }
         }
         if (GEN && p.has_bounds && p.bounds_box) {   // boundary::enforce for open / limit sides (states.cc:53-55)
           const mf_d2 el = ebx[4 * t], eh = ebx[16 + 4 * t];
@@ -454,11 +630,20 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
         double newlike = p.like0 - 0.5 * quad;
         double newlpost = newlike * beta + newlprior;
         if (!want_like) newlike = newlpost = -__builtin_inf();
-        const double logH = newlpost - cur_lpost;
+        double logH = newlpost - cur_lpost;
         accept = valid;
+        if constexpr (DE) {
+          if (my_mv.kind) {                  // chain.cc:989-994: prop.log_hastings_ratio(), NaN => reject
+            if (my_mv.hast != my_mv.hast) accept = false;
+            logH = my_mv.hast + logH;
+          }
+        }
         if (accept && logH < 0) accept = log_u < logH;  // chain.cc:998-1001 (NaN stays accepted)
-        int type = (GENX && (my_meta & 0xFF) != 0) ? 1 : 0;
+        int type = (GENX && (my_meta & AXIS_MASK) != 0) ? 1 : 0;
         if (GENX && p.mix_K > 0) type = (my_meta >> 8) + 10 * type;   // proposal_distribution.cc:117
+        if constexpr (DE) {
+          if (my_mv.kind) type = (my_meta >> 8) + 10 * (my_mv.kind - 1);   // member + 10 * (0 parallel | 1 snooker)
+        }
         p.ntries[c] = ntries0 + 1;
         if (!CPT) p.nhist[c] = nhist0 + 1u;   // (compacted: the engine counts the step for everybody, ptm_aux_kernels.hpp)
         if (hist_on && nhist0 % (unsigned int)p.add_every_n == 0u) {
@@ -539,6 +724,11 @@ __global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 
   }
   if (!PERSIST) break;   // (one tile per block: the launch gives every tile its own block)
   }   // tiles
+}
+
+template <int KIND, bool HIST, int GEN, bool EV = false, bool CPT = false>
+__global__ __launch_bounds__(256, (GEN == 0 ? PTM_MFMA_WAVES : ((PTM_MFMA_GG == 0 && GEN == 2 && KIND == KIND_LOWER) ? 4 : ((GEN == 1 && CPT) ? PTM_MFMA_G1C_WAVES : PTM_MFMA_GEN_WAVES)))) void sweep_mfma32_kernel(const Dev p) {
+  mfma32_body<KIND, HIST, GEN, EV, CPT, false>(p);
 }
 #undef PTM_STAGE
 #undef PTM_SACC

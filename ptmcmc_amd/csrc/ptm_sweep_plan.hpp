@@ -25,17 +25,23 @@ struct SweepFacts {
   bool de, ada;         // differential evolution drawn on the device; an adaptive proposal set
   int mode;             // 0: a whole sweep, 1 / 2: the propose / accept pass around a user likelihood
   bool touched;         // an exchange phase ran since the last sweep
+  // (read by de_mfma_applies alone -- plan_sweep does not look at them; zero: as before they existed)
+  bool prior_draw;      // a member of the set draws from the prior (`de` is set for it too: it routes as differential evolution does)
+  bool history;         // the history ring records every local rung (what differential evolution draws from)
 };
 
 // the environment's say: PTM_FORCE_VALU set, non-empty and not "0" keeps every workload off the matrix cores and off the lanes
 // kernel's population rules (A/B measurements, tests); PTM_COMPACT=0 switches the compacted sweep off; PTM_BOX_PREFILTER=0 switches
 // the box pre-pass (ptm_box_prefilter.hpp) off, =1 gives it every rung of a sweep it is eligible for, unset: the estimate decides
 // (prefilter_flag below); PTM_PREFILTER_GRID=n (n >= 1) caps the pre-pass's grid at n blocks, so that a small population walks many
-// tiles per block as a big one does (tests; the results do not depend on it).  Read once per process.
+// tiles per block as a big one does (tests; the results do not depend on it); PTM_DE_MFMA=0 keeps differential evolution off the
+// matrix cores, =1 gives de_mfma32_kernel every population it is eligible for, unset: its population rule decides (de_mfma_applies
+// below).  Read once per process.
 struct SweepEnv {
   bool force_valu, compact_ok;
   int prefilter;        // 0: the estimate decides, 1: every eligible rung, -1: off
   int prefilter_grid;   // 0: the blocks the device holds at once, n >= 1: at most n blocks
+  int de_mfma;          // PTM_DE_MFMA -- 0 (unset): the population rule of de_mfma_applies decides, 1: every eligible population, -1 ("0"): off
 };
 inline const SweepEnv& sweep_env() {
   static const SweepEnv v = [] {
@@ -43,8 +49,10 @@ inline const SweepEnv& sweep_env() {
     const char* c = getenv("PTM_COMPACT");
     const char* b = getenv("PTM_BOX_PREFILTER");
     const char* g = getenv("PTM_PREFILTER_GRID");
+    const char* d = getenv("PTM_DE_MFMA");
     const long gn = (g && *g) ? strtol(g, nullptr, 10) : 0;
-    return SweepEnv{f && *f && *f != '0', !(c && *c == '0'), (b && *b) ? (*b == '0' ? -1 : 1) : 0, gn >= 1 ? (int)(gn < (1 << 20) ? gn : (1 << 20)) : 0};
+    return SweepEnv{f && *f && *f != '0', !(c && *c == '0'), (b && *b) ? (*b == '0' ? -1 : 1) : 0, gn >= 1 ? (int)(gn < (1 << 20) ? gn : (1 << 20)) : 0,
+                    (d && *d) ? (*d == '0' ? -1 : 1) : 0};
   }();
   return v;
 }
@@ -126,6 +134,23 @@ inline SweepPlan plan_sweep(const SweepFacts& f, const SweepEnv& env) {
   s.family = FAM_GENERAL;
   s.uni = uni; s.simple = simple; s.ada = ada;
   return s;
+}
+
+// Differential evolution on the matrix cores (de_mfma32_kernel, ptm_de_mfma_kernel.hpp): asked next to the plan, which stays what it
+// was -- where this holds, the engine launches that kernel in place of the plan's and prepares as for the plan's (a general sweep
+// that is not compacted).  The kernel is the box-bounds build of the 32-D matrix-core sweep with history, so: 32 padded dimensions,
+// whole waves per rung, a whole sweep on device target and proposals, a fixed set with differential evolution in it and no draw from
+// the prior, an all-uniform prior with open / `limit` bounds, history on.
+// Population: unset, PTM_DE_MFMA leaves it to chains x DP > 2^21 -- exactly where plan_sweep leaves the lanes kernel for the general
+// one with differential evolution, so the kernel only ever takes over from sweep_kernel<32, ...>; 1 takes every eligible population
+// (tests, measurements), 0 none.
+inline bool de_mfma_applies(const SweepFacts& f, const SweepEnv& env) {
+  if (env.de_mfma < 0 || env.force_valu) return false;
+  if (f.DP != 32 || (f.W % 64) != 0 || f.mode != 0) return false;
+  if (f.user_like || f.host_prop || f.ada) return false;
+  if (!f.de || f.prior_draw || f.mix_K <= 0 || !f.history) return false;
+  if (!(f.all_uniform && (!f.has_bounds || f.bounds_box))) return false;
+  return env.de_mfma > 0 || f.chains * f.DP > (1ll << 21);
 }
 
 // ---- which rungs the box pre-pass takes -------------------------------------------------------------------------------------
