@@ -32,6 +32,16 @@ extern "C" {
 
 typedef struct ptm_engine ptm_engine;
 
+/* The horizon.  The largest value of any chain's Ntries, Naccept or Nhist that the engine represents: the reference's own `int`
+ * (chain.hh:151-152).  ptm_restore refuses counters outside [0, PTM_COUNT_MAX]; every call that advances chains refuses
+ * (PTM_ERR_UNSUPPORTED, nothing queued, the engine stays usable) when it could take a counter past it: a call of n PT steps is
+ * refused if and only if  max over this engine's chains of max(Ntries, Nhist) + 2 n > PTM_COUNT_MAX  -- 2 being the most add_state
+ * calls one chain can make in one step (a rung in two exchange trials, chain.cc:1410-1537).  A step made in pieces (ptm_exchange_decide*,
+ * ptm_exchange_install, ptm_sweep_rungs, ptm_exchange_finish_and_sweep) is one step: its first call is the one that is asked.
+ * The remedy is a checkpoint that shifts the counters down: INTEGRATION.md, "The horizon".  The step count itself is 64 bits
+ * (56 of them reach the random streams) and has no limit a run can meet. */
+#define PTM_COUNT_MAX 2147483647
+
 typedef enum {
   PTM_OK = 0,
   PTM_ERR_INVALID = -1,      /* bad argument / call order */
@@ -293,7 +303,8 @@ int ptm_init_from_prior_k(ptm_engine* e, int k);
 int ptm_draw_prior_rows(ptm_engine* e, int k_begin, int n, double* x_out, double* ll_out, double* lp_out);
 
 /* ---- the hot path ------------------------------------------------------------------------------------- */
-/* n x { MH_chain::step for every chain } -- no exchange phase */
+/* n x { MH_chain::step for every chain } -- no exchange phase.  (This and every other call that advances chains:
+ * PTM_ERR_UNSUPPORTED at the horizon, see PTM_COUNT_MAX.) */
 int ptm_sweep(ptm_engine* e, int n);
 /* n x parallel_tempering_chains::step (chain.cc:1393-1571; single-shard engines: rung_count == n_rungs).  ASYNCHRONOUS: the call
  * queues work on the engine's stream and returns; results are there when a getter, a setter or ptm_sync looks.  On the persistent
@@ -410,7 +421,10 @@ int ptm_batch_end(ptm_engine* e);
  * configured like the one they came from (same seed, ladder, proposals, target); the run then continues bit for bit.
  * swap_tries / swap_accepts may be NULL (counters restart at 0).  An engine that keeps a history ring or a MAP starts
  * them afresh from the restored state; ptm_set_history / ptm_set_map (below) put saved ones back, and for an evolving
- * run ptm_set_evolve_temps + ptm_set_invtemps the ladders. */
+ * run ptm_set_evolve_temps + ptm_set_invtemps the ladders.
+ * The states are taken as they were saved: a saved state went through stateSpace::enforce when it was proposed, and ptm_restore does
+ * not enforce it again (ptm_set_states does; the reference's two-sided reflection, states.cc:31-45, is not idempotent).
+ * PTM_ERR_INVALID, with nothing touched: a chain's ntries, naccept or nhist outside [0, PTM_COUNT_MAX], or naccept > ntries. */
 int ptm_restore(ptm_engine* e, const double* X, const double* llike, const int32_t* ntries, const int32_t* naccept,
                 const int32_t* last_type, const int64_t* nhist, uint64_t step_count, const int64_t* swap_tries,
                 const int64_t* swap_accepts);
@@ -497,7 +511,8 @@ int ptm_calibrate(ptm_engine* e, ptm_calibration* out);
  * A series' length is its chain's own count of add_state calls (PTM_ARR_NHIST; a rung exchanged twice in a step makes one more, so
  * the walkers of a rung differ): every series gets the windows of its own length, in the same launches; ptm_ess_report groups the
  * series whose lengths lead to the same widths and strides (esslimit < 0: as good as always all of them).
- * PTM_ERR_INVALID: no history ring, rung >= history_rungs, nfeat < 1 or > dim.  No reference counterpart for the population form. */
+ * PTM_ERR_INVALID: no history ring, rung >= history_rungs, nfeat < 1 or > dim.  PTM_ERR_UNSUPPORTED: a chain of the rung has made more than
+ * 2e9 add_state calls ("more than 2e9 steps": the kernels count samples in an int).  No reference counterpart for the population form. */
 /* one pass with fixed windows (ess_estimator::windowed) over the saved history of local rung `rung` (< history_rungs), every walker at once */
 int ptm_ess_windowed(ptm_engine* e, int rung, int nfeat, int width, int every, int burn, double* ess /*[W]*/, int32_t* nwin /*[W]*/);
 /* ess_estimator::report (width doubling / coarse-to-fine stride search of esslimit >= 0), width >= 1, every >= 1 */
@@ -520,7 +535,8 @@ int ptm_ess_last_on_device(ptm_engine* e);
  * Runs on the engine's stream and waits for it.  up / down / count may be NULL.
  * PTM_ERR_INVALID: a null engine or output, ilen < 1, no history ring, history_rungs < n_rungs, n_rungs < 2, or a window row
  * the ring no longer holds ("history_capacity must hold the evidence window": the outputs are left untouched).
- * PTM_ERR_UNSUPPORTED: a rung shard (the reference has no MPI form either, chain.cc:1592); walker splits are ordinary engines. */
+ * PTM_ERR_UNSUPPORTED: a rung shard (the reference has no MPI form either, chain.cc:1592); walker splits are ordinary engines; a chain
+ * that has made more than 2e9 add_state calls ("more than 2e9 steps"; the outputs are left untouched). */
 int ptm_log_evidence(ptm_engine* e, int ilen, double* log_evidence /*[W]*/, double* up /*[(Nt-1)*W] or NULL*/,
                      double* down /*[(Nt-1)*W] or NULL*/, int32_t* count /*[Nt*W] or NULL*/);
 

@@ -19,6 +19,7 @@
 #include "../../include/ptm_engine.h"
 #include "ptm_aux_kernels.hpp"
 #include "ptm_box_prefilter.hpp"
+#include "ptm_count_limit.hpp"
 #include "ptm_de_mfma_kernel.hpp"
 #include "ptm_devlike_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
@@ -180,6 +181,10 @@ struct ptm_engine {
   long long ladder_fallbacks = 0;   // launches that gave up (their steps were repeated on the two-launch path)
   hipEvent_t lad_event = nullptr;   // end of this engine's last launch of that kernel (two engines' grids must not share the device)
   unsigned int nhist_pending = 0;   // steps whose one-add-per-chain the compacted sweep left uncounted (flush_nhist)
+  // the horizon (ptm_count_limit.hpp): an upper bound of every chain's Ntries and Nhist, raised by each admitted call (count_guard)
+  CountHorizon horizon;
+  bool step_booked = false;         // the PT step in progress (a step made in pieces) has been admitted: its later pieces are not asked again
+  int steps_prepaid = 0;            // steps ptm_shard_step has been admitted for, whose pieces go through the public calls
   double* hastings = nullptr;
   int* htype = nullptr;
   unsigned char *hvalid = nullptr, *acc_out = nullptr;
@@ -1571,7 +1576,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   p.c_begin = rung0 * e->W; p.c_end = (rung0 + nr) * e->W;
   if ((user_like(e) || e->pcb) && (rung0 != 0 || nr != e->nloc)) return fail(PTM_ERR_UNSUPPORTED, "partial sweeps with a user likelihood (host or device) or host-side proposals are not built");
   auto close_step = [&]() {
-    e->step += 1; e->touched = false;
+    e->step += 1; e->touched = false; e->step_booked = false;
     if (e->compact_step) { e->nhist_pending += 1; e->compact_step = false; }
   };
   if (nr == 0) { if (last) close_step(); return PTM_OK; }
@@ -1892,6 +1897,7 @@ static int reset_counters(ptm_engine* e) {
       (rc = upload(e->nhist, z.data(), Nc, e->stream)))                                                        // chain.cc:871-875
     return rc;
   e->nhist_pending = 0; e->compact_step = false; e->touched = false;
+  e->horizon.rebase(1); e->step_booked = false;
   HIPCHK(hipMemsetAsync(e->touch, 0, Nc, e->stream));
   HIPCHK(hipMemsetAsync(e->arr_below, 0xFF, (size_t)e->W * 4, e->stream));
   HIPCHK(hipMemsetAsync(e->arr_above, 0xFF, (size_t)e->W * 4, e->stream));
@@ -1912,8 +1918,11 @@ static int reset_counters(ptm_engine* e) {
   return PTM_OK;
 }
 
-static int run_eval(ptm_engine* e, int n, double* x, int* valid, double* lp, double* ll, int eval_like) {
+// enforce == false: the states are taken as they are (ptm_restore: a saved state went through its one enforce when it was proposed, and
+// the reference's two-sided reflection is not idempotent -- states.cc:31-45 folds to a NEGATIVE offset, so a second pass moves it)
+static int run_eval(ptm_engine* e, int n, double* x, int* valid, double* lp, double* ll, int eval_like, bool enforce = true) {
   Dev p = make_dev(e);
+  if (!enforce) p.has_bounds = 0;
   const DpLaunch* dl = dp_launch(e->DP);
   if (!dl) return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
   HIPCHK(dl->eval(p, n, x, valid, lp, ll, eval_like, e->stream));
@@ -1935,9 +1944,13 @@ static void unpad_rows(const double* r, size_t n, size_t D, size_t DP, double* X
 }
 static void unpad_rows(const std::vector<double>& r, size_t n, size_t D, size_t DP, double* X) { unpad_rows(r.data(), n, D, DP, X); }
 
+static int set_states(ptm_engine* e, const double* X, const double* llike, bool enforce);
 extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llike) {
   SETTLE(e);
   NO_BATCH(e, "ptm_set_states");
+  return set_states(e, X, llike, true);
+}
+static int set_states(ptm_engine* e, const double* X, const double* llike, bool enforce) {
   if (!e || !X) return fail(PTM_ERR_INVALID, "null argument");
   if (!e->have_target && !llike) return fail(PTM_ERR_INVALID, "set the target first (or pass llike)");
   const size_t Nc = e->Nc, D = e->D, DP = e->DP;
@@ -1945,7 +1958,7 @@ extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llik
   int rc;
   if ((rc = upload(xrows(e), rows.data(), Nc * DP, e->stream))) return rc;
   if (llike && (rc = upload(e->ll, llike, Nc, e->stream))) return rc;
-  if ((rc = run_eval(e, (int)Nc, xrows(e), nullptr, e->lp, e->ll, (llike || user_like(e)) ? 0 : 1))) return rc;
+  if ((rc = run_eval(e, (int)Nc, xrows(e), nullptr, e->lp, e->ll, (llike || user_like(e)) ? 0 : 1, enforce))) return rc;
   if (e->dfn) {
     // the device likelihood evaluates the (enforced) start states; the best posterior starts over with them
     if ((rc = devlike_reset_best(e))) return rc;
@@ -2153,11 +2166,40 @@ extern "C" int ptm_draw_prior_rows(ptm_engine* e, int k_begin, int n, double* x_
 }
 
 // ---- hot path ----------------------------------------------------------------------------------------------------
+// The horizon (PTM_COUNT_MAX, ptm_count_limit.hpp): may this engine take n more PT steps?  One add and one compare while the host's
+// bound allows it; when the bound trips, the two arrays are read once (queued and deferred work first, so they are the true counters),
+// the bound is re-based to the true maximum and the question is asked again.  A refusal queues nothing and changes nothing.
+static int count_guard(ptm_engine* e, long long n, const char* who) {
+  if (e->horizon.admit(n)) return PTM_OK;
+  int rc;
+  if ((rc = ladder_settle(e)) || (rc = flush_nhist(e))) return rc;
+  const size_t Nc = e->Nc;
+  std::vector<int32_t> nt(Nc);
+  std::vector<uint32_t> nh(Nc);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(nt.data(), e->ntries, Nc * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(nh.data(), e->nhist, Nc * 4, hipMemcpyDeviceToHost));
+  e->horizon.rebase(count_true_max(nt.data(), nh.data(), Nc));
+  if (e->horizon.admit(n)) return PTM_OK;
+  return fail(PTM_ERR_UNSUPPORTED, "%s: %lld more steps could take a chain's Ntries / Nhist (now %lld at the most) past PTM_COUNT_MAX = %lld, the largest count the engine "
+              "represents; checkpoint, shift the counters down and restore (INTEGRATION.md, \"The horizon\")", who, n, (long long)e->horizon.bound, (long long)PTM_COUNT_MAX);
+}
+// the same for ONE step made in pieces: its first piece is the one that asks (close_step ends the step)
+static int count_guard_piece(ptm_engine* e, const char* who) {
+  if (e->step_booked) return PTM_OK;
+  if (e->steps_prepaid > 0) e->steps_prepaid -= 1;
+  else { const int rc = count_guard(e, 1, who); if (rc) return rc; }
+  e->step_booked = true;
+  return PTM_OK;
+}
+
 extern "C" int ptm_sweep(ptm_engine* e, int n) {
   SETTLE(e);
   NO_BATCH(e, "ptm_sweep");
   int rc = ready(e);
   if (rc) return rc;
+  // (after an exchange phase of its own -- ptm_exchange_decide -- the first sweep belongs to the step that call was admitted for)
+  if ((rc = count_guard(e, (long long)n - (e->step_booked && n > 0 ? 1 : 0), "ptm_sweep"))) return rc;
   for (int k = 0; k < n; ++k)
     if ((rc = launch_sweep(e))) return rc;
   return PTM_OK;
@@ -2411,6 +2453,7 @@ extern "C" int ptm_step(ptm_engine* e, int n) {
   if (rc) return rc;
   if (e->nloc != e->Nt) return fail(PTM_ERR_INVALID, "ptm_step needs the whole ladder on this engine; sharded engines use ptm_exchange_*");
   NO_BATCH(e, "ptm_step");
+  if ((rc = count_guard(e, n, "ptm_step"))) return rc;
   if (n > 0) {
     int f = 0;
     // (the persistent ladder kernel first: where both apply it steps a small ladder in half the fused kernel's time -- 20 rungs of 6
@@ -2477,6 +2520,7 @@ extern "C" int ptm_exchange_decide(ptm_engine* e, const void* ll_below, const vo
   if ((!first && !ll_below) || (!last && (!ll_above || halo_rungs < 1)))
     return fail(PTM_ERR_INVALID, "missing llike halo: a shard needs the top rung below it and >= 1 rung above it");
   if (!last && halo_rungs > e->Nt - (e->r0 + e->nloc)) return fail(PTM_ERR_INVALID, "halo deeper than the ladder above this shard");
+  if ((rc = count_guard_piece(e, "ptm_exchange_decide"))) return rc;
   if (e->Nt > 1)
     return launch_decide(e, first ? nullptr : (const double*)ll_below, last ? nullptr : (const double*)ll_above, halo_rungs,
                          last ? nullptr : (double*)send_up, first ? nullptr : (double*)send_down);
@@ -2493,6 +2537,7 @@ extern "C" int ptm_exchange_decide_gathered(ptm_engine* e, const void* ll_all, c
   if (e->evolve_rate > 0 && e->evolve_cut >= 0 && !lp_all) return fail(PTM_ERR_INVALID, "a posterior-ordering cut needs the whole ladder's lpriors too");
   const bool first = e->r0 == 0, last = e->r0 + e->nloc == e->Nt;
   if ((!last && !send_up) || (!first && !send_down)) return fail(PTM_ERR_INVALID, "missing boundary message buffer");
+  if ((rc = count_guard_piece(e, "ptm_exchange_decide_gathered"))) return rc;
   if (e->Nt > 1)
     return launch_decide(e, nullptr, nullptr, 0, last ? nullptr : (double*)send_up, first ? nullptr : (double*)send_down, (const double*)ll_all,
                          (const double*)lp_all);
@@ -2594,6 +2639,7 @@ extern "C" int ptm_exchange_install(ptm_engine* e, const void* recv_below, const
   if (rc) return rc;
   const bool first = e->r0 == 0, last = e->r0 + e->nloc == e->Nt;
   if ((!first && !recv_below) || (!last && !recv_above)) return fail(PTM_ERR_INVALID, "missing boundary message from a neighbour shard");
+  if ((rc = count_guard_piece(e, "ptm_exchange_install"))) return rc;
   return launch_install(e, first ? nullptr : (const double*)recv_below, last ? nullptr : (const double*)recv_above);
 }
 extern "C" int ptm_sweep_rungs(ptm_engine* e, int first_local_rung, int n_rungs, int closes_step) {
@@ -2602,6 +2648,7 @@ extern "C" int ptm_sweep_rungs(ptm_engine* e, int first_local_rung, int n_rungs,
   NO_DEVLIKE(e, "ptm_sweep_rungs");
   int rc = ready(e);
   if (rc) return rc;
+  if ((rc = count_guard_piece(e, "ptm_sweep_rungs"))) return rc;
   return launch_sweep(e, first_local_rung, n_rungs, closes_step != 0);
 }
 
@@ -2616,6 +2663,7 @@ extern "C" int ptm_exchange_finish_and_sweep(ptm_engine* e, const void* recv_bel
   if (rc) return rc;
   const bool first = e->r0 == 0, last = e->r0 + e->nloc == e->Nt;
   if ((!first && !recv_below) || (!last && !recv_above)) return fail(PTM_ERR_INVALID, "missing boundary message from a neighbour shard");
+  if ((rc = count_guard_piece(e, "ptm_exchange_finish_and_sweep"))) return rc;
   if ((rc = launch_install(e, first ? nullptr : (const double*)recv_below, last ? nullptr : (const double*)recv_above))) return rc;
   return launch_sweep(e);
 }
@@ -2774,6 +2822,7 @@ static int shard_recover(ptm_engine* e) {
   return ptm_exchange_redo(e, s->ll_all, s->lp_all, s->send_up, s->send_down);
 }
 
+static int shard_steps(ptm_engine* e, int n);
 extern "C" int ptm_shard_step(ptm_engine* e, int n) {
   SETTLE(e);
   NO_BATCH(e, "ptm_shard_step");
@@ -2781,6 +2830,15 @@ extern "C" int ptm_shard_step(ptm_engine* e, int n) {
   if (rc) return rc;
   if (!e->shard) return fail(PTM_ERR_INVALID, "ptm_shard_init first");
   if (user_like(e) || e->pcb) return fail(PTM_ERR_UNSUPPORTED, "sharded steps with a user likelihood (host or device) or host-side proposals are not built");
+  // all n steps are admitted here, before anything is queued; their pieces go through the public calls, which then do not ask again
+  if ((rc = count_guard(e, n, "ptm_shard_step"))) return rc;
+  e->steps_prepaid = n > 0 ? n : 0;
+  rc = shard_steps(e, n);
+  e->steps_prepaid = 0;
+  return rc;
+}
+static int shard_steps(ptm_engine* e, int n) {
+  int rc;
   ShardComm* s = e->shard;
   if (e->evolve_rate > 0) {
     // Evolving ladders: every shard replays the whole ladder's trials from the whole ladder's llikes (and lpriors, with a
@@ -2943,15 +3001,18 @@ extern "C" int ptm_restore(ptm_engine* e, const double* X, const double* llike, 
   SETTLE(e);
   NO_BATCH(e, "ptm_restore");
   if (!e || !X || !llike || !ntries || !naccept || !last_type || !nhist) return fail(PTM_ERR_INVALID, "null argument");
-  // (a history ring / MAP restart from the restored state here; ptm_set_history / ptm_set_map put saved ones back)
-  int rc = ptm_set_states(e, X, llike);   // enforces (a no-op on saved states), recomputes lprior, resets counters
-  if (rc) return rc;
+  // the counters first, before anything is touched: inside the horizon (PTM_COUNT_MAX), and no more accepts than tries
   const size_t Nc = e->Nc;
   std::vector<unsigned int> nh(Nc);
   for (size_t c = 0; c < Nc; ++c) {
-    if (nhist[c] < 0 || nhist[c] > 0xFFFFFFFFll) return fail(PTM_ERR_INVALID, "nhist out of range");
+    const char* why = count_restore_error(ntries[c], naccept[c], nhist[c]);
+    if (why) return fail(PTM_ERR_INVALID, "%s out of range (chain %zu: ntries %d, naccept %d, nhist %lld): every counter lies in [0, PTM_COUNT_MAX = %lld] and naccept <= ntries",
+                         why, c, (int)ntries[c], (int)naccept[c], (long long)nhist[c], (long long)PTM_COUNT_MAX);
     nh[c] = (unsigned int)nhist[c];
   }
+  // (a history ring / MAP restart from the restored state here; ptm_set_history / ptm_set_map put saved ones back)
+  int rc = set_states(e, X, llike, false);   // the states as they were saved (no second enforce), their lpriors recomputed, the counters reset
+  if (rc) return rc;
   if ((rc = upload(e->ntries, ntries, Nc, e->stream)) || (rc = upload(e->naccept, naccept, Nc, e->stream)) ||
       (rc = upload(e->last_type, last_type, Nc, e->stream)) || (rc = upload(e->nhist, nh.data(), Nc, e->stream)))
     return rc;
@@ -2967,6 +3028,7 @@ extern "C" int ptm_restore(ptm_engine* e, const double* X, const double* llike, 
     HIPCHK(hipStreamSynchronize(e->stream));   // `both` leaves scope
   }
   e->step = step_count;
+  e->horizon.rebase(count_true_max(ntries, nh.data(), Nc));
   HIPCHK(hipStreamSynchronize(e->stream));
   return PTM_OK;
 }

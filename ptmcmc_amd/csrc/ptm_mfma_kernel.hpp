@@ -592,6 +592,8 @@ __device__ __forceinline__ void mfma32_body(const Dev p) {   // (by value, as a 
     // ---- stage 5, lanes PL gp .. PL gp + PL - 1 (chain = lane): Metropolis test and add_state counters
     //      (chain.cc:973-1019, 916-949)
     bool accept = false;
+    // (an `int` is enough: the host admits no step that could take Nhist past PTM_COUNT_MAX (ptm_count_limit.hpp), so the largest add
+    //  number a kernel sees is PTM_COUNT_MAX - 1 and hrow <= PTM_COUNT_MAX even with add_every_n = 1 -- never negative by overflow)
     int hrow = -1;   // >= 0: this add_state call saves a history row (chain.cc:935-946), the ring row index
     bool mapw = false;   // this add_state call sets a new MAP (chain.cc:931-934): the row is copied below
     const bool hist_on = HIST && rl < p.hist.rungs;

@@ -19,6 +19,7 @@ PRIOR_FLAT, PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_POLAR, PRIOR_COPOLAR, PRIOR_LOG
 PROP_DENSE, PROP_DIAG, PROP_LOWER = 0, 1, 2
 ARR_LLIKE, ARR_LPRIOR, ARR_LPOST, ARR_NTRIES, ARR_NACCEPT, ARR_LAST_TYPE, ARR_NHIST, ARR_NSIZE, ARR_ROW_LABELS = range(9)
 FN_LOG, FN_EXP, FN_SIN_0_PI, FN_COS_HPI, FN_SQRT, FN_DIV, FN_SQRT_RAW = range(7)
+COUNT_MAX = 2**31 - 1   # PTM_COUNT_MAX: the largest Ntries / Naccept / Nhist the engine represents (include/ptm_engine.h, "The horizon")
 PRIOR_NAMES = {"uni": 1, "uniform": 1, "gauss": 2, "gaussian": 2, "pol": 3, "polar": 3, "cpol": 4, "copol": 4, "log": 5}
 
 EXPORTS = [

@@ -1,6 +1,6 @@
 """One run of a big-population engine against the CPU oracle in a process of its own (PTM_BOX_PREFILTER is read once per process):
 the box pre-pass (ptmcmc_amd/csrc/ptm_box_prefilter.hpp) must change nothing in the chains.  Prints the pre-pass's counters.
-usage: python box_prefilter_worker.py lower|dense|nonfinite|sharded|sharded_overlap"""
+usage: python box_prefilter_worker.py lower|dense|nonfinite|sharded|sharded_overlap|aged   (aged: `lower` late in a run, tests/aging_util.py)"""
 import os
 import sys
 
@@ -68,28 +68,49 @@ def counts(engines):
     return "seen=%(seen)d settled=%(settled)d rungs_flagged=%(rungs_flagged)d rungs=%(rungs)d eligible=%(eligible)d" % tot
 
 
-def run_pair(kind, x0=None):
-    """3 + 4 + 5 PT steps, plain sweeps and a checkpoint / resume in between; engine and oracle bit for bit after each leg"""
+def run_pair(kind, x0=None, aged=False):
+    """3 + 4 + 5 PT steps, plain sweeps and a checkpoint / resume in between; engine and oracle bit for bit after each leg.
+    aged: after the first leg engine and oracle are put at PT step 2^32 - 2 with every counter shifted up to 16 below PTM_COUNT_MAX
+    at the run's end -- the next leg's steps cross 2^32, the labels are in use and the compacted sweeps leave their one add per chain
+    to the engine's count (nhist_flush_kernel) up there."""
     pr, eng, lad = PU.make_pair(D, NT, W, 1e9, kind=kind, swap_rate=SR, x0=x0)
     assert eng.sweep_kernel_name.endswith(", 0, false, true>"), eng.sweep_kernel_name
     eng.step(3); eng.sync(); lad.pt_step(3)
     PU.assert_same_state(eng, lad, "after 3 steps")       # (eng.states() puts labelled rows back: restore_rows_kernel)
+    shift = 0
+    same = PU.assert_same_state
+    if aged:
+        import aging_util as AU
+        view, shift = AU.age_pair(eng, lad, 2 + 4 + 5)
+        assert eng.step_count == lad.step == AU.LATE_STEP and eng.sweep_kernel_name.endswith(", 0, false, true>")
+        same = lambda e, l, what: PU.assert_same_state(AU.AgedView(e, shift), l, what)     # (add_every_n = 1: the row counts are shifted alike)
+        same(eng, lad, "aged")
+        eng.step(3); eng.sync(); lad.pt_step(3)
+        assert (eng.row_labels != np.repeat(np.arange(NT, dtype=np.int32), W)).any(), "the labelled path did not run"
+        assert eng.step_count == 2**32 + 1
+        same(eng, lad, "aged, after the 3 steps across 2^32")
+        t, a = eng.counter_sums()
+        assert (t, a) == (int(eng.ntries.astype(np.int64).sum()), int(eng.naccept.astype(np.int64).sum()))
     eng.sweep(2); eng.sync(); lad.sweep(2)
-    PU.assert_same_state(eng, lad, "after plain sweeps")
-    eng.step(4); lad.pt_step(4)
+    same(eng, lad, "after plain sweeps")
+    eng.step(1 if aged else 4); lad.pt_step(1 if aged else 4)
     ck = eng.checkpoint()
-    PU.assert_same_state(eng, lad, "after 7 steps")
+    same(eng, lad, "after 7 steps")
     e2 = E.Engine(D, NT, W, swap_rate=SR)
     pr.configure(e2, kind)
     e2.restore(ck)
     for e in (eng, e2):
         e.step(5); e.sync()
     lad.pt_step(5)
-    PU.assert_same_state(eng, lad, "after 12 steps")
-    PU.assert_same_state(e2, lad, "resumed engine after 12 steps")
+    same(eng, lad, "after 12 steps")
+    same(e2, lad, "resumed engine after 12 steps")
     t, a = eng.swap_counts()
     assert np.array_equal(t, lad.swap_count) and np.array_equal(a, lad.swap_accept_count)
-    acc = int(eng.naccept.sum() - eng.Nc)
+    acc = int(eng.naccept.astype(np.int64).sum() - eng.Nc * (1 + shift))
+    if aged:
+        import aging_util as AU
+        top = int(max(eng.ntries.max(), eng.nhist.max()))
+        assert AU.COUNT_MAX - AU.MARGIN - 2 * 11 <= top <= AU.COUNT_MAX - AU.MARGIN, top
     out = counts([eng]) + " accepts=%d" % acc
     eng.close(); e2.close()
     return out
@@ -145,6 +166,8 @@ if __name__ == "__main__":
     case = sys.argv[1]
     if case == "lower":
         res = run_pair(E.PROP_LOWER)
+    elif case == "aged":
+        res = run_pair(E.PROP_LOWER, aged=True)
     elif case == "dense":
         res = run_pair(E.PROP_DENSE)
     elif case == "nonfinite":

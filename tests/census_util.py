@@ -3,6 +3,7 @@ the reported kernel name against the table's, PT steps and plain sweeps with a f
 tests/test_gpu_build_census.py (in its own process) and tests/census_worker.py (the cases under an environment switch)."""
 import numpy as np
 
+import aging_util as AU
 import oracle_lib as O
 import parity_util as PU
 import proposal_pairs as PP
@@ -28,11 +29,12 @@ def state_space(c):
             blo[d] = E.BOUND_LIMIT
         for d in {2 % D, 4 % D, (D - 2) % D}:
             bhi[d] = E.BOUND_LIMIT
-        if D > 128:     # (four chains only: a quarter of the dimensions limited on either side, so that their few proposals meet a limit)
+        if D > 128:     # (four chains only: one dimension in 64 limited on either side, so that their few proposals meet a limit -- with a
+            #  quarter of them limited next to every proposal was invalid, and a case rested on one accepted move in 36, or on none)
             for d in range(D):
-                if d % 4 == 1:
+                if d % 64 == 1:
                     blo[d] = E.BOUND_LIMIT
-                elif d % 4 == 2:
+                elif d % 64 == 2:
                     bhi[d] = E.BOUND_LIMIT
         if c["bounds"] == "wrap":
             blo[0] = bhi[0] = E.BOUND_WRAP
@@ -54,6 +56,10 @@ def state_space(c):
         if bounds is not None:
             bounded = np.array([lo != E.BOUND_OPEN or hi != E.BOUND_OPEN for lo, hi in zip(bounds[0], bounds[1])])
             x0[:, bounded] *= near
+            if D > 128:   # (the open dimensions start from draws of the target, widened as below and more: moves inwards gain; inside the prior's box)
+                wide = 3.0 * rng.standard_normal((Nt * W, D)) @ np.linalg.cholesky(pr.cov).T
+                wide = np.clip(wide, -0.75 * np.asarray(pr.halfwidths), 0.75 * np.asarray(pr.halfwidths))
+                x0[:, ~bounded] = wide[:, ~bounded]
     elif D > 128:   # (beyond 128 dimensions a start drawn from the prior's box accepts next to nothing: start from draws of the target, widened)
         x0 = 1.5 * rng.standard_normal((Nt * W, D)) @ np.linalg.cholesky(pr.cov).T   # (over-dispersed: moves inwards gain)
     return dict(bounds=bounds, prior=prior, mean=mean, x0=x0, time_kernels=bool(c.get("time_kernels")))
@@ -135,17 +141,21 @@ class Case:
         self.eng.close()
 
 
+def assert_reported_name(eng, name):
+    """the build the engine reports: string for string the table's name"""
+    if name.startswith("sweep_"):
+        assert eng.sweep_kernel_name == name, (eng.sweep_kernel_name, name)
+        assert eng.step_kernel_name == "decide_kernel + " + name, (eng.step_kernel_name, name)
+    else:
+        assert eng.step_kernel_name == name, (eng.step_kernel_name, name)
+
+
 def run_case(name, c):
     """the whole case; returns what it saw (for the worker's line).  Every assertion is the test's."""
     case = Case(c, persistent=name.startswith("ladder_persistent_kernel<"))
     eng = case.eng
     try:
-        # the build the engine reports: string for string the table's name
-        if name.startswith("sweep_"):
-            assert eng.sweep_kernel_name == name, (eng.sweep_kernel_name, name)
-            assert eng.step_kernel_name == "decide_kernel + " + name, (eng.step_kernel_name, name)
-        else:
-            assert eng.step_kernel_name == name, (eng.step_kernel_name, name)
+        assert_reported_name(eng, name)
         done = 0
         for _ in range(3):
             case.step(3); done += 3
@@ -171,4 +181,51 @@ def run_case(name, c):
             assert not np.array_equal(eng.invtemps(), np.tile(case.pr.beta, (eng.W, 1)))
         return dict(name=name, accepted=acc, tries=tries, swaps=int(eng.swap_counts()[1].sum()))
     finally:
+        case.close()
+
+
+AGED_ROUNDS = 7      # PT steps and plain sweeps of a case after it was aged: step(3), sweep(2), step(2)
+
+
+def run_case_aged(name, c):
+    """the same case late in a run (tests/aging_util.py): one young round, then engine and checker are put at PT step 2^32 - 2 with every
+    chain's counters shifted as close to PTM_COUNT_MAX as leaves the rounds 16 below it -- differential evolution keeps its Nhist, its
+    ring may not wrap -- and step(3), sweep(2), step(2) follow, each with the full comparison.  The first of them takes the steps
+    2^32 - 2 .. 2^32 in ONE call: the step kernels cross the word boundary of the step number inside a launch."""
+    case = Case(c, persistent=name.startswith("ladder_persistent_kernel<"))
+    eng = case.eng
+    try:
+        assert_reported_name(eng, name)
+        case.step(3)
+        case.compare("young, after 3 PT steps")
+        case.eng, d = AU.age_pair(eng, case.lad, AGED_ROUNDS, shift_nhist=not c.get("de"), adaptive=bool(c.get("ada")))
+        assert_reported_name(eng, name)
+        assert eng.step_count == case.lad.step == AU.LATE_STEP
+        case.compare("aged by %d" % d)
+
+        def sums():
+            t, a = eng.counter_sums()
+            nt, na = eng.ntries.astype(np.int64), eng.naccept.astype(np.int64)
+            assert (t, a) == (int(nt.sum()), int(na.sum())), ((t, a), int(nt.sum()), int(na.sum()))
+            assert (na <= nt).all() and nt.min() >= d
+            return t, a
+        t0, a0 = sums()
+        assert d > 2**30 and t0 > 2**32      # (four chains at the least: the sums are past 32 bits)
+        case.step(3)
+        assert eng.step_count == case.lad.step == 2**32 + 1
+        case.compare("aged, after the 3 PT steps across 2^32")
+        case.sweep(2)
+        case.compare("aged, after 2 plain sweeps")
+        case.step(2)
+        assert eng.step_count == case.lad.step == 2**32 + 5
+        case.compare("aged, after 2 more PT steps")
+        t1, a1 = sums()
+        tries, acc = t1 - t0, a1 - a0
+        assert 0 < acc < tries, (acc, tries)
+        top = max(int(eng.ntries.max()), int(eng.nhist.max()))
+        assert top <= AU.COUNT_MAX - AU.MARGIN, top
+        assert top > AU.COUNT_MAX - AU.MARGIN - AU.ADDS_PER_STEP * AGED_ROUNDS - max(c.get("hist") or 1, 1) * CAP - 16, top     # (and it did run late)
+        return dict(name=name, accepted=acc, tries=tries, swaps=int(eng.swap_counts()[1].sum()), top=top)
+    finally:
+        case.eng = eng
         case.close()

@@ -1,7 +1,9 @@
 """One case of differential evolution on the matrix cores (de_mfma32_kernel) against the CPU oracle, in a process of its own: the engine
 reads PTM_DE_MFMA and PTM_LADDER once per process (tests/test_gpu_de_mfma.py sets PTM_DE_MFMA=1 PTM_LADDER=0).  Engine and oracle are
 built by proposal_pairs.de_pair; states, scalars, counters, every saved row and the MAPs are compared bit for bit.
-usage: python de_mfma_worker.py CASE      prints "ok key=value ..." """
+usage: python de_mfma_worker.py CASE [aged]     prints "ok key=value ..."
+(aged: after the case's first PT step engine and oracle are put late in a run, tests/aging_util.py -- PT step 2^32 - 2, Ntries and Naccept
+shifted up to 16 below PTM_COUNT_MAX at the run's end; Nhist stays, differential evolution's ring may not wrap)"""
 import os
 import sys
 
@@ -54,7 +56,7 @@ def check_types(seen, snooker, K):
     assert any(1 <= (v % 10) <= K for v in seen), seen
 
 
-def run_steps(case):
+def run_steps(case, aged=False):
     D, Nt, W, kind, N, snooker, ninit, K, steps = CASES[case]
     cap = 2 * steps + 8
     ev = case == "evolving"
@@ -71,6 +73,16 @@ def run_steps(case):
         PU.assert_same_state(eng, lad, "after %d PT steps" % done)
         if ev:
             assert np.array_equal(eng.invtemps(), lad.betaw), done
+        if aged and done == 1:
+            import aging_util as AU
+            AU.age_pair(eng, lad, steps - 1, shift_nhist=False)
+            assert eng.step_count == lad.step == AU.LATE_STEP and eng.sweep_kernel_name == kind_name(kind, ev)
+            PU.assert_same_state(eng, lad, "aged")
+            ck0 = eng.naccept.astype(np.int64)
+    if aged:
+        top = int(eng.ntries.max())
+        assert eng.step_count == lad.step == AU.LATE_STEP + steps - 1
+        assert AU.COUNT_MAX - AU.MARGIN - 2 * steps <= top <= AU.COUNT_MAX - AU.MARGIN, top
     PU.assert_same_history_and_map(eng, lad, cap)
     he, nsize = eng.history(), eng.nsize
     if case == "no_init":
@@ -84,7 +96,20 @@ def run_steps(case):
     if case == "limit_mean":
         tries, acc = eng.ntries.sum() - eng.Nc, eng.naccept.sum() - eng.Nc
         assert 0 < acc < tries
-    out = "kernel=%s accepts=%d" % (eng.sweep_kernel_name.replace(" ", ""), int(eng.naccept.sum() - eng.Nc))
+    out = "kernel=%s accepts=%d" % (eng.sweep_kernel_name.replace(" ", ""), int((eng.naccept.astype(np.int64) - ck0).sum()) if aged else int(eng.naccept.sum() - eng.Nc))
+    eng.close()
+    return out
+
+
+def run_late():
+    """differential evolution late in a run (tests/aging_util.py: late_de_pair): 128 saved rows at a history stride of 2^24, Nhist = 127 * 2^24 - 2,
+    PT step 2^32 - 2; five initial rows per dimension make the member ready at 21 dimensions"""
+    import aging_util as AU
+    D, Nt, W, kind = 21, 4, 128, E.PROP_LOWER
+    pr, eng, lad = AU.late_de_pair(D, Nt, W, kind, snooker=0.3, ninit=5, K=3)
+    assert eng.step_kernel_name == "decide_kernel + " + kind_name(kind, False), eng.step_kernel_name
+    seen = AU.run_late_de(eng, lad)
+    out = "kernel=%s types=%s" % (eng.sweep_kernel_name.replace(" ", ""), ",".join(str(v) for v in sorted(seen)))
     eng.close()
     return out
 
@@ -156,7 +181,9 @@ def name_prior_draw():
 if __name__ == "__main__":
     case = sys.argv[1]
     if case in CASES:
-        res = run_steps(case)
+        res = run_steps(case, aged=sys.argv[2:] == ["aged"])
+    elif case == "late":
+        res = run_late()
     elif case == "sweeps":
         res = run_sweeps()
     elif case == "short_ring":

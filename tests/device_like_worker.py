@@ -202,8 +202,9 @@ def case_recipe(D, Nt, W, kind, steps, ev, de_share, K, ninit, start=None, seed=
     eng.close()
 
 
-def case_lanes(D, Nt, W, ev):
-    """more than 8 dimensions on a small population: the lanes kernel's propose and accept passes around the device function"""
+def case_lanes(D, Nt, W, ev, aged=False):
+    """more than 8 dimensions on a small population: the lanes kernel's propose and accept passes around the device function
+    (aged: after the first six steps engine and checker are put late in a run, tests/aging_util.py: the next six cross PT step 2^32)"""
     rng = np.random.default_rng(7)
     c, k = poly_coefs(D, seed=D + 1)
     beta = E.geometric_ladder(Nt, 1e3)
@@ -232,10 +233,19 @@ def case_lanes(D, Nt, W, ev):
     if ev:
         eng.set_evolve_temps(ev); lad.evolve_temps(ev)
     PU.assert_same_state(eng, lad, "start")
+    view, shift = eng, 0
     for s in range(5):
         eng.step(6); eng.sync(); lad.pt_step(6)
-        PU.assert_same_state(eng, lad, "after %d steps" % (6 * (s + 1)))
-    assert eng.naccept.sum() - eng.Nc > 5
+        PU.assert_same_state(view, lad, "after %d steps" % (6 * (s + 1)))
+        if aged and s == 0:
+            import aging_util as AU
+            view, shift = AU.age_pair(eng, lad, 24, step=2**32 - 3)
+            check_name(eng, "sweep_lanes_kernel<")
+            PU.assert_same_state(view, lad, "aged")
+    if aged:
+        assert eng.step_count == lad.step == 2**32 - 3 + 24
+        assert 2**31 - 2**16 < int(max(eng.ntries.max(), eng.nhist.max())) <= AU.COUNT_MAX - AU.MARGIN
+    assert eng.naccept.astype(np.int64).sum() - eng.Nc * (1 + shift) > 5
     eng.close()
 
 

@@ -29,6 +29,12 @@ def test_philox_on_device_matches_known_answers_and_oracle():
         seed = int(rng.integers(0, 2 ** 63)); tag = int(rng.integers(0, 3)); stream = int(rng.integers(0, 2 ** 32))
         step = int(rng.integers(0, 2 ** 40)); block = int(rng.integers(0, 300))
         assert E.debug_philox(seed, tag, stream, step, block) == O.draw_block(seed, tag, stream, step, block)
+    # every tag (TAG_MH, TAG_PT, TAG_INIT, TAG_SET, TAG_PRIOR) at the edges of the step's two words: c2 = step[31:0], c3 = step[55:32] | tag << 24
+    # (tests/test_late_run_cpu.py holds the checker's layout there to a restatement of Philox4x32-10 of its own)
+    for step in (2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1, 2 ** 40 + 5, 2 ** 56 - 1):
+        for tag in range(5):
+            for seed, stream, block in ((0, 0, 0), (0x5EED0001, 7, 3), (int(rng.integers(0, 2 ** 63)) * 2 + 1, int(rng.integers(0, 2 ** 32)), int(rng.integers(0, 300)))):
+                assert E.debug_philox(seed, tag, stream, step, block) == O.draw_block(seed, tag, stream, step, block), (hex(seed), tag, stream, step, block)
 
 
 def test_elementary_functions_bit_exact():
