@@ -19,6 +19,8 @@
 //   golden-de               JSON on stdout: differential_evolution::draw (standard, snooker, unlikely_alpha, temperature
 //                           mixing) on the histories of a real ladder, with the uniforms each draw consumed.
 //   golden-ess              JSON on stdout: chain::report_effective_samples on fixed AR(1) series.
+//   golden-evidence         JSON on stdout: log_evidence_ratio on the histories of real ladders (fixed and evolving, add_every_N 1..10,
+//                           several initial rows), and what a do_evid ladder prints and keeps over 8 statistics bins.
 //   bench <spec-file>       time parallel_tempering_chains::step() on the
 //                           correlated-Gaussian problem described in spec-file;
 //                           prints one JSON line (cpu_baseline, kind "reference").
@@ -33,6 +35,13 @@
 //   gaussian_prop(cov)                    proposal_distribution.hh:165-218
 //   differential_evolution::draw          proposal_distribution.cc:476-801
 //   chain::report_effective_samples       chain.cc:126-643
+//   parallel_tempering_chains(Ntemps, Tmax, swap_rate, add_every_N, do_evid, verbose_evid) / evolve_temps
+//                                         chain.cc:1163-1211, chain.hh:302-307
+//   parallel_tempering_chains::log_evidence_ratio / bestEvidenceErr / the statistics block of step()
+//                                         chain.cc:1984-2012, chain.hh:301, chain.cc:1577-1676
+//   MH_chain::getStep (Nhist) / size (Nsize) / invTemp / getLogLike(k, true) (raw index)
+//                                         chain.cc:1052-1054, chain.hh:86,205, chain.cc:1079-1086
+//   probability_function (the driver's own likelihood derives from it)   probability_function.hh:31-44
 
 #include <chrono>
 #include <new>
@@ -845,6 +854,174 @@ static int golden_ess() {
   return 0;
 }
 
+// ----------------------------------------------------------------------------------------------
+// golden-evidence: parallel_tempering_chains::log_evidence_ratio (chain.cc:1984-2012) on the histories of real ladders, and the
+// statistics block's totals, record pyramid and "recent ev analysis" (chain.cc:1577-1676) as a do_evid ladder prints them.
+// The driver computes no evidence arithmetic: every recorded answer is the return value of the reference's log_evidence_ratio or
+// bestEvidenceErr, or text the reference printed.  The likelihood is the driver's own probability_function,
+// llike = -floor(32 |x|^2) / 64: an integer multiple of 2^-6, stored as that integer.
+//   groups  short ladders by seed, run lengths differing inside a group; per ladder every chain's Nhist (getStep), Nsize (size),
+//           current invTemp, the saved llikes by RAW index, and log_evidence_ratio(i, i+1, ilen, 1), (i+1, i, ilen, 1) of every pair
+//           at each ilen of a list that brackets the chains' Nhist.
+//   long    one do_evid ladder per verbose_evid value, 8 statistics bins: per report the printed lines from "Total log-evidence:" on,
+//           bestEvidenceErr(), the chains' Nhist / Nsize and the driver's own log_evidence_ratio calls at ilen = the bin.
+// parallel_tempering_chains::step keeps its bin counter and swap tallies in function-local statics, sized when the counter stands
+// at 0 (chain.cc:1398-1406): the long ladders run first (each ends a bin exactly), the groups after them in descending Ntemps.
+// ----------------------------------------------------------------------------------------------
+struct grid_like : public probability_function {
+  grid_like(const stateSpace* sp) : probability_function(sp) {}
+  double evaluate_log(state& s) override {
+    std::valarray<double> x = s.get_params();
+    double q = 0;
+    for (size_t i = 0; i < x.size(); i++) q += x[i] * x[i];
+    return -std::floor(32 * q) / 64;
+  }
+};
+
+static std::string jstr(const std::string& t) {
+  std::string o = "\"";
+  for (char c : t) {
+    if (c == '\t') o += "\\t";
+    else if (c == '"' || c == '\\') { o += '\\'; o += c; }
+    else o += c;
+  }
+  return o + "\"";
+}
+
+static bool evid_llikes(std::ostream& js, parallel_tempering_chains& ptc, int Nt) {
+  js << "\"llike64\":[";
+  for (int r = 0; r < Nt; r++) {
+    chain* c = ptc.subchain(r);
+    js << (r ? "," : "") << "\n  [";
+    for (int e = 0; e < c->size(); e++) {
+      const double v = c->getLogLike(e, true) * 64;
+      if (v != std::floor(v) || std::fabs(v) > 1e9) { fprintf(stderr, "golden-evidence: llike %.17g is no multiple of 2^-6\n", v / 64); return false; }
+      js << (e ? "," : "") << (long)v;
+    }
+    js << "]";
+  }
+  js << "]";
+  return true;
+}
+
+static void evid_counts(std::ostream& js, parallel_tempering_chains& ptc, int Nt) {
+  std::vector<int> nh, ns;
+  std::vector<double> b;
+  for (int r = 0; r < Nt; r++) { nh.push_back(ptc.subchain(r)->getStep()); ns.push_back(ptc.subchain(r)->size()); b.push_back(ptc.subchain(r)->invTemp()); }
+  js << "\"Nhist\":" << jarr_i(nh) << ",\"Nsize\":" << jarr_i(ns) << ",\"invtemp\":" << jarr(b);
+}
+
+static void evid_ratios(std::ostream& js, parallel_tempering_chains& ptc, int Nt, int ilen) {
+  std::vector<double> ab;
+  for (int i = 0; i < Nt - 1; i++) { ab.push_back(ptc.log_evidence_ratio(i, i + 1, ilen, 1)); ab.push_back(ptc.log_evidence_ratio(i + 1, i, ilen, 1)); }
+  js << "{\"ilen\":" << ilen << ",\"ab\":" << jarr(ab) << "}";
+}
+
+static int evidence_run(std::ostream& js, cout_mute& mute) {
+  js << "{\"llike_scale\":64,\n\"long\":[";
+  for (int iv = 0; iv < 2; iv++) {
+    const int verbose = 1 - iv, D = 1, Nt = 3, every = 10, Ninit = 1, reports = 8;
+    const double Tmax = 8.0, swap_rate = 0.3, halfwidth = 2.0, seed = 0.6180 + 0.01 * iv;
+    ProbabilityDist::setSeed(seed);
+    globalRNG.reset(ProbabilityDist::getPRNG());
+    stateSpace sp(D);
+    std::valarray<double> c(0.0, D), h(halfwidth, D), sig(0.9, D);
+    std::valarray<int> t(mixed_dist_product::uniform, D);
+    mixed_dist_product prior(&sp, t, c, h);
+    grid_like like(&sp);
+    parallel_tempering_chains ptc(Nt, Tmax, swap_rate, every, true, verbose != 0);
+    ptc.initialize(&like, &prior, Ninit);
+    gaussian_prop prop(sig);
+    ptc.set_proposal(prop);
+    const int bin = 10000 * (every / 10 + 1);   // chain.cc:1359
+    js << (iv ? "," : "") << "\n{\"verbose\":" << verbose << ",\"D\":" << D << ",\"Nt\":" << Nt << ",\"add_every_N\":" << every << ",\"Ninit\":" << Ninit
+       << ",\"Tmax\":" << jnum(Tmax) << ",\"swap_rate\":" << jnum(swap_rate) << ",\"seed\":" << jnum(seed) << ",\"bin\":" << bin << ",\n\"reports\":[";
+    mute.sink.str("");
+    int seen = 0;
+    for (int k = 0; k < reports * bin; k++) {
+      ptc.step();
+      const std::string text = mute.sink.str();
+      if (text.empty()) continue;
+      mute.sink.str("");
+      const size_t at = text.find("Total log-evidence:");
+      if (at == std::string::npos) continue;
+      js << (seen ? "," : "") << "\n {\"step\":" << k + 1 << ",\"lines\":[";
+      std::istringstream in(text.substr(at));
+      std::string line;
+      bool first = true;
+      while (std::getline(in, line)) { js << (first ? "" : ",") << jstr(line); first = false; }
+      js << "],\"best\":" << jnum(ptc.bestEvidenceErr()) << ",";
+      evid_counts(js, ptc, Nt);
+      js << ",\"query\":";
+      evid_ratios(js, ptc, Nt, bin);
+      js << "}";
+      seen++;
+    }
+    if (seen != reports) { fprintf(stderr, "golden-evidence: %d reports, not %d\n", seen, reports); return 2; }
+    js << "],\n";
+    evid_counts(js, ptc, Nt);
+    js << ",\n";
+    if (!evid_llikes(js, ptc, Nt)) return 2;
+    js << "}";
+    globalRNG.reset();
+  }
+  js << "],\n\"groups\":[";
+  struct gcase { const char* name; int D, Nt, every, Ninit; double evolve; };
+  const gcase gcs[] = {{"A", 2, 4, 1, 1, 0.0}, {"D", 1, 4, 3, 1, 0.01}, {"B", 1, 3, 3, 5, 0.0}, {"C", 1, 2, 2, 3, 0.0}};   // descending Ntemps (see above)
+  const int nladders = 5;
+  for (size_t ig = 0; ig < sizeof gcs / sizeof gcs[0]; ig++) {
+    const gcase& G = gcs[ig];
+    const double Tmax = 12.0, swap_rate = 0.3, halfwidth = 4.0;
+    js << (ig ? "," : "") << "\n{\"name\":\"" << G.name << "\",\"D\":" << G.D << ",\"Nt\":" << G.Nt << ",\"add_every_N\":" << G.every << ",\"Ninit\":" << G.Ninit
+       << ",\"evolve_rate\":" << jnum(G.evolve) << ",\"Tmax\":" << jnum(Tmax) << ",\"swap_rate\":" << jnum(swap_rate) << ",\n\"ladders\":[";
+    for (int k = 0; k < nladders; k++) {
+      const int nsteps = 130 + 43 * k + 9 * (int)ig;
+      const double seed = 0.27 + 0.037 * ig + 0.0041 * k;
+      ProbabilityDist::setSeed(seed);
+      globalRNG.reset(ProbabilityDist::getPRNG());
+      stateSpace sp(G.D);
+      std::valarray<double> c(0.0, G.D), h(halfwidth, G.D), sig(1.3, G.D);
+      std::valarray<int> t(mixed_dist_product::uniform, G.D);
+      mixed_dist_product prior(&sp, t, c, h);
+      grid_like like(&sp);
+      parallel_tempering_chains ptc(G.Nt, Tmax, swap_rate, G.every, false, false);
+      ptc.initialize(&like, &prior, G.Ninit);
+      std::vector<double> beta0;
+      for (int r = 0; r < G.Nt; r++) beta0.push_back(ptc.subchain(r)->invTemp());
+      if (G.evolve > 0) ptc.evolve_temps(G.evolve);
+      gaussian_prop prop(sig);
+      ptc.set_proposal(prop);
+      for (int s = 0; s < nsteps; s++) ptc.step();
+      int lo = ptc.subchain(0)->getStep(), hi = lo;
+      for (int r = 1; r < G.Nt; r++) { lo = std::min(lo, ptc.subchain(r)->getStep()); hi = std::max(hi, ptc.subchain(r)->getStep()); }
+      std::vector<int> ilens = {1, 2, 3, 4, 7, 50, lo - 1, lo, lo + 1, hi, hi + 1, 1000000};
+      js << (k ? "," : "") << "\n {\"seed\":" << jnum(seed) << ",\"nsteps\":" << nsteps << ",\"invtemp0\":" << jarr(beta0) << ",";
+      evid_counts(js, ptc, G.Nt);
+      js << ",\n  \"queries\":[";
+      for (size_t q = 0; q < ilens.size(); q++) { js << (q ? "," : "") << "\n  "; evid_ratios(js, ptc, G.Nt, ilens[q]); }
+      js << "],\n  ";
+      if (!evid_llikes(js, ptc, G.Nt)) return 2;
+      js << "}";
+      globalRNG.reset();
+    }
+    js << "]}";
+  }
+  js << "]}\n";
+  return 0;
+}
+
+static int golden_evidence() {
+  std::ostringstream js;
+  int rc;
+  {
+    cout_mute mute;
+    rc = evidence_run(js, mute);
+  }
+  if (rc) return rc;
+  std::cout << js.str();
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && !strcmp(argv[1], "golden-basic")) {
     ProbabilityDist::setSeed(0.224);  // chain() constructors draw their seed from the master generator (chain.hh:58-62)
@@ -863,7 +1040,8 @@ int main(int argc, char** argv) {
   if (argc >= 2 && !strcmp(argv[1], "golden-eigen")) return golden_eigen();
   if (argc >= 2 && !strcmp(argv[1], "golden-de")) return golden_de();
   if (argc >= 2 && !strcmp(argv[1], "golden-ess")) return golden_ess();
+  if (argc >= 2 && !strcmp(argv[1], "golden-evidence")) return golden_evidence();
   if (argc >= 3 && !strcmp(argv[1], "bench")) return bench(argv[2]);
-  fprintf(stderr, "usage: %s golden-basic | golden-trace <1..12> | golden-eigen | golden-de | golden-ess | bench <specfile>\n", argv[0]);
+  fprintf(stderr, "usage: %s golden-basic | golden-trace <1..12> | golden-eigen | golden-de | golden-ess | golden-evidence | bench <specfile>\n", argv[0]);
   return 2;
 }

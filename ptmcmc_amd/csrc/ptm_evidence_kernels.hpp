@@ -33,7 +33,8 @@ struct EvidSrc {
   int HC, cap, W, Nt, add_every, ilen;
 };
 __device__ __forceinline__ double evid_beta(const EvidSrc& s, int r, int w) { return s.beta_w ? s.beta_w[(long long)w * s.Nt + r] : s.beta[r]; }
-// MH_chain::get_state_idx with Ninit = 1, Nzero = 0: an i outside [0, Nhist) becomes Nhist - 1 (C division, towards zero)
+// MH_chain::get_state_idx in the ring's numbering (the start state is row 0 however many initial rows the reference would hold in
+// front, Nzero = 0): an i outside [0, Nhist) becomes Nhist - 1 (C division, towards zero)
 __device__ __forceinline__ long long evid_idx(long long i, long long nhist, int add_every) {
   if (i < 0 || i >= nhist) i = nhist - 1;
   return 1 + i / add_every;

@@ -1706,21 +1706,26 @@ class evidence_estimator {
     std::vector<int> count;         // [Nt] rows of each rung's window
     bool complete;                  // false: a row of a window was missing (nothing else is to be believed then)
   };
-  static long long state_idx(long long i, long long Nhist, int add_every_N) {   // Ninit = 1, Nzero = 0
+  // MH_chain::get_state_idx with Nzero = 0: row Ninit + i / add_every_N, Ninit the rows initialize(n) put in front (n of them).
+  // The ring's numbering is Ninit = 1 whatever n was: the start state is row 0, further initial draws are kept in front of it.  The
+  // reference's own windows on ladders initialised with 1, 3 and 5 rows (tests/golden/evidence.json.gz) are those of raw row = ring
+  // row + Ninit - 1 and never reach a row in front of Ninit, so the initial rows do not enter the evidence.
+  static long long state_idx(long long i, long long Nhist, int add_every_N, int Ninit = 1) {
     if (i < 0 || i >= Nhist) i = Nhist - 1;
-    return 1 + i / add_every_N;
+    return Ninit + i / add_every_N;
   }
-  static void window(long long Nhist, int ilen, int add_every_N, long long& first, long long& last) {
-    first = state_idx(Nhist - ilen, Nhist, add_every_N);
-    last = state_idx(Nhist, Nhist, add_every_N);
+  static void window(long long Nhist, int ilen, int add_every_N, long long& first, long long& last, int Ninit = 1) {
+    first = state_idx(Nhist - ilen, Nhist, add_every_N, Ninit);
+    last = state_idx(Nhist, Nhist, add_every_N, Ninit);
   }
-  // one ladder: Nhist[Nt] add_state calls and beta[Nt] current inverse temperatures of its chains
-  static result estimate(int Nt, int add_every_N, int ilen, const long long* Nhist, const double* beta, const reader& read) {
+  // one ladder: Nhist[Nt] add_state calls and beta[Nt] current inverse temperatures of its chains; with Ninit != 1 the reader is
+  // asked for the reference's raw rows
+  static result estimate(int Nt, int add_every_N, int ilen, const long long* Nhist, const double* beta, const reader& read, int Ninit = 1) {
     result r;
     r.up.assign(Nt > 1 ? Nt - 1 : 0, 0.0); r.down = r.up; r.count.assign(Nt, 0); r.complete = true; r.evidence = 0;
     auto ratio = [&](int ia, int ib) {
       long long first, last;
-      window(Nhist[ib], ilen, add_every_N, first, last);
+      window(Nhist[ib], ilen, add_every_N, first, last, Ninit);
       const double amb = beta[ia] - beta[ib];
       double sum = 0, count = 0;
       for (long long row = first; row < last; row++) {

@@ -2,6 +2,7 @@
 // stdin, whitespace separated:
 //   ladder Nt W add_every_N ilen   then per chain (rung-major, chain = rung * W + walker): Nhist nrows llike[0..nrows-1]
 //                                  then beta[walker][rung] (W * Nt values: every walker's own ladder)
+//   ladder_init Ninit Nt W add_every_N ilen ...   the same with the rows in the reference's raw numbering, Ninit initial rows in front
 //   records n verbose v[0..n-1]
 // stdout: per walker "w <evidence> | up.. | down.. | count.." (%.17g); per pushed value its lines, then "best <%.17g>".
 #include <cstdio>
@@ -16,8 +17,9 @@ using namespace ptmgpu;
 int main() {
   std::string what;
   while (std::cin >> what) {
-    if (what == "ladder") {
-      int Nt, W, a, ilen;
+    if (what == "ladder" || what == "ladder_init") {
+      int Nt, W, a, ilen, Ninit = 1;
+      if (what == "ladder_init") std::cin >> Ninit;
       std::cin >> Nt >> W >> a >> ilen;
       std::vector<long long> nhist((size_t)Nt * W);
       std::vector<std::vector<double> > rows((size_t)Nt * W);
@@ -37,7 +39,7 @@ int main() {
           if (row < 0 || (size_t)row >= v.size()) return false;
           ll = v[(size_t)row];
           return true;
-        });
+        }, Ninit);
         printf("w %.17g |", res.evidence);
         for (int i = 0; i < Nt - 1; i++) printf(" %.17g", res.up[(size_t)i]);
         printf(" |");

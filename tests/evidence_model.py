@@ -2,8 +2,13 @@
 one rounding per operation) in the reference's order of operations.  What it restates:
 
   window    MH_chain::get_state_idx (chain.cc:1041-1049) of Nhist - ilen and Nhist, as parallel_tempering_chains::log_evidence_ratio
-            calls it (chain.cc:1988-1989): an index outside [0, Nhist) becomes Nhist - 1; with Ninit = 1 and Nzero = 0 the saved row of
-            nominal step i is 1 + i / add_every_N (C division).  The newest saved row is left out; Nhist < ilen gives an empty window.
+            calls it (chain.cc:1988-1989): an index outside [0, Nhist) becomes Nhist - 1; with Nzero = 0 the saved row of nominal
+            step i is Ninit + i / add_every_N (C division).  The newest saved row is left out; Nhist < ilen gives an empty window.
+            Ninit is the number of rows MH_chain::initialize(n) put in front (n of them, chain.cc:846-876).  The engine's ring calls
+            the start state row 0 and the row of step i row 1 + i / add_every_N whatever n was -- further initial draws are kept in
+            front of row 0 --, which is ninit = 1 here, the default.  The recorded ladders of tests/golden/evidence.json.gz
+            (initialize(5), (3) among them) confirm that the two numberings meet: raw row = ring row + Ninit - 1, and no window
+            reaches a row in front of Ninit.
   ratio     chain.cc:1990-2007: amb = beta_a - beta_b; x = llike_b[row] * amb; sum += x; count++; sum / count (0 / 0 = NaN).
   total     chain.cc:1585-1597: up[i] = ratio(i, i+1); down[i] = -ratio(i+1, i); evidence += (up[i] + down[i]) / 2.0; then
             evidence += (up[Nt-2] + down[Nt-2]) / 2.0 / (beta[Nt-2] / beta[Nt-1] - 1).
@@ -22,19 +27,19 @@ def cdiv(a, b):
     return q if (a >= 0) == (b > 0) else -q
 
 
-def state_idx(i, nhist, add_every):
+def state_idx(i, nhist, add_every, ninit=1):
     if i < 0 or i >= nhist:
         i = nhist - 1
-    return 1 + cdiv(i, add_every)
+    return ninit + cdiv(i, add_every)
 
 
-def window(nhist, ilen, add_every):
-    return state_idx(nhist - ilen, nhist, add_every), state_idx(nhist, nhist, add_every)
+def window(nhist, ilen, add_every, ninit=1):
+    return state_idx(nhist - ilen, nhist, add_every, ninit), state_idx(nhist, nhist, add_every, ninit)
 
 
-def ratio(llike_of_row, nhist_b, beta_a, beta_b, ilen, add_every):
+def ratio(llike_of_row, nhist_b, beta_a, beta_b, ilen, add_every, ninit=1):
     """llike_of_row(row) -> float of chain b; returns (ratio, rows)"""
-    first, last = window(nhist_b, ilen, add_every)
+    first, last = window(nhist_b, ilen, add_every, ninit)
     amb = beta_a - beta_b
     total, count = 0.0, 0
     for row in range(first, last):
@@ -44,14 +49,14 @@ def ratio(llike_of_row, nhist_b, beta_a, beta_b, ilen, add_every):
     return (total / count if count else NAN), count
 
 
-def total(readers, nhist, beta, ilen, add_every):
+def total(readers, nhist, beta, ilen, add_every, ninit=1):
     """one ladder: readers[r](row) -> llike, nhist[r], beta[r].  Returns (evidence, up[Nt-1], down[Nt-1], count[Nt])"""
     nt = len(beta)
     up, down, count = [0.0] * (nt - 1), [0.0] * (nt - 1), [0] * nt
     evidence = 0.0
     for i in range(nt - 1):
-        up[i], count[i + 1] = ratio(readers[i + 1], nhist[i + 1], beta[i], beta[i + 1], ilen, add_every)
-        d, count[i] = ratio(readers[i], nhist[i], beta[i + 1], beta[i], ilen, add_every)
+        up[i], count[i + 1] = ratio(readers[i + 1], nhist[i + 1], beta[i], beta[i + 1], ilen, add_every, ninit)
+        d, count[i] = ratio(readers[i], nhist[i], beta[i + 1], beta[i], ilen, add_every, ninit)
         down[i] = -d
         evidence = evidence + (up[i] + down[i]) / 2.0
     evidence = evidence + (up[nt - 2] + down[nt - 2]) / 2.0 / (beta[nt - 2] / beta[nt - 1] - 1)
