@@ -549,6 +549,10 @@ int ptm_debug_boxmuller(int device, const uint32_t* k1, const uint32_t* k2, doub
 /* exhaustive scan of all 2^32 Box-Muller radius arguments a = -2 ln((k+.5)/2^32): for how many is the hot path's
  * unscaled Newton square root NOT the correctly rounded one (or a outside its domain).  Must be 0. */
 int ptm_debug_sqrt_scan(int device, uint64_t* mismatches);
+/* exhaustive scans of the box pre-pass's single-precision Box-Muller against the sweep's: out[0] max |r_f32 - r| over all 2^32 first
+ * arguments, out[1] the largest r_f32, out[2] how many gave a NaN; out[3] max |sin_f32 - sin|, |cos_f32 - cos| over all 2^32 second
+ * arguments, out[4] how many gave a NaN; out[5], out[6] the margin's constants PTM_BP_DZ and PTM_BP_F32_SLACK; out[7] 0. */
+int ptm_debug_boxmuller_f32_scan(int device, double out[8]);
 /* evaluate lprior / llike of arbitrary states with the engine's problem description: X[n][D] */
 /* device-memory helpers for callers without a GPU array library (tests, tools) */
 int ptm_dev_alloc(size_t bytes, void** out);

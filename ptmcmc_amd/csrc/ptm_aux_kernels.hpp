@@ -403,6 +403,38 @@ __global__ void debug_sqrt_scan_kernel(unsigned long long* mismatches) {
   if (out) atomicAdd(mismatches + 1, out);
 }
 
+// exhaustive scans behind PTM_BP_DZ (ptm_sweep_plan.hpp): the single-precision Box-Muller of the box pre-pass against the sweep's.
+// which == 0: all 2^32 first arguments, |r_f32 - bm_sqrt(bm_neg2log(k1))|; which == 1: all 2^32 second arguments, the float sine and
+// cosine against boxmuller_finish at radius 1.  out[0]: the largest difference, out[1]: the largest |r_f32| (which == 0) as bit
+// patterns of non-negative doubles, which order as unsigned integers do; out[2]: the arguments that gave a NaN.
+__global__ __launch_bounds__(256) void debug_boxmuller_f32_scan_kernel(int which, unsigned long long* out) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  double worst = 0.0, top = 0.0;
+  unsigned long long nan = 0;
+  for (uint64_t k = tid; k < (1ull << 32); k += stride) {
+    float r, sn, cs;
+    double d;
+    if (which == 0) {
+      boxmuller_f32_parts((uint32_t)k, 0u, r, sn, cs);
+      d = __builtin_fabs((double)r - bm_sqrt(bm_neg2log((uint32_t)k, (const double*)BM_TABLE)));
+      top = __builtin_fabs((double)r) > top ? __builtin_fabs((double)r) : top;
+    } else {
+      double z0, z1;
+      boxmuller_f32_parts(0u, (uint32_t)k, r, sn, cs);
+      boxmuller_finish(1.0, (uint32_t)k, (const double*)BM_TABLE, z0, z1);
+      const double dc = __builtin_fabs((double)cs - z0), ds = __builtin_fabs((double)sn - z1);
+      d = dc > ds ? dc : ds;
+      if (dc != dc || ds != ds) d = dc + ds;
+    }
+    if (d != d) nan++;
+    else worst = d > worst ? d : worst;
+  }
+  atomicMax(out, (unsigned long long)__double_as_longlong(worst));
+  atomicMax(out + 1, (unsigned long long)__double_as_longlong(top));
+  if (nan) atomicAdd(out + 2, nan);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Calibration of the box a measurement runs on (ptm_calibrate; bench.py puts the figures beside its roofline): MI355X devices of
 // one pool differ by several per cent in the clock they hold under an f64 load, and a bench line cannot otherwise tell a slow

@@ -341,6 +341,26 @@ __device__ __forceinline__ void boxmuller(uint32_t k1, uint32_t k2, Tab tab, dou
   boxmuller_finish(bm_sqrt(bm_neg2log(k1, tab)), k2, tab, z0, z1);
 }
 
+// The same pair in single precision, for a kernel that only needs the normals to three digits (the box pre-pass, ptm_box_prefilter.hpp):
+// u = (k1 + 0.5) / 2^32 and the angle in revolutions, both rounded to float, r = sqrt(-2 ln2 log2 u) with v_log_f32 and v_sqrt_f32,
+// v_sin_f32 / v_cos_f32 (they take revolutions).  No table, no f64.  float(k1) rounds by up to 128 near 2^32 and u reaches 1 there:
+// the radius is 0 where the exact one is up to 2.4e-4, which is the largest error of the pair (tests/test_gpu_box_prefilter_f32.py scans
+// all 2^32 arguments of either half against bm_sqrt(bm_neg2log()) and boxmuller_finish).  The max() keeps the root's argument at or
+// above zero whatever the log's last bit does at u = 1 (and turns a NaN into 0).
+__device__ __forceinline__ void boxmuller_f32_parts(uint32_t k1, uint32_t k2, float& r, float& sn, float& cs) {
+  const float u = ((float)k1 + 0.5f) * 2.3283064365386963e-10f;
+  r = __builtin_sqrtf(__builtin_fmaxf(-1.3862943611198906f * __builtin_amdgcn_logf(u), 0.0f));
+  const float t = ((float)k2 + 0.5f) * 2.3283064365386963e-10f;
+  sn = __builtin_amdgcn_sinf(t);
+  cs = __builtin_amdgcn_cosf(t);
+}
+__device__ __forceinline__ void boxmuller_f32(uint32_t k1, uint32_t k2, float& z0, float& z1) {
+  float r, sn, cs;
+  boxmuller_f32_parts(k1, k2, r, sn, cs);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
 // fmod restated for the boundary wrap (states.cc:24,39): exact for |x/w| < 2^52
 __device__ __forceinline__ double fmod_det(double x, double w) {
   const double q = __builtin_trunc(x / w);

@@ -145,6 +145,11 @@ struct ptm_engine {
   unsigned char *pf_flag = nullptr, *h_pf_flag = nullptr;   // (h_pf_flag: pinned, so that the flags' upload waits for nothing)
   unsigned long long* pf_counts = nullptr;
   std::vector<double> pf_sigma;
+  // ... and for the single-precision kernel the margins of those coordinates (ptm_sweep_plan.hpp: prefilter_margins), made beside the
+  // sigmas; their image for the kernel, the faces' slack added and rounded up to float, is uploaded with the flags (pf_margin, staged in
+  // pinned h_pf_margin)
+  std::vector<double> pf_margin_nat;
+  float *pf_margin = nullptr, *h_pf_margin = nullptr;
   bool pf_dirty = true;
   int pf_flagged = 0, pf_grid = 0;
   bool touched = false;
@@ -518,7 +523,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
   for (auto& b : e->host_blocks) (void)hipHostFree(b.first);
   void* ptrs[] = {e->xdev, e->rowof, e->ll, e->lp, e->ntries, e->naccept, e->last_type, e->arr_below, e->arr_above, e->mv_src, e->mv_dst, e->mv_n,
                   e->err, e->nhist, e->swap_cnt, e->touch, e->swap_log, e->hist.x, e->hist.ll, e->hist.lp, e->hist.meta, e->map.lpost, e->map.ll, e->map.lp, e->map.x, e->blo,
-                  e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt, e->pidx, e->pcnt, e->pf_flag, e->pf_counts,
+                  e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt, e->pidx, e->pcnt, e->pf_flag, e->pf_counts, e->pf_margin,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
                   e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
                   e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws};
@@ -526,6 +531,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
     if (p) (void)hipFree(p);
   if (e->h_sums) (void)hipHostFree(e->h_sums);
   if (e->h_pf_flag) (void)hipHostFree(e->h_pf_flag);
+  if (e->h_pf_margin) (void)hipHostFree(e->h_pf_margin);
   for (hipEvent_t ev : e->kev) (void)hipEventDestroy(ev);
   if (e->t0) (void)hipEventDestroy(e->t0);
   if (e->t1) (void)hipEventDestroy(e->t1);
@@ -962,7 +968,12 @@ extern "C" int ptm_set_proposals(ptm_engine* e, int kind, const double* factors,
   if ((rc = upload(e->onedfrac, f.data(), (size_t)nloc, e->stream))) return rc;
   e->prop_kind = kind; e->prop_stride = stride; e->have_prop = 1;
   e->pf_sigma.assign((size_t)nloc * PREFILTER_DIMS, 0.0);
-  for (int r = 0; r < nloc; ++r) prefilter_sigmas(kind == PTM_PROP_DIAG, factors + (size_t)r * (kind == PTM_PROP_DIAG ? D : D * D), D, &e->pf_sigma[(size_t)r * PREFILTER_DIMS]);
+  e->pf_margin_nat.assign((size_t)nloc * PREFILTER_DIMS, 0.0);
+  for (int r = 0; r < nloc; ++r) {
+    const double* fr = factors + (size_t)r * (kind == PTM_PROP_DIAG ? D : D * D);
+    prefilter_sigmas(kind == PTM_PROP_DIAG, fr, D, &e->pf_sigma[(size_t)r * PREFILTER_DIMS]);
+    prefilter_margins(kind == PTM_PROP_DIAG, fr, D, &e->pf_margin_nat[(size_t)r * PREFILTER_DIMS]);
+  }
   e->pf_dirty = true;
   return PTM_OK;
 }
@@ -1271,6 +1282,7 @@ extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double
     if ((rc = upload(e->prop_tiles + (size_t)local_rung * ntile * 64, tiles.data(), tiles.size(), e->stream))) return rc;
   }
   prefilter_sigmas(kind == PTM_PROP_DIAG, factor, D, &e->pf_sigma[(size_t)local_rung * PREFILTER_DIMS]);
+  prefilter_margins(kind == PTM_PROP_DIAG, factor, D, &e->pf_margin_nat[(size_t)local_rung * PREFILTER_DIMS]);
   e->pf_dirty = true;
   if (one_d_frac >= 0) {
     if (one_d_frac > 1) return fail(PTM_ERR_INVALID, "oneDfrac must be in [0,1]");
@@ -1563,6 +1575,15 @@ static int prefilter_flags(ptm_engine* e) {
     e->pf_flagged += fl[r];
   }
   HIPCHK(hipMemcpyAsync(e->pf_flag, fl, (size_t)e->nloc, hipMemcpyHostToDevice, e->stream));
+  // the single-precision kernel's margins: the factor's (infinite while there is none: nothing settles) plus the faces' slack, as
+  // floats; lane group q of a wave owns dimensions q + 4 i and reads its four side by side
+  const size_t nm = (size_t)e->nloc * PREFILTER_DIMS;
+  if (!e->h_pf_margin) HIPCHK(hipHostMalloc((void**)&e->h_pf_margin, nm * sizeof(float), hipHostMallocDefault));
+  for (int r = 0; r < e->nloc; ++r)
+    for (int d = 0; d < PREFILTER_DIMS; ++d)
+      e->h_pf_margin[(size_t)r * PREFILTER_DIMS + 4 * (d & 3) + (d >> 2)] = d >= nd ? 0.0f :
+          prefilter_margin_f32((e->pf_margin_nat.size() == nm ? e->pf_margin_nat[(size_t)r * PREFILTER_DIMS + d] : INFINITY) + prefilter_face_slack(e->h_plo[d], e->h_phi[d]));
+  HIPCHK(hipMemcpyAsync(e->pf_margin, e->h_pf_margin, nm * sizeof(float), hipMemcpyHostToDevice, e->stream));
   e->pf_dirty = false;
   return PTM_OK;
 }
@@ -1603,7 +1624,8 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     if (pre) {
       if (!e->pidx) {
         int rc;
-        if ((rc = dalloc(&e->pidx, (size_t)e->Nc)) || (rc = dalloc(&e->pcnt, (size_t)e->nloc)) || (rc = dalloc(&e->pf_flag, (size_t)e->nloc)) || (rc = dalloc(&e->pf_counts, 2))) return rc;
+        if ((rc = dalloc(&e->pidx, (size_t)e->Nc)) || (rc = dalloc(&e->pcnt, (size_t)e->nloc)) || (rc = dalloc(&e->pf_flag, (size_t)e->nloc)) || (rc = dalloc(&e->pf_counts, 2)) ||
+            (rc = dalloc(&e->pf_margin, (size_t)e->nloc * PREFILTER_DIMS))) return rc;
         HIPCHK(hipMemsetAsync(e->pf_counts, 0, 16, e->stream));
         e->pf_dirty = true;
       }
@@ -1623,11 +1645,17 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
       b.seed = e->cfg.seed; b.step = e->step;
       b.x = p.x; b.ll = e->ll; b.lp = e->lp; b.beta = e->beta; b.prop_tiles = e->prop_tiles; b.box_row = e->box_row; b.ntries = e->ntries;
       b.pidx = e->pidx; b.pcnt = e->pcnt; b.cidx = e->cidx; b.ccnt = e->ccnt; b.counts = e->pf_counts;
-      const size_t lds = BoxPreLds(nullptr, nr).bytes;
-      if (!e->pf_grid) {   // a persistent grid: the blocks the device holds at once
+      // single precision behind a margin unless PTM_BOX_PREFILTER_EXACT asks for the sweep's own arithmetic: the same chains either way
+      const bool exact = sweep_env().prefilter_exact != 0;
+      BoxPreF32 bf;
+      bf.b = b; bf.margin = e->pf_margin;
+      const size_t lds = exact ? BoxPreLds(nullptr, nr).bytes : BoxPreF32Lds(nullptr, nr).bytes;
+      if (!e->pf_grid) {   // a persistent grid: the blocks the device holds at once, of the kernel that is launched
         int per_cu = 0, dev = 0;
         hipDeviceProp_t pr;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_kernel, 256, BoxPreLds(nullptr, e->nloc).bytes) != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
+        const hipError_t oc = exact ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_kernel, 256, BoxPreLds(nullptr, e->nloc).bytes)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_f32_kernel, 256, BoxPreF32Lds(nullptr, e->nloc).bytes);
+        if (oc != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
         HIPCHK(hipGetDevice(&dev));
         HIPCHK(hipGetDeviceProperties(&pr, dev));
         e->pf_grid = per_cu * (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
@@ -1635,7 +1663,9 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
         if (cap > 0 && cap < e->pf_grid) e->pf_grid = cap;
       }
       const long long tiles = (long long)nr * ((e->W + 255) / 256);
-      hipLaunchKernelGGL(box_prefilter_kernel, dim3((unsigned)(tiles < e->pf_grid ? tiles : e->pf_grid)), dim3(256), lds, e->stream, b);
+      const dim3 grid((unsigned)(tiles < e->pf_grid ? tiles : e->pf_grid));
+      if (exact) hipLaunchKernelGGL(box_prefilter_kernel, grid, dim3(256), lds, e->stream, b);
+      else hipLaunchKernelGGL(box_prefilter_f32_kernel, grid, dim3(256), lds, e->stream, bf);
       HIPCHK(hipGetLastError());
     }
     p.cidx = e->cidx; p.ccnt = e->ccnt; p.cidx_slot = labelled ? 1 : 0;
@@ -3662,6 +3692,28 @@ extern "C" int ptm_debug_sqrt_scan(int device, uint64_t* mismatches) {
   HIPCHK(hipMemcpy(v, d, 16, hipMemcpyDeviceToHost));
   (void)hipFree(d);
   *mismatches = v[0] + v[1];   // arguments where bm_sqrt is not the correctly rounded root + arguments outside its domain
+  return PTM_OK;
+}
+
+extern "C" int ptm_debug_boxmuller_f32_scan(int device, double out[8]) {
+  int rc = need_device();
+  if (rc) return rc;
+  if (!out) return fail(PTM_ERR_INVALID, "null argument");
+  if (device >= 0) HIPCHK(hipSetDevice(device));
+  unsigned long long* d = nullptr;
+  HIPCHK(hipMalloc((void**)&d, 48));
+  HIPCHK(hipMemset(d, 0, 48));
+  hipLaunchKernelGGL(debug_boxmuller_f32_scan_kernel, dim3(256 * 16), dim3(256), 0, 0, 0, d);
+  hipLaunchKernelGGL(debug_boxmuller_f32_scan_kernel, dim3(256 * 16), dim3(256), 0, 0, 1, d + 3);
+  HIPCHK(hipGetLastError());
+  unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
+  HIPCHK(hipMemcpy(v, d, 48, hipMemcpyDeviceToHost));
+  (void)hipFree(d);
+  double w[6];
+  memcpy(w, v, sizeof w);   // (the maxima are bit patterns of doubles)
+  out[0] = w[0]; out[1] = w[1]; out[2] = (double)v[2];   // radius: max |r_f32 - r|, max r_f32, NaNs
+  out[3] = w[3]; out[4] = (double)v[5];                  // sine and cosine: max difference, NaNs
+  out[5] = PTM_BP_DZ; out[6] = PTM_BP_F32_SLACK; out[7] = 0.0;
   return PTM_OK;
 }
 

@@ -226,6 +226,26 @@ struct BoxPreLds {
   PTM_LDS_FN BoxPreLds(void* base, int nrung) { LdsCarve c(base); carve(c, nrung); }
 };
 
+// ---- box_prefilter_f32_kernel (ptm_box_prefilter.hpp): the same launch, drawing without tables
+struct BoxPreF32Lds {
+  double* lbox;   // [64] prior box
+  int* tpre;      // [nrung] inclusive prefix of the rungs' 256-walker tiles
+  int* pcn;       // [nrung] the rungs' list lengths
+  int* tsum;      // [257]
+  size_t bytes;
+  template <class C>
+  PTM_LDS_FN void carve(C& c, int nrung) {
+    c.take(lbox, "lbox", 64);
+    c.take(tpre, "tpre", nrung);
+    c.take(pcn, "pcn", nrung);
+    c.take(tsum, "tsum", TILE_SCAN_INTS);
+    c.slack("slack", TILE_SCAN_SLACK);
+    bytes = c.size();
+  }
+  BoxPreF32Lds() = default;
+  PTM_LDS_FN BoxPreF32Lds(void* base, int nrung) { LdsCarve c(base); carve(c, nrung); }
+};
+
 // ---- sweep_kernel (ptm_kernels.hpp): the 20 KB of Box-Muller tables every variant stages; the builds whose waves share a rung and
 // whose factor is not diagonal (staged) keep one copy of the rung's factor per wave too (4 waves per block)
 struct GeneralLds {

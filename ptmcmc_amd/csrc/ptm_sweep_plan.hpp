@@ -36,12 +36,14 @@ struct SweepFacts {
 // (prefilter_flag below); PTM_PREFILTER_GRID=n (n >= 1) caps the pre-pass's grid at n blocks, so that a small population walks many
 // tiles per block as a big one does (tests; the results do not depend on it); PTM_DE_MFMA=0 keeps differential evolution off the
 // matrix cores, =1 gives de_mfma32_kernel every population it is eligible for, unset: its population rule decides (de_mfma_applies
-// below).  Read once per process.
+// below); PTM_BOX_PREFILTER_EXACT=1 runs the pre-pass on its double-precision kernel.  Read once per process.
 struct SweepEnv {
   bool force_valu, compact_ok;
   int prefilter;        // 0: the estimate decides, 1: every eligible rung, -1: off
   int prefilter_grid;   // 0: the blocks the device holds at once, n >= 1: at most n blocks
   int de_mfma;          // PTM_DE_MFMA -- 0 (unset): the population rule of de_mfma_applies decides, 1: every eligible population, -1 ("0"): off
+  int prefilter_exact;  // PTM_BOX_PREFILTER_EXACT -- 0 (unset, "0"): the pre-pass draws in single precision behind a margin (box_prefilter_f32_kernel),
+                        // 1: in the sweep's double precision (box_prefilter_kernel: A/B runs inside one library, and a fallback).  The chains are the same
 };
 inline const SweepEnv& sweep_env() {
   static const SweepEnv v = [] {
@@ -50,9 +52,10 @@ inline const SweepEnv& sweep_env() {
     const char* b = getenv("PTM_BOX_PREFILTER");
     const char* g = getenv("PTM_PREFILTER_GRID");
     const char* d = getenv("PTM_DE_MFMA");
+    const char* x = getenv("PTM_BOX_PREFILTER_EXACT");
     const long gn = (g && *g) ? strtol(g, nullptr, 10) : 0;
     return SweepEnv{f && *f && *f != '0', !(c && *c == '0'), (b && *b) ? (*b == '0' ? -1 : 1) : 0, gn >= 1 ? (int)(gn < (1 << 20) ? gn : (1 << 20)) : 0,
-                    (d && *d) ? (*d == '0' ? -1 : 1) : 0};
+                    (d && *d) ? (*d == '0' ? -1 : 1) : 0, (x && *x && *x != '0') ? 1 : 0};
   }();
   return v;
 }
@@ -177,6 +180,59 @@ inline void prefilter_sigmas(bool diag, const double* factor, int D, double* sig
     sigma[d] = std::sqrt(s2);
   }
 }
+// ---- the single-precision pre-pass's margin (box_prefilter_f32_kernel) ------------------------------------------------------------
+// That kernel forms a_d = sum_k float(T[d][k]) z32_k in float where the sweep forms A_d = sum_k T[d][k] z_k in double, and settles a
+// chain only where x_d + a_d is outside the box by more than m_d >= |a_d - A_d|.  Two terms, per unit of S_d = sum_k |T[d][k]|:
+//   PTM_BP_DZ          |z32 - z| per normal: the float radius, sine and cosine against the sweep's and the rounding of their product.
+//                      Scanned over all 2^32 arguments of either half on the device (tests/test_gpu_box_prefilter_f32.py; the maxima
+//                      are in DESIGN 3.1): max |dr| = 2.45e-4 where float(k1) rounds to 2^32, 6.76 max |dtrig| and 2^-22 for the
+//                      product add a few 1e-6.  The constant is more than twice their sum; the test holds it to that.
+//   PTM_BP_F32_SLACK   the rounding of T to float and of the float products and sums.  With u = 2^-24: float(T) = T (1 + e0), |e0| <= u,
+//                      and in ANY order of summation (chained fused multiply-adds, plain products, partial sums added in a tree) a
+//                      term of a 16-term sum passes through at most one product rounding and 15 additions, so what it arrives as is
+//                      T z32 (1 + e0)(1 + e1)...(1 + e16), and |prod (1 + e) - 1| <= 17 u / (1 - 17 u) = 1.0133e-6 (Higham, Accuracy
+//                      and Stability of Numerical Algorithms, lemma 3.1).  Times |z32| <= 6.7637 + PTM_BP_DZ: 6.86e-6 S_d, rounded up.
+//                      (The sweep's own double-precision sum is off by 17 2^-53 6.77 S_d = 1.3e-14 S_d: inside the rounding up.)
+//   Under- and overflow of float: a product or a factor entry below 2^-126 loses at most 2^-126 absolutely whether the hardware
+//   flushes it or not -- 16 terms and their 16 factor entries times 6.77: PTM_BP_F32_TINY for every row that is not zero; a row with
+//   S_d > 1e37 could pass FLT_MAX in a partial sum (16 x 6.77 x ...), and gets an infinite margin: it settles nothing.
+// A zero row has a = A = 0 and the margin 0.  The double-precision roundings of x + a and of lo - m, hi + m are no part of this
+// function: prefilter_face_slack covers them from the faces they happen at.
+#define PTM_BP_DZ 6.0e-4
+#define PTM_BP_F32_SLACK 7.0e-6
+#define PTM_BP_F32_TINY 3.0e-36
+inline double prefilter_margin(double sumabs) {
+  if (sumabs == 0.0) return 0.0;
+  if (!(sumabs <= 1e37)) return INFINITY;   // (a NaN too)
+  return (PTM_BP_DZ + PTM_BP_F32_SLACK) * sumabs + PTM_BP_F32_TINY;
+}
+// the margins of a rung's first 16 dimensions (factor: row-major D x D, or D sigmas); a lower-triangular factor's rows d < 16 end at column d
+inline void prefilter_margins(bool diag, const double* factor, int D, double* margin) {
+  for (int d = 0; d < PREFILTER_DIMS; ++d) {
+    double s = 0.0;
+    if (d < D) {
+      if (diag) s = std::fabs(factor[d]);
+      else for (int k = 0; k < D; ++k) s += std::fabs(factor[(size_t)d * D + k]);
+    }
+    margin[d] = prefilter_margin(s);
+  }
+}
+// x + double(a) is rounded in the pre-pass, x + A in the sweep, lo - m and hi + m on their way into the comparison: four roundings of
+// numbers next to a face, each at most 2^-53 of it (the part of them that scales with m sits in the half of PTM_BP_DZ the scan leaves
+// free).  Only a factor some 1e13 times narrower than the box's coordinates makes this the larger term.  An open face needs nothing.
+inline double prefilter_face_slack(double lo, double hi) {
+  const double a = std::fabs(lo) < INFINITY ? std::fabs(lo) : 0.0, b = std::fabs(hi) < INFINITY ? std::fabs(hi) : 0.0;
+  return 0x1p-50 * (a > b ? a : b);
+}
+// the kernel reads a margin as a float (four registers per lane instead of eight): the smallest normal float that is not below m
+inline float prefilter_margin_f32(double m) {
+  if (!(m > 0.0)) return m == 0.0 ? 0.0f : INFINITY;   // (a NaN: nothing settles)
+  if (m < 1.17549435e-38) return 1.17549435e-38f;
+  float f = (float)m;
+  if ((double)f < m) f = std::nextafterf(f, INFINITY);
+  return f;
+}
+
 // P(x + sigma z leaves [0, w]) for x uniform in [0, w], z standard normal: 1 - erf(u / sqrt 2) + (2 / u)(phi(0) - phi(u)), u = w / sigma
 // (for a narrow proposal 0.798 sigma / w: a half-normal's mean step out of each of the two faces)
 inline double prefilter_out_1d(double sigma, double w) {

@@ -29,7 +29,7 @@ EXPORTS = [
     "ptm_copy_llike", "ptm_copy_lprior", "ptm_llike_device_ptr", "ptm_exchange_decide", "ptm_exchange_decide_gathered", "ptm_set_shard_map", "ptm_exchange_redo_count", "ptm_exchange_redo", "ptm_exchange_finish_and_sweep", "ptm_exchange_install", "ptm_sweep_rungs", "ptm_exchange_buffer_doubles", "ptm_exchange_row_capacity", "ptm_shard_unique_id", "ptm_shard_init", "ptm_shard_step", "ptm_shard_finalize", "ptm_get_states", "ptm_batch_begin", "ptm_batch_end",
     "ptm_get_array", "ptm_get_swap_counts", "ptm_get_last_swaps", "ptm_max_swaps_per_step", "ptm_get_history", "ptm_get_history_invtemps", "ptm_set_history", "ptm_set_map", "ptm_get_map", "ptm_restore", "ptm_step_count",
     "ptm_timer_start", "ptm_timer_stop", "ptm_get_kernel_times", "ptm_calibrate", "ptm_get_counter_sums", "ptm_get_ladder_stats", "ptm_sweep_kernel_name", "ptm_step_kernel_name", "ptm_debug_eval",
-    "ptm_debug_philox", "ptm_debug_boxmuller", "ptm_debug_sqrt_scan", "ptm_debug_evaluate",
+    "ptm_debug_philox", "ptm_debug_boxmuller", "ptm_debug_sqrt_scan", "ptm_debug_boxmuller_f32_scan", "ptm_debug_evaluate",
     "ptm_dev_alloc", "ptm_dev_free", "ptm_dev_copy",
     "ptm_set_target_device", "ptm_target_device_rows", "ptm_get_best_evaluated",
     "ptm_set_proposal_adaptive", "ptm_get_proposal_adapt_state", "ptm_set_proposal_adapt_state",
@@ -174,6 +174,8 @@ def load():
     L.ptm_restore.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p, _i32p, C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_int64),
                               C.POINTER(C.c_int64)]
     L.ptm_debug_sqrt_scan.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
+    if hasattr(L, "ptm_debug_boxmuller_f32_scan"):   # (an older library, PTM_ENGINE_LIB in A/B runs, has no single-precision pre-pass)
+        L.ptm_debug_boxmuller_f32_scan.argtypes = [C.c_int, C.POINTER(C.c_double)]
     L.ptm_debug_evaluate.argtypes = [C.c_void_p, _dp, C.c_int, _i32p, _dp, _dp, _dp]
     if hasattr(L, "ptm_set_target_device"):
         L.ptm_set_target_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -241,6 +243,13 @@ def debug_sqrt_scan(device=-1):
     n = C.c_uint64()
     _chk(load().ptm_debug_sqrt_scan(device, C.byref(n)))
     return n.value
+
+
+def debug_boxmuller_f32_scan(device=-1):
+    """the box pre-pass's single-precision Box-Muller against the sweep's, over all 2^32 arguments of either half"""
+    o = (C.c_double * 8)()
+    _chk(load().ptm_debug_boxmuller_f32_scan(device, o))
+    return dict(max_dr=o[0], max_r=o[1], radius_nan=int(o[2]), max_dtrig=o[3], trig_nan=int(o[4]), dz=o[5], f32_slack=o[6])
 
 
 def _series3(series):
