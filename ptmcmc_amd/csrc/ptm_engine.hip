@@ -1588,6 +1588,37 @@ static int prefilter_flags(ptm_engine* e) {
   return PTM_OK;
 }
 
+// the box pre-pass over local rungs [rung0, rung0 + nr) of rows x, behind partition_kernel and in front of the compacted sweep
+static int launch_box_prefilter(ptm_engine* e, const double* x, int rung0, int nr, bool labelled) {
+  BoxPreF32 bf;
+  memset(&bf, 0, sizeof bf);
+  BoxPre& b = bf.b;
+  b.W = e->W; b.Nt = e->Nt; b.r0 = e->r0; b.w_off = e->cfg.walker_begin; b.rung0 = rung0; b.nrung = nr; b.labelled = labelled ? 1 : 0;
+  b.seed = e->cfg.seed; b.step = e->step;
+  b.x = x; b.ll = e->ll; b.lp = e->lp; b.beta = e->beta; b.prop_tiles = e->prop_tiles; b.box_row = e->box_row; b.ntries = e->ntries;
+  b.pidx = e->pidx; b.pcnt = e->pcnt; b.cidx = e->cidx; b.ccnt = e->ccnt; b.counts = e->pf_counts;
+  bf.margin = e->pf_margin;
+  // single precision behind a margin unless PTM_BOX_PREFILTER_EXACT asks for the sweep's own arithmetic: the same chains either way
+  struct { const void* fn; bool tables; } k = {(const void*)box_prefilter_f32_kernel, false};
+  if (sweep_env().prefilter_exact != 0) { k.fn = (const void*)box_prefilter_kernel; k.tables = true; }
+  if (!e->pf_grid) {   // a persistent grid: the blocks the device holds at once, of the kernel that is launched
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t pr;
+    const hipError_t oc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, 256, BoxPreLds(nullptr, k.tables, e->nloc).bytes);
+    if (oc != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipGetDeviceProperties(&pr, dev));
+    e->pf_grid = per_cu * (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
+    const int cap = sweep_env().prefilter_grid;   // PTM_PREFILTER_GRID: many tiles per block on a small population (tests)
+    if (cap > 0 && cap < e->pf_grid) e->pf_grid = cap;
+  }
+  const long long tiles = (long long)nr * ((e->W + 255) / 256);
+  void* args[] = {&bf};   // (BoxPre is BoxPreF32's first member: the exact kernel takes that much of it)
+  (void)hipLaunchKernel(k.fn, dim3((unsigned)(tiles < e->pf_grid ? tiles : e->pf_grid)), dim3(256), args, BoxPreLds(nullptr, k.tables, nr).bytes, e->stream);
+  HIPCHK(hipGetLastError());
+  return PTM_OK;
+}
+
 static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = true) {
   const bool labelled = e->label_step;   // (set by this step's exchange phase under the very conditions of the compacted sweep below)
   e->label_step = false;
@@ -1638,36 +1669,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
                        e->cidx, e->ccnt, labelled ? (const unsigned short*)e->rowof : nullptr, pre ? (const unsigned char*)e->pf_flag : nullptr, e->pidx, e->pcnt);
     e->compact_step = true;   // (every partial sweep of this step goes the same way: the step is counted once, at its end)
     HIPCHK(hipGetLastError());
-    if (pre) {
-      BoxPre b;
-      memset(&b, 0, sizeof b);
-      b.W = e->W; b.Nt = e->Nt; b.r0 = e->r0; b.w_off = e->cfg.walker_begin; b.rung0 = rung0; b.nrung = nr; b.labelled = labelled ? 1 : 0;
-      b.seed = e->cfg.seed; b.step = e->step;
-      b.x = p.x; b.ll = e->ll; b.lp = e->lp; b.beta = e->beta; b.prop_tiles = e->prop_tiles; b.box_row = e->box_row; b.ntries = e->ntries;
-      b.pidx = e->pidx; b.pcnt = e->pcnt; b.cidx = e->cidx; b.ccnt = e->ccnt; b.counts = e->pf_counts;
-      // single precision behind a margin unless PTM_BOX_PREFILTER_EXACT asks for the sweep's own arithmetic: the same chains either way
-      const bool exact = sweep_env().prefilter_exact != 0;
-      BoxPreF32 bf;
-      bf.b = b; bf.margin = e->pf_margin;
-      const size_t lds = exact ? BoxPreLds(nullptr, nr).bytes : BoxPreF32Lds(nullptr, nr).bytes;
-      if (!e->pf_grid) {   // a persistent grid: the blocks the device holds at once, of the kernel that is launched
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t pr;
-        const hipError_t oc = exact ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_kernel, 256, BoxPreLds(nullptr, e->nloc).bytes)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)box_prefilter_f32_kernel, 256, BoxPreF32Lds(nullptr, e->nloc).bytes);
-        if (oc != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); per_cu = 2; }
-        HIPCHK(hipGetDevice(&dev));
-        HIPCHK(hipGetDeviceProperties(&pr, dev));
-        e->pf_grid = per_cu * (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
-        const int cap = sweep_env().prefilter_grid;   // PTM_PREFILTER_GRID: many tiles per block on a small population (tests)
-        if (cap > 0 && cap < e->pf_grid) e->pf_grid = cap;
-      }
-      const long long tiles = (long long)nr * ((e->W + 255) / 256);
-      const dim3 grid((unsigned)(tiles < e->pf_grid ? tiles : e->pf_grid));
-      if (exact) hipLaunchKernelGGL(box_prefilter_kernel, grid, dim3(256), lds, e->stream, b);
-      else hipLaunchKernelGGL(box_prefilter_f32_kernel, grid, dim3(256), lds, e->stream, bf);
-      HIPCHK(hipGetLastError());
-    }
+    if (pre) { int rc = launch_box_prefilter(e, p.x, rung0, nr, labelled); if (rc) return rc; }
     p.cidx = e->cidx; p.ccnt = e->ccnt; p.cidx_slot = labelled ? 1 : 0;
   }
   // the timed bracket holds the sweep kernel alone (its name: ptm_sweep_kernel_name): the list fill and partition_kernel of a

@@ -43,6 +43,34 @@ typedef const int __attribute__((address_space(4))) * cip;
 __device__ __forceinline__ cdp as_c(const double* p) { return (cdp)(uintptr_t)p; }
 __device__ __forceinline__ cip as_c(const int* p) { return (cip)(uintptr_t)p; }
 
+// The tile prefix of a compacted launch (the compacted 32-D sweep, the box pre-pass): inclusive scan of ceil(cnt[rung0 + r] / 256) over the
+// launch's nrung rungs r into tpre (LDS).  Each of the block's 256 threads sums a contiguous chunk, one thread scans the chunk totals in
+// tsum ([TILE_SCAN_INTS], LDS).  Returns the number of tiles.  KEEP: the counts stay in LDS too, in pcn.  Every thread of the block calls it.
+template <bool KEEP>
+__device__ __forceinline__ int tile_prefix_scan(const int* cnt, int rung0, int nrung, int* tpre, int* tsum, int* pcn = nullptr) {
+  const int per = (nrung + 255) / 256;
+  int loc = 0;
+  for (int k = 0; k < per; ++k) {
+    const int r = threadIdx.x * per + k;
+    if (r < nrung) {
+      const int n = cnt[rung0 + r];
+      if (KEEP) pcn[r] = n;
+      loc += (n + 255) >> 8; tpre[r] = loc;
+    }
+  }
+  tsum[threadIdx.x] = loc;
+  __syncthreads();
+  if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = tsum[t]; tsum[t] = run; run += v; } tsum[256] = run; }
+  __syncthreads();
+  const int off = tsum[threadIdx.x];
+  for (int k = 0; k < per; ++k) {
+    const int r = threadIdx.x * per + k;
+    if (r < nrung) tpre[r] += off;
+  }
+  __syncthreads();
+  return tsum[256];
+}
+
 // problem description + state pointers; passed BY VALUE to every kernel (kernarg segment => scalar loads)
 // Optional history of the first `rungs` local rungs -- what MH_chain::add_state pushes every add_every_N-th call
 // (chain.cc:935-946: state, llike, lpost, acceptance ratio, type).  A ring of `cap` rows per chain: saved row s of chain

@@ -204,17 +204,18 @@ struct Mfma32Lds {
   PTM_LDS_FN Mfma32Lds(void* base, bool gen, bool compacted, int nrung) { LdsCarve c(base); carve(c, gen, compacted, nrung); }
 };
 
-// ---- box_prefilter_kernel (ptm_box_prefilter.hpp): a launch over nrung rungs
+// ---- box_prefilter_kernel / box_prefilter_f32_kernel (ptm_box_prefilter.hpp): a launch over nrung rungs; tables: the pass draws from
+// the Box-Muller tables (the double-precision one)
 struct BoxPreLds {
-  double* bm;     // Box-Muller tables
+  double* bm = nullptr;   // Box-Muller tables
   double* lbox;   // [64] prior box
   int* tpre;      // [nrung] inclusive prefix of the rungs' 256-walker tiles
   int* pcn;       // [nrung] the rungs' list lengths
   int* tsum;      // [257]
   size_t bytes;
   template <class C>
-  PTM_LDS_FN void carve(C& c, int nrung) {
-    c.take(bm, "bm", BM_TABLE_DOUBLES);
+  PTM_LDS_FN void carve(C& c, bool tables, int nrung) {
+    if (tables) c.take(bm, "bm", BM_TABLE_DOUBLES);
     c.take(lbox, "lbox", 64);
     c.take(tpre, "tpre", nrung);
     c.take(pcn, "pcn", nrung);
@@ -223,27 +224,7 @@ struct BoxPreLds {
     bytes = c.size();
   }
   BoxPreLds() = default;
-  PTM_LDS_FN BoxPreLds(void* base, int nrung) { LdsCarve c(base); carve(c, nrung); }
-};
-
-// ---- box_prefilter_f32_kernel (ptm_box_prefilter.hpp): the same launch, drawing without tables
-struct BoxPreF32Lds {
-  double* lbox;   // [64] prior box
-  int* tpre;      // [nrung] inclusive prefix of the rungs' 256-walker tiles
-  int* pcn;       // [nrung] the rungs' list lengths
-  int* tsum;      // [257]
-  size_t bytes;
-  template <class C>
-  PTM_LDS_FN void carve(C& c, int nrung) {
-    c.take(lbox, "lbox", 64);
-    c.take(tpre, "tpre", nrung);
-    c.take(pcn, "pcn", nrung);
-    c.take(tsum, "tsum", TILE_SCAN_INTS);
-    c.slack("slack", TILE_SCAN_SLACK);
-    bytes = c.size();
-  }
-  BoxPreF32Lds() = default;
-  PTM_LDS_FN BoxPreF32Lds(void* base, int nrung) { LdsCarve c(base); carve(c, nrung); }
+  PTM_LDS_FN BoxPreLds(void* base, bool tables, int nrung) { LdsCarve c(base); carve(c, tables, nrung); }
 };
 
 // ---- sweep_kernel (ptm_kernels.hpp): the 20 KB of Box-Muller tables every variant stages; the builds whose waves share a rung and

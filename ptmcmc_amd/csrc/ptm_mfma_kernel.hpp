@@ -249,26 +249,7 @@ __device__ __forceinline__ void mfma32_body(const Dev p) {   // (by value, as a 
   // CPT: the launch's rungs, their listed-walker counts as an inclusive prefix of 256-walker tiles (LDS, after everything else)
   const int rung0 = p.c_begin / p.W;
   int ntiles = (p.c_end - p.c_begin + 255) >> 8;   // 256-chain tiles of this launch (ranges are multiples of 64)
-  if constexpr (CPT) {
-    // inclusive scan of ceil(count / 256) over the rungs: each thread sums a contiguous chunk, one wave scans the chunk totals
-    const int per = (nrung + 255) / 256;
-    int loc = 0;
-    for (int k = 0; k < per; ++k) {
-      const int r = threadIdx.x * per + k;
-      if (r < nrung) { loc += (p.ccnt[rung0 + r] + 255) >> 8; L.tpre[r] = loc; }
-    }
-    L.tsum[threadIdx.x] = loc;
-    __syncthreads();
-    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < 256; ++t) { const int v = L.tsum[t]; L.tsum[t] = run; run += v; } L.tsum[256] = run; }
-    __syncthreads();
-    const int off = L.tsum[threadIdx.x];
-    for (int k = 0; k < per; ++k) {
-      const int r = threadIdx.x * per + k;
-      if (r < nrung) L.tpre[r] += off;
-    }
-    __syncthreads();
-    ntiles = L.tsum[256];
-  }
+  if constexpr (CPT) ntiles = tile_prefix_scan<false>(p.ccnt, rung0, nrung, L.tpre, L.tsum);
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
   int c0, rl, w0, nact = 64, lbase = 0;
   bool live = true;

@@ -132,7 +132,11 @@ int main() {
     for (int cpt = 0; cpt < 2; ++cpt)
       for (int nrung : {1, 7, 564, 1024})
         layout_row<Mfma32Lds>(fmt("mfma32 mgen=%d compacted=%d nrung=%d", mgen, cpt, nrung), mgen != 0, cpt != 0, nrung);
-  for (int nrung : {1, 7, 564, 1024}) layout_row<BoxPreLds>(fmt("prepass nrung=%d", nrung), nrung);
+  for (int nrung : {1, 7, 564, 1024}) {
+    const size_t with = layout_row<BoxPreLds>(fmt("prepass nrung=%d", nrung), true, nrung).bytes;
+    const size_t without = layout_row<BoxPreLds>(fmt("prepass tables=0 nrung=%d", nrung), false, nrung).bytes;
+    if (with - without != BM_TABLE_DOUBLES * sizeof(double)) broken(fmt("prepass nrung=%d", nrung), "the table-free layout is not the tables smaller", "bm");
+  }
   general_rows<4>(); general_rows<8>(); general_rows<16>(); general_rows<32>();
   layout_row<Mfma64Lds>("mfma64");
   layout_row<Mfma128Lds>("mfma128");
