@@ -540,6 +540,34 @@ int ptm_ess_last_on_device(ptm_engine* e);
 int ptm_log_evidence(ptm_engine* e, int ilen, double* log_evidence /*[W]*/, double* up /*[(Nt-1)*W] or NULL*/,
                      double* down /*[(Nt-1)*W] or NULL*/, int32_t* count /*[Nt*W] or NULL*/);
 
+/* ---- split R-hat across the walkers of a rung on the device ----------------------------------------------------------------
+ * The Gelman-Rubin diagnostic on split chains: do the W independent replicas of one rung agree with each other?  As the facade's
+ * rhat_estimator states it (ptmcmc_amd/host/ptmcmc_gpu.hh), on the saved rows of the history ring where they lie.  The reference
+ * runs one ladder: no reference counterpart.
+ *  - The first nfeat parameters are the features; nrows (even, >= 4) saved rows per chain are looked at.
+ *  - Walker w's window is its own newest nrows saved rows: newest_w = 1 + (Nhist_w - 1) / add_every_n (PTM_ARR_NHIST: the row the
+ *    effective-sample-size calls assign to nominal step Nhist - 1, the exclusive end of the evidence window), rows
+ *    newest_w - nrows + 1 .. newest_w in ascending order.  Row 0, the start state, is never part of it.  The walkers of a rung may
+ *    differ in Nhist; each uses its own window, all of one length.
+ *  - The window's first and second half, n = nrows / 2 rows each, are sequences 2w and 2w + 1: m = 2W sequences.
+ *  - Per sequence k and feature f, sequentially in row order: mean_k = (sum x) / n; then, in a second walk over the same rows,
+ *    var_k = (sum (x - mean_k) * (x - mean_k)) / (n - 1).
+ *  - Per feature, sequentially over k = 0 .. m - 1: M = (sum mean_k) / m; between = n * (sum (mean_k - M)^2) / (m - 1);
+ *    within = (sum var_k) / m; var_plus = ((n - 1) / n) * within + between / n; rhat = sqrt(var_plus / within).
+ * Operations run as written (multiply, then add; no contraction), so the answers carry the host estimator's bits.  A constant
+ * feature gives the formula's IEEE result (NaN or infinity): nothing is special-cased.
+ * Outputs: rhat[nfeat]; mean (M), within, between [nfeat] or NULL; seq_mean, seq_var [(2*W)*nfeat] ([k*nfeat + f]) or NULL -- with
+ * them a caller can pool walker splits that run as separate engines.
+ * ptm_rhat runs on the engine's stream and waits for it.  ptm_rhat_series is the same on a caller's series, host array
+ * series[(t*nseries + s)*nfeat + f], t < n, with nseries in place of W and the newest nrows of the n rows as every window: no engine needed.
+ * PTM_ERR_INVALID: a null engine or rhat, no history ring, rung >= history_rungs, nfeat < 1 or > dim, nrows odd or < 4, a chain with
+ * fewer than nrows saved rows behind the start state, or a window row the ring no longer holds ("history_capacity must hold the
+ * window": the outputs are left untouched).  PTM_ERR_UNSUPPORTED: a chain of the rung has made more than 2e9 add_state calls. */
+int ptm_rhat(ptm_engine* e, int rung, int nfeat, int nrows, double* rhat /*[nfeat]*/, double* mean, double* within, double* between /*[nfeat] or NULL*/,
+             double* seq_mean, double* seq_var /*[2*W*nfeat] or NULL*/);
+int ptm_rhat_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* rhat /*[nfeat]*/, double* mean, double* within,
+                    double* between /*[nfeat] or NULL*/, double* seq_mean, double* seq_var /*[2*nseries*nfeat] or NULL*/);
+
 /* ---- verification hooks (used by tests/ only; evaluate device functions on arrays) ---------------------- */
 enum { PTM_FN_LOG = 0, PTM_FN_EXP = 1, PTM_FN_SIN_0_PI = 2, PTM_FN_COS_HPI = 3, PTM_FN_SQRT = 4, PTM_FN_DIV = 5,
        PTM_FN_SQRT_RAW = 6 };

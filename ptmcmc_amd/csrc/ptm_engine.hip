@@ -25,6 +25,7 @@
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
 #include "ptm_launch.hpp"
+#include "ptm_rhat_kernels.hpp"
 #include "ptm_shard_rccl.hpp"
 
 using namespace ptm;
@@ -3627,6 +3628,87 @@ extern "C" int ptm_log_evidence(ptm_engine* e, int ilen, double* log_evidence, d
   if (count) HIPCHK(hipMemcpyAsync(count, d_cnt, Nc * 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return PTM_OK;
+}
+
+// ---- split R-hat across the walkers of a rung on the device (ptm_rhat_kernels.hpp) ------------------------------------------
+// rhat_estimator (ptmcmc_amd/host/ptmcmc_gpu.hh) on the ring where it lies, or on a caller's series.  The kernels write into the
+// workspace; the caller's arrays are filled only when no row of a window was missing.  d_nhist: the chains' own counts of add_state
+// calls on the device (null: src.steps for all); wrapped: a slot may have been written twice.
+static int rhat_run(hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat, int nrows,
+                    double* rhat, double* mean, double* within, double* between, double* seq_mean, double* seq_var) {
+  const size_t lanes = (size_t)2 * W * nfeat;
+  const size_t o_mean = 0, o_var = o_mean + ess_align(lanes * 8), o_out = o_var + ess_align(lanes * 8), o_flag = o_out + ess_align((size_t)4 * nfeat * 8),
+               total = o_flag + 256;
+  if (*ws_bytes < total) {
+    if (*ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
+    HIPCHK(hipMalloc(ws, total));
+    *ws_bytes = total;
+  }
+  unsigned char* b = (unsigned char*)*ws;
+  double *d_mean = (double*)(b + o_mean), *d_var = (double*)(b + o_var), *d_out = (double*)(b + o_out);
+  int* d_flag = (int*)(b + o_flag);
+  HIPCHK(hipMemsetAsync(d_flag, 0, 4, st));
+  const dim3 grid((unsigned)((lanes + RHAT_THREADS - 1) / RHAT_THREADS));
+  if (wrapped) hipLaunchKernelGGL(rhat_sequence_kernel<true>, grid, dim3(RHAT_THREADS), 0, st, src, d_nhist, W, nfeat, nrows, d_mean, d_var, d_flag);
+  else hipLaunchKernelGGL(rhat_sequence_kernel<false>, grid, dim3(RHAT_THREADS), 0, st, src, d_nhist, W, nfeat, nrows, d_mean, d_var, d_flag);
+  HIPCHK(hipGetLastError());
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (flag) return fail(PTM_ERR_INVALID, "ptm_rhat: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", src.cap, nrows);
+  hipLaunchKernelGGL(rhat_reduce_kernel, dim3((unsigned)((nfeat + RHAT_THREADS - 1) / RHAT_THREADS)), dim3(RHAT_THREADS), 0, st, 2 * W, nfeat, nrows / 2, d_mean, d_var, d_out);
+  HIPCHK(hipGetLastError());
+  std::vector<double> out((size_t)4 * nfeat);
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost, st));
+  if (seq_mean) HIPCHK(hipMemcpyAsync(seq_mean, d_mean, lanes * 8, hipMemcpyDeviceToHost, st));
+  if (seq_var) HIPCHK(hipMemcpyAsync(seq_var, d_var, lanes * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int f = 0; f < nfeat; ++f) {
+    const size_t F = (size_t)f, N = (size_t)nfeat;
+    if (mean) mean[f] = out[F];
+    if (within) within[f] = out[N + F];
+    if (between) between[f] = out[2 * N + F];
+    rhat[f] = std::sqrt(out[3 * N + F] / out[N + F]);   // (the host's IEEE division and square root)
+  }
+  return PTM_OK;
+}
+static int rhat_shape(const char* who, int nfeat_max, int nfeat, int nrows) {
+  if (nfeat < 1 || nfeat > nfeat_max) return fail(PTM_ERR_INVALID, "%s: nfeat must be in 1..%d", who, nfeat_max);
+  if (nrows < 4 || (nrows & 1)) return fail(PTM_ERR_INVALID, "%s: nrows must be even and at least 4", who);
+  return PTM_OK;
+}
+extern "C" int ptm_rhat(ptm_engine* e, int rung, int nfeat, int nrows, double* rhat, double* mean, double* within, double* between, double* seq_mean,
+                        double* seq_var) {
+  if (!e || !rhat) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_rhat");
+  int rc = rhat_shape("ptm_rhat", e->D, nfeat, nrows);
+  if (rc) return rc;
+  EssSrc src;
+  std::vector<int> steps_of;
+  if ((rc = ess_ring_source(e, rung, nfeat, &src, &steps_of))) return rc;   // (settles a pending ladder launch and the uncounted adds first)
+  if ((double)2 * e->W * nfeat > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_rhat: bad shape");
+  long long newest_min = 0, newest_max = 0;
+  for (int w = 0; w < e->W; ++w) {
+    const long long st = steps_of.empty() ? src.steps : steps_of[(size_t)w];
+    const long long newest = st > 0 ? 1 + (st - 1) / src.add_every : 0;   // (= the saved rows behind the start state)
+    if (!w || newest < newest_min) newest_min = newest;
+    if (!w || newest > newest_max) newest_max = newest;
+  }
+  if (newest_min < nrows) return fail(PTM_ERR_INVALID, "ptm_rhat: a chain of the rung has saved %lld rows behind its start state, fewer than nrows (%d)", newest_min, nrows);
+  if (nrows > src.cap) return fail(PTM_ERR_INVALID, "ptm_rhat: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", src.cap, nrows);
+  return rhat_run(e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->nhist + (size_t)rung * e->W, newest_max >= (long long)src.cap, e->W, nfeat, nrows, rhat, mean, within,
+                  between, seq_mean, seq_var);
+}
+extern "C" int ptm_rhat_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* rhat, double* mean, double* within,
+                               double* between, double* seq_mean, double* seq_var) {
+  if (!rhat) return fail(PTM_ERR_INVALID, "null argument");
+  int rc = rhat_shape("ptm_rhat_series", 2000000000, nfeat, nrows);
+  if (rc) return rc;
+  if ((int64_t)nrows > n) return fail(PTM_ERR_INVALID, "ptm_rhat_series: the series have %lld rows, fewer than nrows (%d)", (long long)n, nrows);
+  if (nseries >= 1 && (double)2 * nseries * nfeat > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_rhat_series: bad shape");
+  EssSeries S;
+  if ((rc = ess_series_source(&S, device, series, n, nseries, nfeat))) return rc;
+  return rhat_run(nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, rhat, mean, within, between, seq_mean, seq_var);
 }
 
 // ---- verification hooks ------------------------------------------------------------------------------------------------

@@ -35,6 +35,7 @@ EXPORTS = [
     "ptm_set_proposal_adaptive", "ptm_get_proposal_adapt_state", "ptm_set_proposal_adapt_state",
     "ptm_ess_windowed", "ptm_ess_report", "ptm_ess_series_windowed", "ptm_ess_series_report", "ptm_ess_last_on_device",
     "ptm_log_evidence",
+    "ptm_rhat", "ptm_rhat_series",
     "ptm_get_prefilter_counts",
 ]
 
@@ -193,6 +194,9 @@ def load():
         L.ptm_ess_last_on_device.argtypes = [C.c_void_p]
     if hasattr(L, "ptm_log_evidence"):
         L.ptm_log_evidence.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _i32p]
+    if hasattr(L, "ptm_rhat"):
+        L.ptm_rhat.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.ptm_rhat_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
     _lib = L
     return L
 
@@ -279,6 +283,28 @@ def effective_samples_series(series, width, every, esslimit=-1, device=-1):
     return ess, length
 
 
+def _rhat_outputs(m, nfeat, sequences, out):
+    """(rhat, mean, within, between[, seq_mean, seq_var]) to fill: the caller's `out` or new arrays"""
+    if out is not None:
+        return tuple(out)
+    o = tuple(np.empty(nfeat) for _ in range(4))
+    return o + (np.empty((m, nfeat)), np.empty((m, nfeat))) if sequences else o
+
+
+def rhat_series(series, nrows=None, sequences=False, out=None, device=-1):
+    """split R-hat across series [n, nseries, nfeat] on the device, over the newest `nrows` rows (None: the largest even count) of
+    every series: (rhat, mean, within, between)[nfeat]; sequences=True adds (seq_mean, seq_var)[2 nseries, nfeat], the halves of
+    series s being sequences 2s and 2s + 1 (ptm_rhat_series).  out: arrays to fill instead (they keep their contents when the call fails)."""
+    a = _series3(series)
+    n, ns, nf = a.shape
+    if nrows is None:
+        nrows = n - n % 2
+    o = _rhat_outputs(2 * ns, nf, sequences, out)
+    p = [_d(v) for v in o] + [None] * (6 - len(o))
+    _chk(load().ptm_rhat_series(device, _d(a), n, ns, nf, int(nrows), *p))
+    return o
+
+
 class DeviceBuffer:
     """A raw device allocation (for tests and tools that have no GPU array library at hand)."""
 
@@ -357,6 +383,7 @@ class Engine:
         cfg.exchange_row_capacity = exchange_row_capacity
         cfg.history_rungs, cfg.history_capacity = history_rungs, history_capacity
         self.hist_rungs, self.hist_cap = history_rungs, history_capacity
+        self.add_every_n = add_every_n
         cfg.map_rungs = map_rungs
         self.map_rungs = map_rungs
         cfg.walker_begin = walker_begin
@@ -770,6 +797,24 @@ class Engine:
         ev, up, down, count = out
         _chk(self.L.ptm_log_evidence(self.h, int(ilen), _d(ev), _d(up), _d(down), count.ctypes.data_as(_i32p)))
         return ev, up, down, count
+
+    def split_rhat(self, rung=0, nfeat=None, nrows=None, sequences=False, out=None):
+        """split R-hat across the walkers of local rung `rung`, from the history ring, on the device: every walker's newest `nrows`
+        saved rows (even, >= 4; None: the largest even window every walker of the rung still has), their halves the 2 W sequences:
+        (rhat, mean, within, between)[nfeat]; sequences=True adds (seq_mean, seq_var)[2 W, nfeat] (ptm_rhat).  out: arrays to fill
+        instead (they keep their contents when the call fails)."""
+        nf = self.D if nfeat is None else int(nfeat)
+        if nrows is None:
+            if not (0 <= int(rung) < self.hist_rungs):
+                raise PtmError("rung %d keeps no history (history_rungs = %d)" % (rung, self.hist_rungs))
+            nh = self.nhist.reshape(self.nloc, self.W)[int(rung)].astype(np.int64)
+            newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
+            have = min(int(newest.min()), self.hist_cap)                       # (a wrapped ring holds its newest `capacity` rows)
+            nrows = have - have % 2
+        o = _rhat_outputs(2 * self.W, max(nf, 0), sequences, out)
+        p = [_d(v) for v in o] + [None] * (6 - len(o))
+        _chk(self.L.ptm_rhat(self.h, int(rung), nf, int(nrows), *p))
+        return o
 
     @property
     def exchange_row_capacity(self):

@@ -1748,6 +1748,93 @@ class evidence_estimator {
   }
 };
 
+// ---- split R-hat across independent chains ----------------------------------------------------------------------------------------
+// rhat_estimator: do W independent replicas of one chain agree with each other?  The Gelman-Rubin diagnostic on split chains (Gelman
+// et al., "Bayesian Data Analysis", 3rd ed., sec. 11.4), on plain rows.  The reference runs one ladder and has no counterpart.
+//   * chain w's window is its own newest nrows saved rows (nrows even, >= 4), newest_w = 1 + (Nhist_w - 1) / add_every_N in the ring's
+//     numbering (row 0 the start state, never part of a window): rows newest_w - nrows + 1 .. newest_w in ascending order;
+//   * its first and second half, n = nrows / 2 rows each, are sequences 2w and 2w + 1: m = 2W sequences;
+//   * per sequence k and feature, in row order: mean_k = (sum x) / n, then in a second walk over the same rows
+//     var_k = (sum (x - mean_k) * (x - mean_k)) / (n - 1)  (two passes: a series far from zero loses nothing);
+//   * per feature, over k = 0 .. m - 1 in order: M = (sum mean_k) / m, between = n * (sum (mean_k - M)^2) / (m - 1),
+//     within = (sum var_k) / m, var_plus = ((n - 1) / n) * within + between / n, rhat = sqrt(var_plus / within).
+// A constant feature gives the formula's IEEE result (NaN or infinity).  The engine's kernels run the same operations in the same
+// order on the device's own ring (ptm_rhat): same bits.
+class rhat_estimator {
+ public:
+  // the features of saved row `row` (the ring's numbering) of chain `chain`; false: the row is not there any more
+  typedef std::function<bool(int chain, long long row, std::vector<double>& features)> reader;
+  struct result {
+    std::vector<double> rhat, mean, within, between;   // [nfeat]
+    std::vector<double> seq_mean, seq_var;             // [2W * nfeat]: sequence k, feature f at k * nfeat + f
+    bool complete;                                     // false: a row of a window was missing (nothing else is to be believed then)
+    int worst() const {                                // the feature that decides: the first NaN if there is one, else the largest rhat
+      int at = 0;
+      for (size_t f = 0; f < rhat.size(); f++) {
+        if (rhat[f] != rhat[f]) return (int)f;
+        if (rhat[f] > rhat[(size_t)at]) at = (int)f;
+      }
+      return at;
+    }
+  };
+  static long long newest_row(long long Nhist, int add_every_N, int first_row = 1) { return first_row + (Nhist - 1) / add_every_N; }
+  // the second half of the definition, from the sequences' means and variances (r.seq_mean, r.seq_var)
+  static void combine(result& r, int m, int nfeat, int n) {
+    const double nd = (double)n, md = (double)m;
+    r.rhat.assign((size_t)nfeat, 0.0); r.mean = r.rhat; r.within = r.rhat; r.between = r.rhat;
+    for (int f = 0; f < nfeat; f++) {
+      double msum = 0;
+      for (int k = 0; k < m; k++) msum += r.seq_mean[(size_t)k * nfeat + f];
+      const double M = msum / md;
+      double bsum = 0, wsum = 0;
+      for (int k = 0; k < m; k++) {
+        const double d = r.seq_mean[(size_t)k * nfeat + f] - M;
+        volatile double dd = d * d;   // (the product rounded before the sum, whatever the compiler's contraction rule)
+        bsum += dd;
+      }
+      for (int k = 0; k < m; k++) wsum += r.seq_var[(size_t)k * nfeat + f];
+      volatile double nb = nd * bsum;
+      const double between = nb / (md - 1.0), within = wsum / md;
+      volatile double scaled = ((nd - 1.0) / nd) * within;
+      const double var_plus = scaled + between / nd;
+      r.mean[(size_t)f] = M; r.within[(size_t)f] = within; r.between[(size_t)f] = between;
+      r.rhat[(size_t)f] = std::sqrt(var_plus / within);
+    }
+  }
+  // W chains; newest[W]: each chain's newest saved row
+  static result estimate(int W, int nfeat, int nrows, const long long* newest, const reader& read) {
+    result r;
+    const int n = nrows / 2, m = 2 * W;
+    r.complete = true;
+    r.seq_mean.assign((size_t)m * nfeat, 0.0); r.seq_var = r.seq_mean;
+    std::vector<double> rows((size_t)nrows * nfeat), v;
+    for (int w = 0; w < W; w++) {
+      for (int i = 0; i < nrows; i++) {
+        if (!read(w, newest[w] - nrows + 1 + i, v) || (int)v.size() < nfeat) { r.complete = false; v.assign((size_t)nfeat, 0.0); }
+        for (int f = 0; f < nfeat; f++) rows[(size_t)i * nfeat + f] = v[(size_t)f];
+      }
+      for (int half = 0; half < 2; half++)
+        for (int f = 0; f < nfeat; f++) {
+          const double* x = rows.data() + (size_t)half * n * nfeat + f;
+          double sum = 0;
+          for (int i = 0; i < n; i++) sum += x[(size_t)i * nfeat];
+          const double mean = sum / (double)n;
+          double ssq = 0;
+          for (int i = 0; i < n; i++) {
+            const double d = x[(size_t)i * nfeat] - mean;
+            volatile double dd = d * d;
+            ssq += dd;
+          }
+          const size_t o = (size_t)(2 * w + half) * nfeat + f;
+          r.seq_mean[o] = mean;
+          r.seq_var[o] = ssq / (double)(n - 1);
+        }
+    }
+    combine(r, m, nfeat, n);
+    return r;
+  }
+};
+
 // evidence_records: what the statistics block keeps of the totals (chain.cc:1603-1675) -- the pyramid total_evidence_records (level 0
 // every total from the second epoch on; level i the average of the last two of level i-1 whenever evidence_count is a multiple of
 // 2^i), the "recent ev analysis" over the newest 2 (Ndim - j) + 1 entries of each level but the top one, and the smallest standard
@@ -3257,6 +3344,76 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
   bool ess_dev_last = false;
   bool ess_ran_on_device() const { return ess_dev_last; }   // the last estimate of this ladder launched the device's kernels
+  // ---- split R-hat across the replicas of rung `rung` (rhat_estimator above; no reference counterpart: it runs one ladder): every
+  // replica's newest `nrows` saved rows (even, >= 4), the first `nfeat` parameters.  The device estimates from its own ring (ptm_rhat:
+  // the host estimator's bits) when the ring is there; with host-side proposals (the history is the host mirror) and with
+  // PTM_HOST_RHAT=1 the estimate is made here.
+  bool rhat_on_device_possible() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_RHAT"); return v && *v && *v != '0'; }();   // (A/B: keep the host path)
+    return !(off || host_mode || hist_rows <= 0);
+  }
+  // the saved rows behind the start state that every replica of the rung has, and the ring still holds
+  int rhat_rows_available(int rung = 0) {
+    std::vector<int64_t> nh((size_t)Ntemps * W);
+    ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "split_rhat");
+    long long have = -1;
+    for (int w = 0; w < W; w++) {
+      const long long st = nh[(size_t)rung * W + w], newest = st > 0 ? rhat_estimator::newest_row(st, add_every_N) : 0;
+      if (have < 0 || newest < have) have = newest;
+    }
+    if (!host_mode && have > hist_rows) have = hist_rows;
+    return (int)have;
+  }
+  rhat_estimator::result split_rhat(int rung = 0, int nfeat = -1, int nrows = -1) {
+    if (nfeat < 0 || nfeat > dim) nfeat = dim;
+    if (nrows < 0) { nrows = rhat_rows_available(rung); nrows -= nrows % 2; }
+    rhat_dev_last = false;
+    rhat_estimator::result r;
+    if (rhat_on_device_possible()) {
+      const size_t nf = (size_t)(nfeat > 0 ? nfeat : 0), ns = 2 * (size_t)W * nf;
+      r.rhat.assign(nf, 0.0); r.mean = r.rhat; r.within = r.rhat; r.between = r.rhat;
+      r.seq_mean.assign(ns, 0.0); r.seq_var = r.seq_mean;
+      ptm_check(ptm_rhat(eng, rung, nfeat, nrows, r.rhat.data(), r.mean.data(), r.within.data(), r.between.data(), r.seq_mean.data(), r.seq_var.data()), "split_rhat");
+      r.complete = true;
+      rhat_dev_last = true;
+      return r;
+    }
+    if (rung < 0 || rung >= (host_mode ? Ntemps : history_rungs()) || nfeat < 1 || nrows < 4 || nrows % 2) {
+      std::cout << "parallel_tempering_chains::split_rhat: rung " << rung << ", nfeat " << nfeat << ", nrows " << nrows << " (a recorded rung, 1..dim, even and >= 4)" << std::endl;
+      exit(1);
+    }
+    std::vector<int64_t> nh((size_t)Ntemps * W);
+    ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "split_rhat");
+    std::vector<long long> newest((size_t)W);
+    for (int w = 0; w < W; w++) {
+      const long long st = nh[(size_t)rung * W + w];
+      newest[(size_t)w] = st > 0 ? rhat_estimator::newest_row(st, add_every_N) : 0;
+      if (newest[(size_t)w] < nrows) { std::cout << "parallel_tempering_chains::split_rhat: replica " << w << " has saved " << newest[(size_t)w] << " rows behind its start state, fewer than nrows (" << nrows << ")" << std::endl; exit(1); }
+    }
+    rhat_estimator::reader read;
+    if (host_mode) read = [this, rung](int w, long long row, std::vector<double>& v) {   // (the mirror counts its initial draws in front)
+      const mirror_t& m = mirror[(size_t)rung * W + w];
+      const long long at = row - 1 + Ninit_rows;
+      if (row < 1 || (size_t)at >= m.rows()) return false;
+      v.assign(m.x.begin() + (size_t)at * dim, m.x.begin() + ((size_t)at + 1) * dim);
+      return true;
+    };
+    else {
+      read_history((size_t)rung * W + W - 1, "split_rhat");
+      read = [this, rung](int w, long long row, std::vector<double>& v) {
+        const size_t HC = (size_t)history_rungs() * W, cap = hist_rows;
+        const size_t o = (size_t)(row % (long long)cap) * HC + (size_t)rung * W + w;
+        if (row < 1 || hmeta[4 * o + 3] != (int32_t)row) return false;
+        v.assign(hx.begin() + o * dim, hx.begin() + (o + 1) * dim);
+        return true;
+      };
+    }
+    r = rhat_estimator::estimate(W, nfeat, nrows, newest.data(), read);
+    if (!r.complete) { std::cout << "parallel_tempering_chains::split_rhat: the saved history no longer holds the window (" << nrows << " rows)" << std::endl; exit(1); }
+    return r;
+  }
+  bool rhat_dev_last = false;
+  bool rhat_ran_on_device() const { return rhat_dev_last; }   // the last split_rhat of this ladder ran the device's kernels
   // swap_count / swap_accept_count (chain.hh:244-245)
   void swap_counts(std::vector<int64_t>& tries, std::vector<int64_t>& accepts) {
     std::vector<int64_t> t((size_t)W * (Ntemps > 1 ? Ntemps - 1 : 1)), a(t.size());
@@ -3346,7 +3503,7 @@ class ptmcmc_sampler : public bayes_sampler {
   bool restarting;
   std::string restart_dir;
   int checkp_at_step;
-  double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0;
+  double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0, rhat_stop = -1;
   int nreplicas, replica_begin = 0, device = -1;
 
   // every flag read into a typed value (a flag without a value reads as T())
@@ -3374,6 +3531,7 @@ class ptmcmc_sampler : public bayes_sampler {
     if (Nptc == 0) dump_n = 1;
     prop_adapt_rate = flag<double>("prop_adapt_rate");
     ess_stop = flag<double>("chain_ess_stop");
+    rhat_stop = flag<double>("chain_rhat_stop");
     pt_stop_evid_err = flag<double>("pt_stop_evid_err");
     dpriormin = flag<double>("chain_dprior_min");
     nreplicas = optSet("replicas") ? flag<int>("replicas") : 1;
@@ -3463,6 +3621,7 @@ class ptmcmc_sampler : public bayes_sampler {
         {"replicas", "1", "Independent replicas of the ladder run side by side on the device (files <base>_c<w>_t<k>.dat). [1]"},
         {"replica_begin", "0", "Global index of this process's first replica (one process per GPU, disjoint ranges). [0]"},
         {"device", "-1", "GPU of this process. [-1: the current device, e.g. by HIP_VISIBLE_DEVICES]"},
+        {"chain_rhat_stop", "-1.0", "Stop as soon as the split R-hat of the cold chains across the replicas, the largest over the parameters, is below this. [-1: never]"},
     };
     for (size_t i = 0; i < sizeof flags / sizeof flags[0]; i++) addOption(flags[i].name, flags[i].about, flags[i].preset);
   }
@@ -3705,7 +3864,7 @@ class ptmcmc_sampler : public bayes_sampler {
       cc->keep_history((int)de_rows, Nptc);
       cc->use_device_de(true);
     } else {
-      cc->keep_history(2 + 2 * (ess_stop > 0 ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
+      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
     }
     cc->set_replica_range(replica_begin, nreplicas, device);
     if (pt_evolve_rate > 0) cc->evolve_temps(pt_evolve_rate, pt_evolve_lpost_cut);   // ptmcmc.cc:512
@@ -3786,6 +3945,22 @@ class ptmcmc_sampler : public bayes_sampler {
             if (ess_len.first > ess_stop) {
               stop = true;
               std::cout << "ptmcmc_sampler::run: Stopping based on chain_ess_stop Effective Sample Size criterion." << std::endl;
+            }
+          }
+          if (rhat_stop > 0) {   // this build's own: do the replicas' cold chains agree?  (the reference runs one ladder)
+            // the newest (1 - burn_frac) share of the saved rows every replica has, an even count
+            int nrows = (int)((1.0 - nburn_frac) * cc->rhat_rows_available(0));
+            nrows -= nrows % 2;
+            if (nrows >= 4) {
+              const rhat_estimator::result r = cc->split_rhat(0, -1, nrows);
+              const int k = r.worst();
+              char line[160];
+              snprintf(line, sizeof line, "Split R-hat over %d replicas, %d rows: max=%.17g (par %d)", nrep, nrows, r.rhat[(size_t)k], k);
+              std::cout << line << std::endl;
+              if (r.rhat[(size_t)k] < rhat_stop) {   // (a NaN is below nothing)
+                stop = true;
+                std::cout << "ptmcmc_sampler::run: Stopping based on chain_rhat_stop criterion." << std::endl;
+              }
             }
           }
         }
