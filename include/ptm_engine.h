@@ -236,8 +236,37 @@ int ptm_set_proposal_adapt_state(ptm_engine* e, const double* weights, const dou
  * every sweep fetches the current states, calls `propose` once for all moving chains, and runs the rest of
  * MH_chain::step on the device.  `result` (may be NULL) is told the outcomes after the accept kernel.  Replaces the
  * proposals of ptm_set_proposals; propose == NULL goes back to them.  Whole-shard sweeps only (ptm_sweep, ptm_step,
- * ptm_exchange_finish_and_sweep; not ptm_sweep_rungs). */
+ * ptm_exchange_finish_and_sweep; not ptm_sweep_rungs).  Clears device proposals (ptm_set_proposal_device, below): the last of the two
+ * setters called wins. */
 int ptm_set_proposal_callback(ptm_engine* e, ptm_propose_batch_fn propose, ptm_proposal_result_fn result, void* user);
+/* The same proposals ON THE DEVICE: ptm_propose_batch_fn's contract with every array in device memory and no host round trip.
+ * `propose` is called on the HOST once per sweep, in stream order; it enqueues its work on `stream` (a hipStream_t) and may return
+ * before that work has run: ptm_step(n) returns without waiting, as it does for the engine's own proposals.  n_rows is the local
+ * chain count; `step` is ptm_step_count at the sweep (a host value: the call is made when the sweep is queued).
+ * Rows [0, *count_dev) are the chains that make a Metropolis move this step (touch flag 0: rungs touched by an exchange attempt
+ * make none, chain.cc:1553-1557), in local-chain order -- the set and order ptm_propose_batch_fn is handed.  X_cur_dev
+ * [n_rows][dim] row-major, natural dimension order; rung_dev / walker_dev [n_rows] the GLOBAL rung and walker of each row.  Rows
+ * past the count hold the other chains' current states and ids, so a fixed-shape evaluation of all n_rows rows is safe; their
+ * outputs are never read.
+ * Before the call the engine presets log_hastings = 0, type = 0, valid = 1 for every row; X_prop_dev [n_rows][dim] is undefined on
+ * entry, and the function writes whole states (not offsets) for every row below the count.  The outputs mean what
+ * ptm_propose_batch_fn's mean: a NaN ratio rejects, valid = 0 is state::invalid(), type becomes last_type on acceptance.
+ * `result` (may be NULL) is called once per sweep after the accept pass has been queued, with accepted_dev[k] in {0, 1} for
+ * k < *count_dev: the rows and order of the propose call.
+ * propose == NULL goes back to the engine's own proposals.  Setting device proposals clears host-side proposals and the reverse
+ * (the last call wins); every argument is checked before anything changes.  Works with the Gaussian target, the host-callback
+ * likelihood (and a prior callback), the device likelihood (ptm_set_target_device: the step then stays on the device end to end),
+ * evolving ladders, history, MAP and populations split by walkers.  Refused (PTM_ERR_UNSUPPORTED) where host-side proposals are:
+ * ptm_sweep_rungs on part of a shard, rung-sharded steps.  While set, ptm_set_proposal_de, _prior_draw and the like answer as they
+ * do with host-side proposals, and the sweep is the lanes kernel's general build. */
+typedef void (*ptm_propose_device_fn)(void* user, void* stream, int n_rows, int dim,
+        const double* X_cur_dev,            /* [n_rows][dim] row-major, natural dimension order */
+        const int32_t* rung_dev, const int32_t* walker_dev,   /* [n_rows] GLOBAL rung / walker of each row */
+        const int32_t* count_dev, uint64_t step,
+        double* X_prop_dev, double* log_hastings_dev, int32_t* type_dev, int32_t* valid_dev);
+typedef void (*ptm_proposal_result_device_fn)(void* user, void* stream, int n_rows,
+        const int32_t* rung_dev, const int32_t* walker_dev, const int32_t* count_dev, const int32_t* accepted_dev);
+int ptm_set_proposal_device(ptm_engine* e, ptm_propose_device_fn propose, ptm_proposal_result_device_fn result, void* user);
 /* Differential evolution (ter Braak & Vrugt 2008) drawn ON THE DEVICE from each chain's own saved history -- the reference's
  * differential_evolution (proposal_distribution.cc:476-801) as the reference sampler configures it by default (ptmcmc.cc:81-91: no
  * temperature mixing, unlikely_alpha = 0).  It becomes the member of the rungs' proposal sets (ptm_set_proposal_mixture) whose SCALE

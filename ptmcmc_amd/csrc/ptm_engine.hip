@@ -22,6 +22,7 @@
 #include "ptm_count_limit.hpp"
 #include "ptm_de_mfma_kernel.hpp"
 #include "ptm_devlike_kernels.hpp"
+#include "ptm_devprop_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
 #include "ptm_launch.hpp"
@@ -125,6 +126,19 @@ struct ptm_engine {
   ptm_propose_batch_fn pcb = nullptr;
   ptm_proposal_result_fn pres = nullptr;
   void* pcb_user = nullptr;
+  // device proposals (ptm_set_proposal_device; ptm_devprop_kernels.hpp): the user's functions, and buffers that belong to this path
+  // alone (the device likelihood's pack runs later in the same step with its own count and row -> chain index).  By row: the packed
+  // current states and the proposals in natural order [Nc][D], ids, log-Hastings ratios, types, validity, outcomes, the count, the
+  // row -> chain index and the pack's chunk totals; by chain: what the sweep kernel reads under host_prop
+  ptm_propose_device_fn dpfn = nullptr;
+  ptm_proposal_result_device_fn dpres = nullptr;
+  void* dp_user = nullptr;
+  double *dp_xcur = nullptr, *dp_xnew = nullptr, *dp_hast_k = nullptr;
+  int32_t *dp_rung = nullptr, *dp_walker = nullptr, *dp_type_k = nullptr, *dp_valid_k = nullptr, *dp_acc_k = nullptr, *dp_count = nullptr;
+  int *dp_rows = nullptr, *dp_chunks = nullptr;
+  double *dp_xprop = nullptr, *dp_hastings = nullptr;
+  int* dp_htype = nullptr;
+  unsigned char *dp_hvalid = nullptr, *dp_acc_out = nullptr;
   // device likelihood (ptm_set_target_device): the user's function enqueues on the stream; its batch buffers (owned or the
   // caller's), the count, the row -> chain index, the chunk totals of the pack, hand-over buffers in device memory whatever the
   // population, and the best log-posterior seen with its state {lpost, x[D]}
@@ -284,6 +298,10 @@ static double* xrows(ptm_engine* e) {
   if (e->rows_labelled) flush_rows(e);
   return e->xdev;
 }
+
+// proposals the engine does not draw itself: the host's (ptm_set_proposal_callback) or the user's on the device (ptm_set_proposal_device).
+// Either way the sweep kernel takes ready-made proposals (host_prop)
+static inline bool user_prop(const ptm_engine* e) { return e->pcb != nullptr || e->dpfn != nullptr; }
 
 extern "C" const char* ptm_last_error(void) { return g_err.c_str(); }
 extern "C" int ptm_abi_version(void) { return PTM_ABI_VERSION; }
@@ -527,7 +545,9 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
                   e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt, e->pidx, e->pcnt, e->pf_flag, e->pf_counts, e->pf_margin,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
                   e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
-                  e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws};
+                  e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws,
+                  e->dp_xcur, e->dp_xnew, e->dp_hast_k, e->dp_rung, e->dp_walker, e->dp_type_k, e->dp_valid_k, e->dp_acc_k, e->dp_count, e->dp_rows, e->dp_chunks,
+                  e->dp_xprop, e->dp_hastings, e->dp_htype, e->dp_hvalid, e->dp_acc_out};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (e->h_sums) (void)hipHostFree(e->h_sums);
@@ -731,6 +751,7 @@ extern "C" int ptm_set_proposal_callback(ptm_engine* e, ptm_propose_batch_fn pro
   if (!e) return fail(PTM_ERR_INVALID, "null engine");
   if (!propose) {   // back to the device proposals, if any were set
     e->pcb = nullptr; e->pres = nullptr; e->pcb_user = nullptr;
+    e->dpfn = nullptr; e->dpres = nullptr; e->dp_user = nullptr;   // (the last proposal setter wins)
     e->have_prop = e->prop ? 1 : 0;
     return PTM_OK;
   }
@@ -748,6 +769,43 @@ extern "C" int ptm_set_proposal_callback(ptm_engine* e, ptm_propose_batch_fn pro
     return rc;
   if (!e->onedfrac) return fail(PTM_ERR_INVALID, "engine not built");
   e->pcb = propose; e->pres = result; e->pcb_user = user;
+  e->dpfn = nullptr; e->dpres = nullptr; e->dp_user = nullptr;   // (the last proposal setter wins)
+  e->have_prop = 1;
+  return PTM_OK;
+}
+
+extern "C" int ptm_set_proposal_device(ptm_engine* e, ptm_propose_device_fn propose, ptm_proposal_result_device_fn result, void* user) {
+  if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  if (!propose && result) return fail(PTM_ERR_INVALID, "a result function without a propose function");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_set_proposal_device");
+  if (!propose) {   // back to the device's own proposals, if any were set
+    e->dpfn = nullptr; e->dpres = nullptr; e->dp_user = nullptr;
+    e->pcb = nullptr; e->pres = nullptr; e->pcb_user = nullptr;
+    e->have_prop = e->prop ? 1 : 0;
+    return PTM_OK;
+  }
+  if (!e->onedfrac) return fail(PTM_ERR_INVALID, "engine not built");
+  const size_t Nc = e->Nc, D = e->D, DP = e->DP;
+  int rc;
+  if (!e->dp_count) {
+    if ((rc = dalloc(&e->dp_xcur, Nc * D)) || (rc = dalloc(&e->dp_xnew, Nc * D)) || (rc = dalloc(&e->dp_hast_k, Nc)) || (rc = dalloc(&e->dp_rung, Nc)) ||
+        (rc = dalloc(&e->dp_walker, Nc)) || (rc = dalloc(&e->dp_type_k, Nc)) || (rc = dalloc(&e->dp_valid_k, Nc)) || (rc = dalloc(&e->dp_acc_k, Nc)) ||
+        (rc = dalloc(&e->dp_rows, Nc)) || (rc = dalloc(&e->dp_chunks, (Nc + DL_CHUNK - 1) / DL_CHUNK)) || (rc = dalloc(&e->dp_xprop, Nc * DP)) ||
+        (rc = dalloc(&e->dp_hastings, Nc)) || (rc = dalloc(&e->dp_htype, Nc)) || (rc = dalloc(&e->dp_hvalid, Nc)) || (rc = dalloc(&e->dp_acc_out, Nc)) ||
+        (rc = dalloc(&e->dp_count, 1)))
+      return rc;
+    // the rows of chains that make no move are read by the sweep kernel and never used: let them hold zeros, not what the allocator left
+    HIPCHK(hipMemsetAsync(e->dp_xprop, 0, Nc * DP * 8, e->stream));
+    HIPCHK(hipMemsetAsync(e->dp_xnew, 0, Nc * D * 8, e->stream));
+    HIPCHK(hipMemsetAsync(e->dp_hastings, 0, Nc * 8, e->stream));
+    HIPCHK(hipMemsetAsync(e->dp_htype, 0, Nc * 4, e->stream));
+    HIPCHK(hipMemsetAsync(e->dp_hvalid, 0, Nc, e->stream));
+    HIPCHK(hipMemsetAsync(e->dp_acc_out, 0, Nc, e->stream));
+    HIPCHK(hipMemsetAsync(e->dp_acc_k, 0, Nc * 4, e->stream));
+  }
+  e->dpfn = propose; e->dpres = result; e->dp_user = user;
+  e->pcb = nullptr; e->pres = nullptr; e->pcb_user = nullptr;   // (the last proposal setter wins)
   e->have_prop = 1;
   return PTM_OK;
 }
@@ -1153,7 +1211,7 @@ extern "C" int ptm_set_proposal_prior_draw(ptm_engine* e, int member) {
   if (member < 0 || member >= K) return fail(PTM_ERR_INVALID, "prior draw: member %d is not one of the set's %d (top) members", member, K);
   if (e->ada_on && member == e->ada.nested) return fail(PTM_ERR_INVALID, "prior draw: member %d is the nested set", member);
   if (e->set_neg[member]) return fail(PTM_ERR_INVALID, "prior draw: member %d has a negative scale, which marks differential evolution", member);
-  if (e->pcb) return fail(PTM_ERR_INVALID, "host-side proposals are set (ptm_set_proposal_callback): they replace every device proposal");
+  if (user_prop(e)) return fail(PTM_ERR_INVALID, "host-side proposals are set (ptm_set_proposal_callback): they replace every device proposal");
   { const int rc = prior_drawable(e); if (rc) return rc; }
   e->prior_member = member;
   return PTM_OK;
@@ -1212,7 +1270,7 @@ extern "C" int ptm_set_proposal_de(ptm_engine* e, const ptm_de_params* q, int n_
   if (e->hist.rungs != e->nloc || e->hist.cap < 2)
     return fail(PTM_ERR_INVALID, "differential evolution draws from every rung's saved history: create the engine with history_rungs = rung_count and a "
                                  "history_capacity that holds every row of the run");
-  if (e->pcb) return fail(PTM_ERR_INVALID, "host-side proposals are set (ptm_set_proposal_callback): they replace every device proposal");
+  if (user_prop(e)) return fail(PTM_ERR_INVALID, "host-side proposals are set (ptm_set_proposal_callback): they replace every device proposal");
   if (!(q->snooker >= 0 && q->snooker <= 1) || !(q->gamma_one_frac >= 0 && q->gamma_one_frac <= 1) || !(q->reduce_gamma > 0) ||
       !(q->ignore_frac >= 0 && q->ignore_frac < 1) || n_init_extra < 0 || (n_init_extra > 0 && !init_rows))
     return fail(PTM_ERR_INVALID, "differential evolution: snooker and gamma_one_frac in [0, 1], reduce_gamma > 0, ignore_frac in [0, 1), init rows given");
@@ -1317,7 +1375,7 @@ static Dev make_dev(ptm_engine* e, bool labelled = false) {   // labelled: the c
   p.hist = e->hist;
   p.map = e->map;
   p.c_begin = 0; p.c_end = e->Nc;
-  p.host_prop = e->pcb ? 1 : 0; p.hastings = e->hastings; p.htype = e->htype; p.hvalid = e->hvalid; p.acc_out = e->acc_out;
+  p.host_prop = user_prop(e) ? 1 : 0; p.hastings = e->hastings; p.htype = e->htype; p.hvalid = e->hvalid; p.acc_out = e->acc_out;
   return p;
 }
 
@@ -1361,7 +1419,7 @@ static SweepFacts sweep_facts(const ptm_engine* e, long long chains, bool touche
   f.has_bounds = e->has_bounds; f.bounds_box = e->bounds_box; f.all_uniform = e->all_uniform; f.has_mean = e->has_mean; f.any_oned = e->any_oned;
   f.mix_K = e->mix_K;
   f.evolving = e->betaC != nullptr; f.tracked = e->hist.rungs || e->map.rungs;
-  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.ada = e->ada_on;
+  f.user_like = user_like(e); f.host_prop = user_prop(e); f.ada = e->ada_on;
   f.de = e->de_on || e->prior_member >= 0;   // (a prior member routes as differential evolution does: only the lanes and general kernels draw it)
   f.mode = f.user_like ? 1 : 0;   // (the propose and accept passes run on one build)
   f.touched = touched;
@@ -1515,6 +1573,7 @@ extern "C" int ptm_set_target_device(ptm_engine* e, ptm_loglike_device_fn fn, vo
     e->dl_own_ll = true;
   }
   HIPCHK(hipMemsetAsync(e->dl_gate, 0, Nc, e->stream));
+  HIPCHK(hipMemsetAsync(e->dl_xprop, 0, Nc * DP * 8, e->stream));   // (device proposals: the sweep reads, and never uses, the rows of chains that make no move)
   if ((rc = devlike_reset_best(e))) return rc;
   e->dfn = fn; e->dfn_user = user;
   e->cb = nullptr;   // (the last target setter wins)
@@ -1620,6 +1679,41 @@ static int launch_box_prefilter(ptm_engine* e, const double* x, int rung0, int n
   return PTM_OK;
 }
 
+// ---- device proposals (ptm_set_proposal_device) ---------------------------------------------------------------------------
+// pack the chains that make a Metropolis move this step (touch flag 0) into the batch, name their rungs and walkers, call the user's
+// function on the stream and put its proposals, ratios, types and validity where the sweep kernel reads them by chain (xprop: the
+// buffer of the branch the sweep takes).  Everything is queued; nothing waits.
+static int devprop_stage(ptm_engine* e, double* xprop) {
+  const int n = e->Nc, D = e->D;
+  const int nchunk = (n + DL_CHUNK - 1) / DL_CHUNK;
+  const double* xcur = xrows(e);
+  hipLaunchKernelGGL(devlike_count_kernel, dim3(nchunk), dim3(DL_CHUNK), 0, e->stream, n, (const unsigned char*)e->touch, 0xFF, 0, e->dp_chunks);
+  HIPCHK(hipGetLastError());
+  const unsigned ugrid = (unsigned)(((size_t)n * e->DP + DEVPROP_THREADS - 1) / DEVPROP_THREADS), rgrid = (unsigned)((n + DEVPROP_THREADS - 1) / DEVPROP_THREADS);
+#define PTM_DP_PACK(N) case N: hipLaunchKernelGGL((devlike_pack_kernel<N>), dim3(nchunk), dim3(DL_CHUNK), 0, e->stream, n, D, nchunk, (const unsigned char*)e->touch, 0xFF, 0, \
+                                                  (const int*)e->dp_chunks, xcur, xcur, e->dp_xcur, e->dp_rows, e->dp_count); break;
+  switch (e->DP) {
+    PTM_DP_PACK(4) PTM_DP_PACK(8) PTM_DP_PACK(16) PTM_DP_PACK(32) PTM_DP_PACK(64) PTM_DP_PACK(128) PTM_DP_PACK(256) PTM_DP_PACK(512) PTM_DP_PACK(1024)
+    default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  }
+#undef PTM_DP_PACK
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(devprop_ids_kernel, dim3(rgrid), dim3(DEVPROP_THREADS), 0, e->stream, n, e->W, e->r0, (int)e->cfg.walker_begin, (const int*)e->dp_rows,
+                     e->dp_rung, e->dp_walker, e->dp_hast_k, e->dp_type_k, e->dp_valid_k);
+  HIPCHK(hipGetLastError());
+  e->dpfn(e->dp_user, (void*)e->stream, n, D, e->dp_xcur, e->dp_rung, e->dp_walker, e->dp_count, e->step, e->dp_xnew, e->dp_hast_k, e->dp_type_k, e->dp_valid_k);
+#define PTM_DP_UNPACK(N) case N: hipLaunchKernelGGL((devprop_unpack_kernel<N>), dim3(ugrid), dim3(DEVPROP_THREADS), 0, e->stream, n, D, (const int32_t*)e->dp_count, \
+                                                    (const int*)e->dp_rows, (const double*)e->dp_xnew, (const double*)e->dp_hast_k, (const int32_t*)e->dp_type_k, \
+                                                    (const int32_t*)e->dp_valid_k, xprop, e->dp_hastings, e->dp_htype, e->dp_hvalid); break;
+  switch (e->DP) {
+    PTM_DP_UNPACK(4) PTM_DP_UNPACK(8) PTM_DP_UNPACK(16) PTM_DP_UNPACK(32) PTM_DP_UNPACK(64) PTM_DP_UNPACK(128) PTM_DP_UNPACK(256) PTM_DP_UNPACK(512) PTM_DP_UNPACK(1024)
+    default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  }
+#undef PTM_DP_UNPACK
+  HIPCHK(hipGetLastError());
+  return PTM_OK;
+}
+
 static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = true) {
   const bool labelled = e->label_step;   // (set by this step's exchange phase under the very conditions of the compacted sweep below)
   e->label_step = false;
@@ -1627,7 +1721,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   if (nr < 0) nr = e->nloc - rung0;
   if (rung0 < 0 || nr < 0 || rung0 + nr > e->nloc) return fail(PTM_ERR_INVALID, "rung range out of the shard");
   p.c_begin = rung0 * e->W; p.c_end = (rung0 + nr) * e->W;
-  if ((user_like(e) || e->pcb) && (rung0 != 0 || nr != e->nloc)) return fail(PTM_ERR_UNSUPPORTED, "partial sweeps with a user likelihood (host or device) or host-side proposals are not built");
+  if ((user_like(e) || user_prop(e)) && (rung0 != 0 || nr != e->nloc)) return fail(PTM_ERR_UNSUPPORTED, "partial sweeps with a user likelihood (host or device) or host-side proposals are not built");
   auto close_step = [&]() {
     e->step += 1; e->touched = false; e->step_booked = false;
     if (e->compact_step) { e->nhist_pending += 1; e->compact_step = false; }
@@ -1721,6 +1815,13 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     HIPCHK(copy_unless_shared(e->hvalid, e->h_valid.data(), Nc, hipMemcpyHostToDevice, e->stream));
     p.xprop = e->xprop; p.lprior_new = e->lprior_new; p.gate = e->gate; p.llike_new = e->llike_new;
   }
+  if (e->dpfn) {
+    // device proposals: the user's function fills the rows of the buffer the sweep (or its propose pass) reads its proposals from
+    p.xprop = e->dfn ? e->dl_xprop : e->cb ? e->xprop : e->dp_xprop;
+    p.hastings = e->dp_hastings; p.htype = e->dp_htype; p.hvalid = e->dp_hvalid; p.acc_out = e->dp_acc_out;
+    const int rc = devprop_stage(e, p.xprop);
+    if (rc) return rc;
+  }
   if (e->dfn) {
     // device likelihood: propose pass -> pack -> the user's work -> scatter (+ best) -> accept pass, all queued on the stream
     p.xprop = e->dl_xprop; p.lprior_new = e->dl_lprior_new; p.gate = e->dl_gate; p.llike_new = e->dl_llike_new;
@@ -1747,6 +1848,13 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     e->p_acc.resize(npick);
     for (size_t k = 0; k < npick; ++k) e->p_acc[k] = e->h_acc[e->p_pick[k]] == 1 ? 1 : 0;
     e->pres(e->pcb_user, (int)npick, e->p_rung.data(), e->p_walker.data(), e->p_acc.data());
+  }
+  if (e->dpfn && e->dpres) {   // the same for device proposals: the outcomes by row, then the user's function, queued behind the accept pass
+    const int n = e->Nc;
+    hipLaunchKernelGGL(devprop_result_kernel, dim3((unsigned)((n + DEVPROP_THREADS - 1) / DEVPROP_THREADS)), dim3(DEVPROP_THREADS), 0, e->stream, n,
+                       (const int32_t*)e->dp_count, (const int*)e->dp_rows, (const unsigned char*)e->dp_acc_out, e->dp_acc_k);
+    HIPCHK(hipGetLastError());
+    e->dpres(e->dp_user, (void*)e->stream, n, e->dp_rung, e->dp_walker, e->dp_count, e->dp_acc_k);
   }
   if (ev1) HIPCHK(hipEventRecord(ev1, e->stream));
   if (last) close_step();
@@ -2246,7 +2354,7 @@ static bool fused_applies(const ptm_engine* e) {
   static const bool fused_ok = [] { const char* v = getenv("PTM_FUSED"); return !(v && *v == '0'); }();
   StepFacts f;
   f.DP = e->DP; f.Nt = e->Nt; f.W = e->W;
-  f.user_like = user_like(e); f.host_prop = e->pcb != nullptr; f.ada = e->ada_on || e->prior_member >= 0; f.time_kernels = e->cfg.time_kernels != 0;
+  f.user_like = user_like(e); f.host_prop = user_prop(e); f.ada = e->ada_on || e->prior_member >= 0; f.time_kernels = e->cfg.time_kernels != 0;
   f.evolving = e->evolve_rate > 0; f.evolve_cut = e->evolve_cut >= 0;
   f.decide_lds = fused_decide_lds(e);
   return fused_applies(f, fused_ok);
@@ -2300,7 +2408,7 @@ static bool ladder_applies(ptm_engine* e, long long* grid_out = nullptr, size_t*
   // mixtures, history and MAP tracking have their builds: ladder_flavour); ANY population whose grid is resident at once (below): where
   // it fits, a step costs this kernel its ~6 us of latency whatever the walkers' number (64 walkers x 64 rungs of 12 dimensions with the
   // sampler's defaults: 14 us against 40 on two launches)
-  if (user_like(e) || e->prior_cb || e->pcb) return false;
+  if (user_like(e) || e->prior_cb || user_prop(e)) return false;
   if (e->ada_on) return false;   // (an adaptive proposal set: exchange kernel + the lanes or general kernel's ADA build)
   if (e->prior_member >= 0) return false;   // (a member that draws from the prior: only the lanes and general kernels carry it)
   const int R = 256 / e->DP, NB = (e->Nt + R - 1) / R;
@@ -2692,6 +2800,7 @@ extern "C" int ptm_exchange_finish_and_sweep(ptm_engine* e, const void* recv_bel
   SETTLE(e);
   NO_BATCH(e, "ptm_exchange_finish_and_sweep");
   NO_DEVLIKE(e, "ptm_exchange_finish_and_sweep");
+  if (e && e->dpfn && e->nloc != e->Nt) return fail(PTM_ERR_UNSUPPORTED, "ptm_exchange_finish_and_sweep on a rung shard with device proposals is not built (ptm_set_proposal_device)");
   int rc = ready(e);
   if (rc) return rc;
   const bool first = e->r0 == 0, last = e->r0 + e->nloc == e->Nt;
@@ -2862,7 +2971,7 @@ extern "C" int ptm_shard_step(ptm_engine* e, int n) {
   int rc = ready(e);
   if (rc) return rc;
   if (!e->shard) return fail(PTM_ERR_INVALID, "ptm_shard_init first");
-  if (user_like(e) || e->pcb) return fail(PTM_ERR_UNSUPPORTED, "sharded steps with a user likelihood (host or device) or host-side proposals are not built");
+  if (user_like(e) || user_prop(e)) return fail(PTM_ERR_UNSUPPORTED, "sharded steps with a user likelihood (host or device) or host-side proposals are not built");
   // all n steps are admitted here, before anything is queued; their pieces go through the public calls, which then do not ask again
   if ((rc = count_guard(e, n, "ptm_shard_step"))) return rc;
   e->steps_prepaid = n > 0 ? n : 0;

@@ -37,6 +37,7 @@ EXPORTS = [
     "ptm_log_evidence",
     "ptm_rhat", "ptm_rhat_series",
     "ptm_get_prefilter_counts",
+    "ptm_set_proposal_device",
 ]
 
 
@@ -77,6 +78,11 @@ PROPOSE_BATCH_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, _dp, _i32p, _
 PROPOSAL_RESULT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, _i32p, _i32p, _i32p)
 # ptm_loglike_device_fn (include/ptm_engine.h): user, stream, n_rows, dim, X_dev, count_dev, out_llike_dev (device pointers)
 LOGLIKE_DEVICE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+# ptm_propose_device_fn: user, stream, n_rows, dim, X_cur_dev, rung_dev, walker_dev, count_dev, step, X_prop_dev, log_hastings_dev, type_dev, valid_dev
+PROPOSE_DEVICE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+# ptm_proposal_result_device_fn: user, stream, n_rows, rung_dev, walker_dev, count_dev, accepted_dev
+PROPOSAL_RESULT_DEVICE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 TORCH_LOADED_FIRST = None
@@ -182,6 +188,8 @@ def load():
         L.ptm_set_target_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ptm_target_device_rows.argtypes = [C.c_void_p]
         L.ptm_get_best_evaluated.argtypes = [C.c_void_p, _dp, _dp]
+    if hasattr(L, "ptm_set_proposal_device"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_set_proposal_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "ptm_set_proposal_adaptive"):
         L.ptm_set_proposal_adaptive.argtypes = [C.c_void_p, C.POINTER(PtmAdaptiveSet), _dp, _dp, _dp, _dp, _i32p, _i32p]
         L.ptm_get_proposal_adapt_state.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p]
@@ -201,11 +209,16 @@ def load():
     return L
 
 
-def _wrap_int32_device(torch, ptr, dev):
-    """a 1-element int32 torch tensor over a device pointer (the engine's count), through the CUDA array interface"""
+def _wrap_device(torch, ptr, shape, typestr, dev):
+    """a torch view of an engine-allocated device buffer (no copy), through the CUDA array interface"""
     class _Arr:
-        __cuda_array_interface__ = {"shape": (1,), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
     return torch.as_tensor(_Arr(), device=dev)
+
+
+def _wrap_int32_device(torch, ptr, dev):
+    """a 1-element int32 torch tensor over a device pointer (the engine's count)"""
+    return _wrap_device(torch, ptr, (1,), "<i4", dev)
 
 
 def _chk(rc):
@@ -536,6 +549,59 @@ class Engine:
             rcb = PROPOSAL_RESULT_FN(rtramp)
         self._keep += [propose, rcb]
         _chk(self.L.ptm_set_proposal_callback(self.h, C.cast(propose, C.c_void_p), None if rcb is None else C.cast(rcb, C.c_void_p), None))
+
+    def set_proposal_device(self, fn, result=None):
+        """proposals on the DEVICE (ptm_set_proposal_device): fn(X_cur, rung, walker, count, step, X_prop, log_hastings, type, valid)
+        with torch views of the engine's buffers -- X_cur / X_prop (n_rows, D) float64, rung / walker / type / valid (n_rows,)
+        int32, log_hastings (n_rows,) float64, count a 1-element int32 tensor, step a Python int.  Rows [0, count) are the chains
+        that move this step, in local-chain order; the rest hold the other chains' states, so a fixed-shape evaluation is safe.
+        log_hastings, type and valid arrive preset to 0, 0, 1; X_prop is to be filled with whole states.
+        result(rung, walker, count, accepted), optional, sees the outcomes (accepted[k] in {0, 1} for k < count) after every sweep.
+        Both run once per sweep with the engine's stream current and must only ENQUEUE their work (no .item(), no copy to the
+        host): step(n) queues n steps and returns.  Needs torch imported before the engine library (one HIP runtime).
+        fn = None goes back to the engine's own proposals."""
+        if fn is None:
+            _chk(self.L.ptm_set_proposal_device(self.h, None, None, None))
+            return
+        import torch
+        if not TORCH_LOADED_FIRST:
+            raise PtmError("set_proposal_device needs torch imported BEFORE the engine library was loaded (one HIP runtime per process: "
+                           "see ptmcmc_amd.parallel.EngineShard)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        views = {}
+
+        def view(ptr, shape, typestr):
+            key = (ptr, shape, typestr)
+            v = views.get(key)
+            if v is None:   # the engine's buffers are fixed for its lifetime: each is wrapped once
+                v = views[key] = _wrap_device(torch, ptr, shape, typestr, dev)
+            return v
+
+        def tramp(user, stream, n, dim, xc, rg, wk, cnt, step, xp, lh, ty, va):
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                fn(view(xc, (n, dim), "<f8"), view(rg, (n,), "<i4"), view(wk, (n,), "<i4"), view(cnt, (1,), "<i4"), int(step),
+                   view(xp, (n, dim), "<f8"), view(lh, (n,), "<f8"), view(ty, (n,), "<i4"), view(va, (n,), "<i4"))
+        cb = PROPOSE_DEVICE_FN(tramp)
+        rcb = None
+        if result is not None:
+            def rtramp(user, stream, n, rg, wk, cnt, acc):
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                    result(view(rg, (n,), "<i4"), view(wk, (n,), "<i4"), view(cnt, (1,), "<i4"), view(acc, (n,), "<i4"))
+            rcb = PROPOSAL_RESULT_DEVICE_FN(rtramp)
+        self._keep += [cb, rcb, views]
+        _chk(self.L.ptm_set_proposal_device(self.h, C.cast(cb, C.c_void_p), None if rcb is None else C.cast(rcb, C.c_void_p), None))
+
+    def set_proposal_device_c(self, fnptr, result_fnptr=None, user=None):
+        """proposals on the device through raw C function pointers of the ptm_propose_device_fn / ptm_proposal_result_device_fn
+        shapes (e.g. from a hipcc-built .so: ctypes.cast(lib.my_launcher, ctypes.c_void_p)); user: the pointer both are handed"""
+        def raw(f):
+            if f is None:
+                return None
+            return f.value if isinstance(f, C.c_void_p) else (C.cast(f, C.c_void_p).value if isinstance(f, C._CFuncPtr) else int(f))
+        self._keep += [fnptr, result_fnptr]
+        p, r = raw(fnptr), raw(result_fnptr)
+        _chk(self.L.ptm_set_proposal_device(self.h, None if p is None else C.c_void_p(p), None if r is None else C.c_void_p(r),
+                                            C.c_void_p(user) if user is not None else None))
 
     def set_ladder(self, beta):
         b = np.ascontiguousarray(beta, dtype=np.float64)

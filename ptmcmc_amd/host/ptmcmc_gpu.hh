@@ -747,6 +747,43 @@ class proposal_distribution {
   virtual const sampleable_probability_function* device_draw_source() const { return nullptr; }
 };
 
+// A proposal drawn ON THE DEVICE (ptm_set_proposal_device): the engine calls draw_device once per sweep on its own stream with the
+// current states of the chains that move in device memory (X_cur_dev [n_rows][dim]; rows [0, *count_dev) move, in local-chain order,
+// the rest hold the other chains' states; rung_dev / walker_dev name each row's GLOBAL rung and replica; step is the ladder's step
+// number); it enqueues its work on `stream` (a hipStream_t) and returns.  It writes whole proposed states to X_prop_dev and, where they
+// differ from the presets 0, 0, 1, log_hastings_dev, type_dev and valid_dev.  result_device (asked for by has_result_device) sees the
+// outcomes after the accept pass is queued: accepted_dev[k] in {0, 1} for k < *count_dev, the rows of the draw_device call.
+// The host draw() stays required: wrapped in a proposal_distribution_set, or with PTM_DEVICE_PROPOSAL=0 in the environment, the ladder
+// takes the host-proposal step and calls it once per moving chain.  With a device_likelihood the step stays on the device end to end.
+// ONE clone serves every chain of a ladder on the device path (the batch holds them all).
+class device_proposal : public proposal_distribution {
+ public:
+  virtual void draw_device(void* stream, int n_rows, int dim, const double* X_cur_dev, const int32_t* rung_dev, const int32_t* walker_dev,
+                           const int32_t* count_dev, uint64_t step, double* X_prop_dev, double* log_hastings_dev, int32_t* type_dev,
+                           int32_t* valid_dev) = 0;
+  virtual bool has_result_device() const { return false; }
+  virtual void result_device(void* stream, int n_rows, const int32_t* rung_dev, const int32_t* walker_dev, const int32_t* count_dev,
+                             const int32_t* accepted_dev) {}
+  state draw(state& s, chain* caller) override = 0;
+  proposal_distribution* clone() const override = 0;
+  std::string show() override { return "DeviceProposal()"; }
+  static void device_trampoline(void* self, void* stream, int n_rows, int dim, const double* X_cur_dev, const int32_t* rung_dev,
+                                const int32_t* walker_dev, const int32_t* count_dev, uint64_t step, double* X_prop_dev, double* log_hastings_dev,
+                                int32_t* type_dev, int32_t* valid_dev) {
+    ((device_proposal*)self)->draw_device(stream, n_rows, dim, X_cur_dev, rung_dev, walker_dev, count_dev, step, X_prop_dev, log_hastings_dev, type_dev, valid_dev);
+  }
+  static void device_result_trampoline(void* self, void* stream, int n_rows, const int32_t* rung_dev, const int32_t* walker_dev,
+                                       const int32_t* count_dev, const int32_t* accepted_dev) {
+    ((device_proposal*)self)->result_device(stream, n_rows, rung_dev, walker_dev, count_dev, accepted_dev);
+  }
+  // is this proposal one the ladder hands to the device as it is?  (not wrapped in a set; PTM_DEVICE_PROPOSAL=0 keeps the host path)
+  static bool taken_by_device(const proposal_distribution* p) {
+    const char* v = getenv("PTM_DEVICE_PROPOSAL");
+    if (v && *v == '0') return false;
+    return dynamic_cast<const device_proposal*>(p) != nullptr;
+  }
+};
+
 namespace detail {
 // a standard normal from a chain's generator (the reference: newran's Normal, newran2.cxx:164-217; replaced, not reproduced)
 inline double normal_from(Random& rng) {
@@ -2340,6 +2377,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   bool want_de = false, de_built = false;   // differential evolution drawn on the device from the device's history
   bool adaptive_dev = false;                // the proposal is an adaptive set drawn and adapted on the device (ptm_set_proposal_adaptive)
   bool prior_dev = false;                   // a member of the set draws from the prior on the device (ptm_set_proposal_prior_draw)
+  bool user_dev = false;                    // the proposal is a device_proposal drawn on the device (ptm_set_proposal_device)
   int ring_rows = 0, ring_rungs = 0;   // the device history ring as the engine was created with it
   uint64_t eng_seed = 0;
   struct mirror_t {   // one chain's saved history, raw indexing as MH_chain::states / lposts / llikes (chain.hh:155-163)
@@ -2998,6 +3036,18 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   void set_proposal(proposal_distribution& proposal) {
     for (auto p : props) delete p;
     props.clear();
+    user_dev = false;
+    if (device_proposal::taken_by_device(&proposal)) {
+      // a device_proposal: its draw_device runs on the engine's stream, the likelihood stays where it is (a device_likelihood: the whole
+      // step on the device).  Every rung gets a clone (reports); the first serves the batch.
+      if (host_mode) build_engine(false);
+      for (int i = 0; i < Ntemps; i++) props.push_back(proposal.clone());
+      device_proposal* dp = dynamic_cast<device_proposal*>(props[0]);
+      ptm_check(ptm_set_proposal_device(eng, &device_proposal::device_trampoline, dp->has_result_device() ? &device_proposal::device_result_trampoline : nullptr, dp),
+                "set_proposal_device");
+      user_dev = true; adaptive_dev = false; prior_dev = false;
+      return;
+    }
     int kind = 0;
     double odf = 0;
     std::vector<double> f, all, odfs(Ntemps);
@@ -3094,6 +3144,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
   bool proposals_on_host() const { return host_mode; }
   bool draws_prior_on_device() const { return prior_dev; }
+  bool draws_user_proposal_on_device() const { return user_dev; }
   // Can the device make this proposal's draws from a distribution (draw_from_dist members, device_draw_source)?  Only from the very
   // prior the engine was given as a per-dimension product without a flat dimension (ptm_set_proposal_prior_draw); true without such members
   static bool prior_draws_fit_device(const proposal_distribution& proposal, const sampleable_probability_function* prior, bool prior_on_host) {
@@ -3848,6 +3899,7 @@ class ptmcmc_sampler : public bayes_sampler {
     int kind; double odf; std::vector<double> f;
     const int dim = chain_prior->getDim();
     bool host = !cprop->device_describe(dim, kind, f, odf) && !dynamic_cast<user_gaussian_prop*>(cprop);
+    if (device_proposal::taken_by_device(cprop)) host = false;   // (a device_proposal: drawn on the engine's stream, ptm_set_proposal_device)
     {
       std::vector<int> ty; std::vector<double> ce, hw;
       if (!host && !parallel_tempering_chains::prior_draws_fit_device(*cprop, chain_prior, !chain_prior->describe(ty, ce, hw))) host = true;
@@ -3874,6 +3926,9 @@ class ptmcmc_sampler : public bayes_sampler {
     if (cprop->device_draw_source() || cc->draws_prior_on_device() || draw_from_dist::kept_on_host())
       std::cout << "ptmcmc_sampler::initialize: draws from the prior are made on the " << (cc->draws_prior_on_device() ? "device (ptm_set_proposal_prior_draw)" : "host (the host-proposal step)")
                 << "; proposals are drawn on the " << (cc->proposals_on_host() ? "host" : "device") << std::endl;
+    if (dynamic_cast<device_proposal*>(cprop))
+      std::cout << "ptmcmc_sampler::initialize: the device_proposal is drawn on the " << (cc->draws_user_proposal_on_device() ? "device (ptm_set_proposal_device)" : "host (the host-proposal step)")
+                << std::endl;
     return 0;
   }
 
