@@ -597,6 +597,27 @@ int ptm_rhat(ptm_engine* e, int rung, int nfeat, int nrows, double* rhat /*[nfea
 int ptm_rhat_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* rhat /*[nfeat]*/, double* mean, double* within,
                     double* between /*[nfeat] or NULL*/, double* seq_mean, double* seq_var /*[2*nseries*nfeat] or NULL*/);
 
+/* ---- exact nearest-neighbour squared distances on the device --------------------------------------------------------------
+ * The search inside the k-NN Kullback-Leibler estimator of Perez-Cruz with which the reference tests a proposal's invariance
+ * (test_proposal.hh:350-464), as the facade's kl_estimator states it (ptmcmc_amd/host/ptmcmc_gpu.hh): for every point i of P the
+ * smallest squared distance to a point of Q.  The reference turns to approximate neighbours at the sampler's sizes; this search is
+ * exact, brute force, O(nP nQ dim).
+ *  - The distance is state::dist2 (states.cc:207-233): per dimension diff = |b - a|; in a wrapped dimension also the same with both
+ *    points shifted down by (xmax - xmin) / 2 and wrap-enforced, the smaller of the two; the diff * diff are summed in dimension
+ *    order, multiply, then add (no contraction): nnd2[i] carries the bits of kl_estimator's one_nnd2 / all_nnd2.
+ *  - same_set = 1: Q is P and index i is skipped for query i (all_nnd2); a duplicate of point i elsewhere still gives 0.
+ *  - Host arrays, row-major [n][dim]; no engine needed.  wrapped NULL: no dimension is wrapped; xmin, xmax are read where wrapped.
+ * PTM_ERR_INVALID (nnd2 is left untouched): a null P, Q or nnd2, nP < 1 or nQ < 1, same_set with nQ != nP or nP < 2, dim < 1, a wrapped
+ * dimension without finite xmin < xmax, a non-finite coordinate (looked for on the host before anything is queued).
+ * PTM_ERR_UNSUPPORTED: dim > 128 (the host estimator serves there).  The call works in one device allocation and on a stream of its
+ * own, both kept for the next call (an allocation above 256 MiB is given back), and waits for that stream only; calls are serialised.  PTM_KL_SPLITS=n in the environment forces the number of
+ * parts the searched set is split into (tests). */
+int ptm_nn_dist2(int device, const double* P, int64_t nP, const double* Q, int64_t nQ, int dim, const int32_t* wrapped /*[dim] or NULL*/,
+                 const double* xmin, const double* xmax /*[dim], read where wrapped*/, int same_set /*1: Q is P, index i is skipped for query i*/,
+                 double* nnd2 /*[nP]*/);
+/* the points of the searched set one tile of the search holds (what a test builds its edge sizes around) */
+int ptm_nn_dist2_tile(void);
+
 /* ---- verification hooks (used by tests/ only; evaluate device functions on arrays) ---------------------- */
 enum { PTM_FN_LOG = 0, PTM_FN_EXP = 1, PTM_FN_SIN_0_PI = 2, PTM_FN_COS_HPI = 3, PTM_FN_SQRT = 4, PTM_FN_DIV = 5,
        PTM_FN_SQRT_RAW = 6 };

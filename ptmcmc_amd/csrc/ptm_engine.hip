@@ -25,6 +25,7 @@
 #include "ptm_devprop_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
+#include "ptm_kl_kernels.hpp"
 #include "ptm_launch.hpp"
 #include "ptm_rhat_kernels.hpp"
 #include "ptm_shard_rccl.hpp"
@@ -3819,6 +3820,143 @@ extern "C" int ptm_rhat_series(int device, const double* series, int64_t n, int 
   if ((rc = ess_series_source(&S, device, series, n, nseries, nfeat))) return rc;
   return rhat_run(nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, rhat, mean, within, between, seq_mean, seq_var);
 }
+
+// ---- exact nearest-neighbour squared distances for the k-NN KL estimator (ptm_kl_kernels.hpp) --------------------------------
+// kl_estimator::one_nnd2 / all_nnd2 (ptmcmc_amd/host/ptmcmc_gpu.hh) on a caller's two sample sets.
+// The number of splits of the searched set: four waves for every SIMD of the chip (a wave is KL_THREADS queries), as long as a split
+// keeps four tiles.  PTM_KL_SPLITS=n forces it (tests).
+static int kl_splits(long long nP, long long nQ, int cus) {
+  const char* v = getenv("PTM_KL_SPLITS");
+  long long s = v && *v ? atoll(v) : 0;
+  if (s < 1) {
+    const long long waves = (nP + KL_THREADS - 1) / KL_THREADS, want = 16ll * cus, most = (nQ + 4 * KL_TILE - 1) / (4 * KL_TILE);
+    s = std::min((want + waves - 1) / waves, most);
+  }
+  return (int)std::max(1ll, std::min(s, 1024ll));
+}
+// The workspace and the stream of ptm_nn_dist2, kept from call to call (a stream costs milliseconds to make, a search of ten thousand
+// points less than one): one allocation, grown when a call needs more and given back after a call that needed more than KL_KEEP_BYTES;
+// a stream of its own, so that nothing waits on, or is waited on by, an engine of the same process.  One call at a time.
+static const size_t KL_KEEP_BYTES = (size_t)256 << 20;
+struct KlWorkspace {
+  std::mutex lock;
+  void* all = nullptr;
+  size_t bytes = 0;
+  hipStream_t st = nullptr;
+  int device = -1;
+  int release() {
+    if (st) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipStreamDestroy(st)); st = nullptr; }
+    if (all) { HIPCHK(hipFree(all)); all = nullptr; bytes = 0; }
+    device = -1;
+    return PTM_OK;
+  }
+  int reserve(int dev, size_t need) {
+    int rc;
+    if (device != dev && (rc = release())) return rc;
+    if (!st) { HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); device = dev; }
+    if (bytes < need) {
+      if (all) { HIPCHK(hipFree(all)); all = nullptr; bytes = 0; }
+      HIPCHK(hipMalloc(&all, need));
+      bytes = need;
+    }
+    return PTM_OK;
+  }
+};
+static KlWorkspace g_kl;
+struct KlDeviceGuard {
+  int device_before = -1;   // the caller's current device, put back when the call ends
+  ~KlDeviceGuard() {
+    if (device_before >= 0) (void)hipSetDevice(device_before);
+  }
+};
+template <int DP>
+static void kl_launch(hipStream_t st, bool wrap, dim3 grid, const double* pt, long long nP_pad, int nP, const double* qr, int nQ, int per_split, int same_set, double* part) {
+  if (wrap) hipLaunchKernelGGL((kl_nn_kernel<DP, true>), grid, dim3(KL_THREADS), 0, st, pt, nP_pad, nP, qr, nQ, per_split, same_set, part);
+  else hipLaunchKernelGGL((kl_nn_kernel<DP, false>), grid, dim3(KL_THREADS), 0, st, pt, nP_pad, nP, qr, nQ, per_split, same_set, part);
+}
+extern "C" int ptm_nn_dist2(int device, const double* P, int64_t nP, const double* Q, int64_t nQ, int dim, const int32_t* wrapped, const double* xmin,
+                            const double* xmax, int same_set, double* nnd2) {
+  if (!P || !Q || !nnd2) return fail(PTM_ERR_INVALID, "null argument");
+  if (dim < 1) return fail(PTM_ERR_INVALID, "ptm_nn_dist2: dim must be >= 1");
+  if (nP < 1 || nQ < 1 || nP > 2000000000 || nQ > 2000000000) return fail(PTM_ERR_INVALID, "ptm_nn_dist2: nP and nQ must be in 1..2e9");
+  if (same_set && (nQ != nP || nP < 2)) return fail(PTM_ERR_INVALID, "ptm_nn_dist2: same_set needs nQ == nP >= 2");
+  if (dim > KL_MAX_DIM) return fail(PTM_ERR_UNSUPPORTED, "ptm_nn_dist2: dim > %d (the host estimator serves there)", KL_MAX_DIM);
+  bool wrap = false;
+  for (int d = 0; wrapped && d < dim; ++d)
+    if (wrapped[d]) {
+      if (!xmin || !xmax) return fail(PTM_ERR_INVALID, "null argument");
+      if (!(xmax[d] > xmin[d]) || !std::isfinite(xmin[d]) || !std::isfinite(xmax[d])) return fail(PTM_ERR_INVALID, "ptm_nn_dist2: wrapped dimension %d needs finite xmin < xmax", d);
+      wrap = true;
+    }
+  for (int64_t k = 0; k < nP * dim; ++k)
+    if (!std::isfinite(P[k])) return fail(PTM_ERR_INVALID, "ptm_nn_dist2: P has a non-finite coordinate (point %lld)", (long long)(k / dim));
+  if (!same_set || Q != P)
+    for (int64_t k = 0; k < nQ * dim; ++k)
+      if (!std::isfinite(Q[k])) return fail(PTM_ERR_INVALID, "ptm_nn_dist2: Q has a non-finite coordinate (point %lld)", (long long)(k / dim));
+  int rc = need_device();
+  if (rc) return rc;
+  KlDeviceGuard B;
+  std::lock_guard<std::mutex> one_call(g_kl.lock);
+  if (device >= 0) {
+    int cur = -1;
+    HIPCHK(hipGetDevice(&cur));
+    if (cur != device) { HIPCHK(hipSetDevice(device)); B.device_before = cur; }
+  }
+  int dev = 0, cus = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int DP = 4;
+  while (DP < dim) DP *= 2;
+  const int row = kl_row(DP, wrap);
+  const long long nP_pad = (nP + KL_THREADS - 1) / KL_THREADS * KL_THREADS, nQ_pad = (nQ + KL_TILE - 1) / KL_TILE * KL_TILE;
+  const int splits = kl_splits(nP, nQ, cus);
+  const long long per = (nQ + splits - 1) / splits;
+  const int per_split = (int)std::min<long long>((per + KL_TILE - 1) / KL_TILE * KL_TILE, nQ_pad);
+  // the workspace: both sets as the search wants them, both as they came, the partial minima and the answer, the bounds
+  const size_t pt_bytes = ess_align((size_t)row * nP_pad * 8), qr_bytes = ess_align((size_t)nQ_pad * row * 8), rawp_bytes = ess_align((size_t)nP * dim * 8),
+               rawq_bytes = ess_align((size_t)nQ * dim * 8), part_bytes = ess_align((size_t)(splits + 1) * nP * 8), bounds_bytes = ess_align((size_t)dim * 20);
+  const size_t total = pt_bytes + qr_bytes + rawp_bytes + rawq_bytes + part_bytes + bounds_bytes;
+  if ((rc = g_kl.reserve(dev, total))) return rc;
+  const hipStream_t st = g_kl.st;
+  unsigned char* base = (unsigned char*)g_kl.all;
+  double *d_pt = (double*)base, *d_qr = (double*)(base + pt_bytes), *d_rawp = (double*)(base + pt_bytes + qr_bytes),
+         *d_rawq = (double*)(base + pt_bytes + qr_bytes + rawp_bytes), *part = (double*)(base + pt_bytes + qr_bytes + rawp_bytes + rawq_bytes),
+         *d_min = (double*)(base + pt_bytes + qr_bytes + rawp_bytes + rawq_bytes + part_bytes), *d_max = d_min + dim, *d_out = part + (size_t)splits * nP;
+  int* d_wrapped = (int*)(d_max + dim);
+  if (wrap) {
+    HIPCHK(hipMemcpyAsync(d_min, xmin, (size_t)dim * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_max, xmax, (size_t)dim * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_wrapped, wrapped, (size_t)dim * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipMemsetAsync(d_pt, 0, pt_bytes + qr_bytes, st));   // (the columns and rows behind the last point are read, never used)
+  HIPCHK(hipMemcpyAsync(d_rawp, P, (size_t)nP * dim * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_rawq, Q, (size_t)nQ * dim * 8, hipMemcpyHostToDevice, st));
+  auto blocks = [](long long lanes) { return dim3((unsigned)((lanes + 255) / 256)); };
+  hipLaunchKernelGGL(kl_prepare_kernel, blocks(nP * DP), dim3(256), 0, st, (const double*)d_rawp, (long long)nP, dim, DP, d_wrapped, d_min, d_max, d_pt, 1ll, nP_pad,
+                     (long long)DP * nP_pad, wrap ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(kl_prepare_kernel, blocks(nQ * DP), dim3(256), 0, st, (const double*)d_rawq, (long long)nQ, dim, DP, d_wrapped, d_min, d_max, d_qr, (long long)row,
+                     1ll, (long long)DP, wrap ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  const dim3 grid((unsigned)(nP_pad / KL_THREADS), (unsigned)splits);
+  const double *pt = d_pt, *qr = d_qr;
+#define KL_CASE(N) case N: kl_launch<N>(st, wrap, grid, pt, nP_pad, (int)nP, qr, (int)nQ, per_split, same_set ? 1 : 0, part); break;
+  switch (DP) {
+    KL_CASE(4) KL_CASE(8) KL_CASE(16) KL_CASE(32) KL_CASE(64) KL_CASE(128)
+    default: return fail(PTM_ERR_UNSUPPORTED, "ptm_nn_dist2: no kernel for %d padded dimensions", DP);
+  }
+#undef KL_CASE
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(kl_min_kernel, blocks(nP), dim3(256), 0, st, (const double*)part, splits, (int)nP, d_out);
+  HIPCHK(hipGetLastError());
+  std::vector<double> out((size_t)nP);
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)nP * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (total > KL_KEEP_BYTES) { HIPCHK(hipFree(g_kl.all)); g_kl.all = nullptr; g_kl.bytes = 0; }
+  std::copy(out.begin(), out.end(), nnd2);   // (the caller's array is written last, when nothing can fail any more)
+  return PTM_OK;
+}
+extern "C" int ptm_nn_dist2_tile(void) { return KL_TILE; }
 
 // ---- verification hooks ------------------------------------------------------------------------------------------------
 extern "C" int ptm_debug_eval(int device, int fn, const double* a, const double* b, double* out, int n) {

@@ -38,6 +38,7 @@ EXPORTS = [
     "ptm_rhat", "ptm_rhat_series",
     "ptm_get_prefilter_counts",
     "ptm_set_proposal_device",
+    "ptm_nn_dist2", "ptm_nn_dist2_tile",
 ]
 
 
@@ -205,6 +206,8 @@ def load():
     if hasattr(L, "ptm_rhat"):
         L.ptm_rhat.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
         L.ptm_rhat_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ptm_nn_dist2"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_nn_dist2.argtypes = [C.c_int, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _i32p, _dp, _dp, C.c_int, _dp]
     _lib = L
     return L
 
@@ -316,6 +319,137 @@ def rhat_series(series, nrows=None, sequences=False, out=None, device=-1):
     p = [_d(v) for v in o] + [None] * (6 - len(o))
     _chk(load().ptm_rhat_series(device, _d(a), n, ns, nf, int(nrows), *p))
     return o
+
+
+SEAM_SIGMAS = 6.0   # a wrapped dimension's Gaussian target keeps this many sigma inside its domain (proposal_invariance)
+KL_FLOOR = 5    # test_proposal.hh:402: the floor of the distances is element KL_FLOOR + 1 of the sorted distances within P
+
+
+def _sets2(a):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("a sample set must be an array [n, dim]")
+    return a
+
+
+def nn_dist2(P, Q=None, wrapped=None, xmin=None, xmax=None, out=None, device=-1):
+    """for every point of P [nP, dim] the squared distance to its nearest point of Q [nQ, dim], exactly, on the device; Q=None: to the
+    nearest OTHER point of P itself (a duplicate gives 0).  wrapped [dim]: the dimensions that wrap around [xmin, xmax) -- there the
+    distance is the smaller of |b - a| and the same with both points shifted by half the domain and wrapped (state::dist2).
+    The bits are those of the facade's kl_estimator (ptm_nn_dist2).  out: the array to fill (it keeps its contents when the call fails)."""
+    p = _sets2(P)
+    q = p if Q is None else _sets2(Q)
+    if q.shape[1] != p.shape[1]:
+        raise ValueError("P and Q differ in dimension")
+    dim = p.shape[1]
+    w = lo = hi = None
+    if wrapped is not None:
+        w = np.ascontiguousarray(wrapped, dtype=np.int32)
+        lo, hi = (np.ascontiguousarray(np.zeros(dim) if v is None else v, dtype=np.float64) for v in (xmin, xmax))
+        if w.size != dim or lo.size != dim or hi.size != dim:
+            raise ValueError("wrapped, xmin and xmax must have one entry per dimension")
+    o = np.empty(p.shape[0]) if out is None else out
+    _chk(load().ptm_nn_dist2(device, _d(p), p.shape[0], _d(q), q.shape[0], dim, None if w is None else w.ctypes.data_as(_i32p),
+                             None if w is None else _d(lo), None if w is None else _d(hi), 1 if Q is None else 0, _d(o)))
+    return o
+
+
+def _c_log(v):
+    """the C library's logarithm with its IEEE edges (numpy's own vectorised logarithm may round differently)"""
+    import math
+    v = float(v)
+    if v != v or v < 0:
+        return math.nan
+    return -math.inf if v == 0 else (math.inf if v == math.inf else math.log(v))
+
+
+def kl_from_distances(r1sqs, s1sqs, dim, M):
+    """the k-NN KL estimate from the distances within P and to the M points of Q, in the estimator's order (test_proposal.hh:400-421)"""
+    import math
+    r, s = np.array(r1sqs, dtype=np.float64), np.array(s1sqs, dtype=np.float64)
+    if r.size < KL_FLOOR + 2 or M < 1:
+        raise ValueError("the KL estimator needs at least %d samples of P and 1 of Q" % (KL_FLOOR + 2))
+    floor = np.sort(r)[KL_FLOOR + 1]
+    r, s = np.where(r < floor, floor, r), np.where(s < floor, floor, s)
+    with np.errstate(all="ignore"):
+        ratio = r / s
+    result, N = 0.0, float(r.size)
+    for v in ratio:
+        result = result + -_c_log(v)
+    return result * ((0.5 * float(dim)) / N) + math.log(int(M) / (N - 1.0))
+
+
+def kl_divergence(P, Q, wrapped=None, xmin=None, xmax=None, device=-1):
+    """the k-NN Kullback-Leibler estimate of Perez-Cruz (k = 1) of the sets P from Q, as the reference's proposal test computes it with
+    exact neighbours: the two nearest-neighbour searches run on the device (nn_dist2), floor and sum here"""
+    p, q = _sets2(P), _sets2(Q)
+    if p.shape[0] < KL_FLOOR + 2 or q.shape[0] < 1:
+        raise ValueError("the KL estimator needs at least %d samples of P and 1 of Q" % (KL_FLOOR + 2))
+    r = nn_dist2(p, None, wrapped, xmin, xmax, device=device)
+    s = nn_dist2(p, q, wrapped, xmin, xmax, device=device)
+    return kl_from_distances(r, s, p.shape[1], q.shape[0])
+
+
+def _gauss_jordan(a):
+    """(inverse, determinant) by Gauss-Jordan elimination with partial pivoting, as the facade's kl_estimator::invert"""
+    a = np.array(a, dtype=np.float64)
+    n = a.shape[0]
+    inv, det = np.eye(n), 1.0
+    for c in range(n):
+        piv = c + int(np.argmax(np.abs(a[c:, c])))
+        if a[piv, c] == 0.0:
+            return None, 0.0
+        if piv != c:
+            a[[piv, c]], inv[[piv, c]] = a[[c, piv]], inv[[c, piv]]
+            det = -det
+        d = a[c, c]
+        det = det * d
+        a[c], inv[c] = a[c] / d, inv[c] / d
+        f = a[:, c].copy()
+        f[c] = 0.0
+        a, inv = a - f[:, None] * a[c][None, :], inv - f[:, None] * inv[c][None, :]
+    return inv, det
+
+
+def fake_kl_divergence(P, Q):
+    """the Gaussian "fake KL" of the reference's proposal test, from the two sets' means and covariances (test_proposal.hh:466-502, the
+    unbiasing factor with the size of P as written there).  O(N dim^2): it stays on the host."""
+    p, q = _sets2(P), _sets2(Q)
+    dim, n = p.shape[1], p.shape[0]
+    if n < 2 or q.shape[0] < 2 or q.shape[1] != dim:
+        raise ValueError("the fake KL needs two sets of at least 2 samples in the same dimension")
+
+    def moments(x):
+        mean = np.add.accumulate(x, axis=0)[-1] / float(x.shape[0])
+        d = x - mean
+        cov = np.zeros((dim, dim))
+        for lo in range(0, x.shape[0], 4096):   # (sequential in sample order, a block of outer products at a time)
+            blk = d[lo:lo + 4096]
+            cov = np.add.accumulate(np.concatenate([cov[None], blk[:, :, None] * blk[:, None, :]]), axis=0)[-1]
+        return mean, cov / (float(x.shape[0]) - 1.0)
+
+    mean_p, cov_p = moments(p)
+    mean_q, cov_q = moments(q)
+    factor = (n - dim - 2.0) / (n - 1.0)
+    inv, _ = _gauss_jordan(cov_q)
+    if inv is None:
+        return float("nan")
+    inv = inv * factor
+    prod = np.zeros((dim, dim))
+    for k in range(dim):
+        prod = prod + cov_p[:, k][:, None] * inv[k][None, :]
+    trace = 0.0
+    for i in range(dim):
+        trace = trace + prod[i, i]
+    _, det = _gauss_jordan(prod / factor)
+    dmu = mean_p - mean_q
+    row = np.zeros(dim)
+    for j in range(dim):
+        row = row + inv[:, j] * dmu[j]
+    quad = 0.0
+    for i in range(dim):
+        quad = quad + dmu[i] * row[i]
+    return 0.5 * (((-dim + trace) + -_c_log(det)) + (quad - (dim + trace) / n))
 
 
 class DeviceBuffer:
@@ -1017,3 +1151,81 @@ class Engine:
     def step_kernel_name(self):
         """what step() launches (ptm_step_kernel_name)"""
         return self.L.ptm_step_kernel_name(self.h).decode()
+
+
+def proposal_verdict(redraws, alt):
+    """how the reference's proposal test judges a statistic (test_proposal.hh:311-343): the redraw values by magnitude, Ncut =
+    int(sqrt(ntry)), the cut half way between sorted entries ntry - Ncut and ntry - Ncut - 1 (0 with one redraw):
+    (cut, "PASS" if alt < cut else "FAIL")"""
+    import math
+    d = np.sort(np.abs(np.asarray(redraws, dtype=np.float64)))
+    ntry = d.size
+    ncut = int(math.sqrt(ntry))
+    cut = float((d[ntry - ncut] + d[ntry - ncut - 1]) / 2.0) if ntry > 1 else 0.0
+    return cut, "PASS" if alt < cut else "FAIL"
+
+
+def proposal_invariance(dim, centre, sigma, install, nsamp=10000, ncyc=5, ntry=10, bounds=None, seed=0x5EED0001, min_accept=0.0, device=-1):
+    """Does a proposal leave a known target invariant?  The reference's test_proposal::test (test_proposal.hh:202-348) on the engine:
+    nsamp samples of the target -- a Gaussian per dimension (centre, sigma) on the space `bounds` = (lower types, upper types, xmin,
+    xmax) or None, samples outside a limit redrawn -- are the walkers of a one-rung engine whose prior is that target over a
+    constant likelihood; install(engine) sets the proposal under test (set_proposals, set_proposal_device, set_proposal_callback ...);
+    sweeps are made until ncyc * nsamp moves have been accepted (after 2000 sweeps with under 1% of them the goal is halved, or the
+    test gives up below min_accept: None is returned).  In a wrapped dimension the target must keep SEAM_SIGMAS sigma inside the domain
+    (ValueError otherwise): the engine wraps a Gaussian's draws but evaluates the plain Gaussian, where the reference sums the images.  The transformed set is then compared with the target set and with a fresh
+    draw by the k-NN KL estimate (exact neighbours, on the device) and the Gaussian fake KL, both calibrated on ntry and 30 ntry redraws.
+    Returns a dict: kl, kl_x, fake_kl, fake_kl_x (transformed against the start set, and the other way round), alt_kl, alt_kl_x,
+    alt_fake_kl, alt_fake_kl_x (against a fresh draw), kl_redraws, fake_kl_redraws, kl_cut, fake_kl_cut, kl_verdict, fake_kl_verdict,
+    acceptance (of the last sweep), sweeps, ncyc, target, transformed."""
+    if bounds is not None:   # a wrapped dimension: the engine wraps the Gaussian's draws but evaluates the plain Gaussian (no periodic sum)
+        c, sg = np.asarray(centre, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+        for d in range(dim):
+            if bounds[0][d] == BOUND_WRAP and bounds[1][d] == BOUND_WRAP and (c[d] - SEAM_SIGMAS * sg[d] < bounds[2][d] or c[d] + SEAM_SIGMAS * sg[d] > bounds[3][d]):
+                raise ValueError("the target comes within %g sigma of the seam of wrapped dimension %d: its samples wrap around, the density the steps "
+                                 "aim at does not; move the centre inside or shrink sigma" % (SEAM_SIGMAS, d))
+    eng = Engine(dim, 1, nsamp, seed=seed, min_prior=-1e300, device=device)   # (min_prior: the prior gate never acts)
+    try:
+        wrap = None
+        if bounds is not None:
+            eng.set_bounds(*bounds)
+            lo_t, hi_t, xmin, xmax = (np.asarray(v) for v in bounds)
+            wrap = ((lo_t == BOUND_WRAP) & (hi_t == BOUND_WRAP)).astype(np.int32), xmin.astype(np.float64), xmax.astype(np.float64)
+            if not wrap[0].any():
+                wrap = None
+        eng.set_prior(["gauss"] * dim, centre, sigma)
+        eng.set_target_gaussian(np.zeros((dim, dim)), 0.0)
+        eng.set_ladder([1.0])
+        install(eng)
+        eng.init_from_prior()
+        target = eng.states().reshape(nsamp, dim).copy()
+        goal, cum, icyc, sweeps, rate = int(ncyc * nsamp), 0, 1, 0, 0.0
+        accepted = eng.counter_sums()[1]
+        while cum < goal:
+            eng.sweep(1)
+            now = eng.counter_sums()[1]
+            step, accepted = now - accepted, now
+            cum, sweeps, rate = cum + step, sweeps + 1, step / nsamp
+            if icyc == 2000 and cum < goal * 0.01:
+                ncyc = ncyc / 2.0
+                if rate < min_accept:
+                    return None
+                goal, icyc, cum = int(ncyc * nsamp), 0, 0
+            icyc += 1
+        transformed = eng.states().reshape(nsamp, dim).copy()
+        fntry = 30 * ntry
+        redraw = lambda k: eng.draw_prior_rows(1 + k, 1)[0].reshape(nsamp, dim)
+        w = wrap or (None, None, None)
+        kl = lambda a, b: kl_divergence(a, b, *w, device=device)
+        out = dict(kl=kl(transformed, target), kl_x=kl(target, transformed), fake_kl=fake_kl_divergence(transformed, target),
+                   fake_kl_x=fake_kl_divergence(target, transformed))
+        out["kl_redraws"] = np.array([kl(redraw(k), target) for k in range(ntry)])
+        out["fake_kl_redraws"] = np.array([fake_kl_divergence(redraw(ntry + k), target) for k in range(fntry)])
+        alt = redraw(ntry + fntry)
+        out.update(alt_kl=kl(transformed, alt), alt_kl_x=kl(alt, transformed), alt_fake_kl=fake_kl_divergence(transformed, alt),
+                   alt_fake_kl_x=fake_kl_divergence(alt, transformed))
+        out["kl_cut"], out["kl_verdict"] = proposal_verdict(out["kl_redraws"], out["alt_kl"])
+        out["fake_kl_cut"], out["fake_kl_verdict"] = proposal_verdict(out["fake_kl_redraws"], out["alt_fake_kl"])
+        out.update(acceptance=rate, sweeps=sweeps, ncyc=ncyc, target=target, transformed=transformed)
+        return out
+    finally:
+        eng.close()

@@ -37,6 +37,7 @@
 #include <map>
 #include <memory>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <valarray>
@@ -1872,6 +1873,222 @@ class rhat_estimator {
   }
 };
 
+// ---- the statistics of the proposal test (test_proposal.hh:350-502, 592-644) ------------------------------------------------------
+// kl_estimator: the k-NN Kullback-Leibler estimator of Perez-Cruz with k = 1 and the Gaussian "fake KL" from means and covariances,
+// on plain rows (sample i of a set at x + i * dim), as test_proposal states them with approx_nn = false.
+//   * dist2 is state::dist2 (states.cc:207-233): per dimension diff = |b - a|; in a wrapped dimension also the alternative, both
+//     points shifted down by half the domain and wrap-enforced (boundary::enforce above), the smaller of the two; diff * diff is
+//     summed in dimension order, the product rounded before it is added;
+//   * all_nnd2: for every point the nearest OTHER INDEX of its own set (a duplicate gives 0); one_nnd2: the nearest point of Q;
+//   * kl: r = all_nnd2(P), s[i] = one_nnd2(P[i], Q); the floor is element kfloor + 1 = 6 of the sorted r and is applied to both;
+//     result = sum_i -log(r_i / s_i) in index order, result *= (0.5 * dim) / N, result += log(M / (N - 1.0)).  N < 7 or M < 1 is
+//     refused (the reference reads out of bounds there);
+//   * fake_kl: means and covariances sequentially in sample order, divided by N - 1; the unbiasing factor uses nQ = the size of P,
+//     as the reference writes it.  The inverse and the determinant are Gauss-Jordan with partial pivoting (the reference uses Eigen's:
+//     the last digits differ).
+// The engine's ptm_nn_dist2 runs the two searches on the device, every pair's sum in the same order: same bits (combine() is the rest).
+class kl_estimator {
+ public:
+  static const int kfloor = 5;
+  struct result {
+    double value;
+    std::vector<double> r1sqs, s1sqs;   // [N] the distances within P and to Q, before the floor
+  };
+  // space: null, or the space whose wrapped dimensions count
+  static double dist2(const double* a, const double* b, int dim, const stateSpace* space = nullptr) {
+    double result = 0;
+    for (int i = 0; i < dim; i++) {
+      double xa = a[i], xb = b[i];
+      double diff = std::fabs(xb - xa);
+      if (space && space->get_bound(i).isWrapped()) {
+        const boundary bd = space->get_bound(i);
+        double xmin, xmax;
+        bd.getDomainLimits(xmin, xmax);
+        const double halfwrap = (xmax - xmin) / 2;
+        xa -= halfwrap;
+        xb -= halfwrap;
+        bd.enforce(xa);
+        bd.enforce(xb);
+        const double altdiff = std::fabs(xb - xa);
+        if (altdiff < diff) diff = altdiff;
+      }
+      volatile double dd = diff * diff;   // (the product rounded before the sum, whatever the compiler's contraction rule)
+      result += dd;
+    }
+    return result;
+  }
+  static std::vector<double> all_nnd2(const double* P, long long N, int dim, const stateSpace* space = nullptr) {   // test_proposal.hh:442-464
+    std::vector<double> nnd2((size_t)N, -1.0);
+    for (long long i = 0; i < N; i++)
+      for (long long j = i + 1; j < N; j++) {
+        const double d2 = dist2(P + i * dim, P + j * dim, dim, space);
+        if (nnd2[(size_t)i] < 0 || nnd2[(size_t)i] > d2) nnd2[(size_t)i] = d2;
+        if (nnd2[(size_t)j] < 0 || nnd2[(size_t)j] > d2) nnd2[(size_t)j] = d2;
+      }
+    return nnd2;
+  }
+  static double one_nnd2(const double* p, const double* Q, long long M, int dim, const stateSpace* space = nullptr) {   // test_proposal.hh:424-441
+    double nnd2 = -1;
+    for (long long i = 0; i < M; i++) {
+      const double d2 = dist2(Q + i * dim, p, dim, space);
+      if (nnd2 < 0 || nnd2 > d2) nnd2 = d2;
+    }
+    return nnd2;
+  }
+  static void check_sizes(long long N, long long M) {
+    if (N < kfloor + 2 || M < 1) throw std::invalid_argument("kl_estimator: needs at least 7 samples of P and 1 of Q");
+  }
+  // test_proposal.hh:400-421 from the two distance arrays (taken by value: the floor is applied to the copies)
+  static double combine(std::vector<double> r1sqs, std::vector<double> s1sqs, int dim_, long long M) {
+    const double N = (double)r1sqs.size();
+    check_sizes((long long)r1sqs.size(), M);
+    std::vector<double> dists = r1sqs;
+    std::sort(dists.begin(), dists.end());
+    const double floor = dists[kfloor + 1];
+    for (auto& d2 : r1sqs) if (d2 < floor) d2 = floor;
+    for (auto& d2 : s1sqs) if (d2 < floor) d2 = floor;
+    double result = 0;
+    for (size_t i = 0; i < r1sqs.size(); i++) result += -std::log(r1sqs[i] / s1sqs[i]);
+    const double dim = dim_;
+    volatile double scaled = result * ((0.5 * dim) / N);
+    result = scaled;
+    result += std::log((int)M / (N - 1.0));
+    return result;
+  }
+  static result kl(const double* P, long long N, const double* Q, long long M, int dim, const stateSpace* space = nullptr) {
+    check_sizes(N, M);
+    result r;
+    r.r1sqs = all_nnd2(P, N, dim, space);
+    r.s1sqs.resize((size_t)N);
+    for (long long i = 0; i < N; i++) r.s1sqs[(size_t)i] = one_nnd2(P + i * dim, Q, M, dim, space);
+    r.value = combine(r.r1sqs, r.s1sqs, dim, M);
+    return r;
+  }
+  // test_proposal.hh:592-644: mean[dim] and cov[dim * dim]
+  static void sample_cov(const double* X, long long N, int dim, std::vector<double>& mean, std::vector<double>& cov) {
+    mean.assign((size_t)dim, 0.0);
+    cov.assign((size_t)dim * dim, 0.0);
+    for (long long s = 0; s < N; s++)
+      for (int j = 0; j < dim; j++) mean[(size_t)j] += X[s * dim + j];
+    for (auto& x : mean) x /= (double)(size_t)N;
+    for (long long s = 0; s < N; s++)
+      for (int j = 0; j < dim; j++) {
+        const double jdiff = X[s * dim + j] - mean[(size_t)j];
+        volatile double jj = jdiff * jdiff;
+        cov[(size_t)j * dim + j] += jj;
+        for (int i = j + 1; i < dim; i++) {
+          const double idiff = X[s * dim + i] - mean[(size_t)i];
+          volatile double val = idiff * jdiff;
+          cov[(size_t)i * dim + j] += val;
+          cov[(size_t)j * dim + i] += val;
+        }
+      }
+    for (auto& x : cov) x /= ((double)(size_t)N - 1.0);
+  }
+  // inverse [n * n] and determinant of a [n * n] by Gauss-Jordan elimination with partial pivoting; false: singular
+  static bool invert(std::vector<double> a, int n, std::vector<double>& inv, double& det) {
+    inv.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; i++) inv[(size_t)i * n + i] = 1.0;
+    det = 1.0;
+    for (int c = 0; c < n; c++) {
+      int piv = c;
+      for (int r = c + 1; r < n; r++)
+        if (std::fabs(a[(size_t)r * n + c]) > std::fabs(a[(size_t)piv * n + c])) piv = r;
+      if (a[(size_t)piv * n + c] == 0.0) { det = 0.0; return false; }
+      if (piv != c) {
+        for (int k = 0; k < n; k++) { std::swap(a[(size_t)piv * n + k], a[(size_t)c * n + k]); std::swap(inv[(size_t)piv * n + k], inv[(size_t)c * n + k]); }
+        det = -det;
+      }
+      const double d = a[(size_t)c * n + c];
+      det *= d;
+      for (int k = 0; k < n; k++) { a[(size_t)c * n + k] /= d; inv[(size_t)c * n + k] /= d; }
+      for (int r = 0; r < n; r++) {
+        if (r == c) continue;
+        const double f = a[(size_t)r * n + c];
+        if (f == 0.0) continue;
+        for (int k = 0; k < n; k++) {
+          volatile double fa = f * a[(size_t)c * n + k], fi = f * inv[(size_t)c * n + k];
+          a[(size_t)r * n + k] -= fa;
+          inv[(size_t)r * n + k] -= fi;
+        }
+      }
+    }
+    return true;
+  }
+  // test_proposal.hh:466-502
+  static double fake_kl(const double* P, long long N, const double* Q, long long M, int dim) {
+    if (N < 2 || M < 2) throw std::invalid_argument("kl_estimator::fake_kl: needs at least 2 samples of each set");
+    std::vector<double> meanP, meanQ, covP, covQ, inv, prod((size_t)dim * dim, 0.0), unscaled((size_t)dim * dim), tmp;
+    sample_cov(P, N, dim, meanP, covP);
+    sample_cov(Q, M, dim, meanQ, covQ);
+    const int nQ = (int)N;   // (as the reference writes it: samplesP.size())
+    const double unbiasing_factor = (nQ - dim - 2.0) / (nQ - 1.0);
+    double det = 0;
+    if (!invert(covQ, dim, inv, det)) return NAN;
+    for (auto& x : inv) x *= unbiasing_factor;
+    auto at = [dim](int i, int j) { return (size_t)i * dim + j; };
+    double trace = 0;
+    for (int i = 0; i < dim; i++)
+      for (int j = 0; j < dim; j++) {
+        double s = 0;
+        for (int k = 0; k < dim; k++) { volatile double t = covP[at(i, k)] * inv[at(k, j)]; s += t; }
+        prod[at(i, j)] = s;
+        unscaled[at(i, j)] = s / unbiasing_factor;
+      }
+    for (int i = 0; i < dim; i++) trace += prod[at(i, i)];
+    double result = 0;
+    result += -dim + trace;
+    double det2 = 0;
+    invert(unscaled, dim, tmp, det2);
+    result += -std::log(det2);
+    double quad = 0;
+    for (int i = 0; i < dim; i++) {
+      double s = 0;
+      for (int j = 0; j < dim; j++) { volatile double t = inv[at(i, j)] * (meanP[(size_t)j] - meanQ[(size_t)j]); s += t; }
+      volatile double t = (meanP[(size_t)i] - meanQ[(size_t)i]) * s;
+      quad += t;
+    }
+    result += quad - (dim + trace) / nQ;
+    return 0.5 * result;
+  }
+};
+
+// kl_verdict: how test_proposal::test judges a statistic against its redraws (test_proposal.hh:311-343) -- the redraw values by
+// magnitude, Ncut = int(sqrt(ntry)), the cut half way between sorted entries ntry - Ncut and ntry - Ncut - 1 (none, 0, with one
+// redraw), and the lines it prints; name is "KL" or "fKL" (the line after FAIL says "KL value" for both, as written there).
+class kl_verdict {
+ public:
+  int Ncut;
+  double cut_frac, cut;
+  bool pass;
+  kl_verdict(std::vector<double> diffs, double alt) {
+    const int ntry = (int)diffs.size();
+    for (auto& d : diffs) d = std::fabs(d);
+    std::sort(diffs.begin(), diffs.end());
+    Ncut = (int)std::sqrt((double)ntry);
+    cut = 0;
+    cut_frac = Ncut * 1.0 / ntry;
+    if (ntry > 1) cut = (diffs[(size_t)(ntry - Ncut)] + diffs[(size_t)(ntry - Ncut - 1)]) / 2.0;
+    have_cut = ntry > 1;
+    pass = alt < cut;
+  }
+  std::string lines(const std::string& name, double transformed, double transformedX, double alt, double altX, double ncyc) const {
+    std::ostringstream os;
+    if (have_cut) os << "\nEstimate that only " << cut_frac * 100 << "% of " << name << "diff measurements are likely to exceed " << cut << " for matching distributions.\n";
+    os << "Transformed " << name << "div=" << transformed << " <-> " << transformedX << "\n";
+    os << "Alt-transformed " << name << "div=" << alt << " <-> " << altX << "\n";
+    if (alt - transformed > std::fabs(cut))
+      os << "When 'Transformed' is signficantly less than 'alt-Transformed' it may indicate that the effect of the proposal (after ncyc=" << ncyc
+         << " applications) is too small to measure at this level.\n";
+    if (pass) os << "PASS\n";
+    else os << "FAIL\nKL value is " << alt / cut << " times the stated threshold.\n";
+    return os.str();
+  }
+
+ private:
+  bool have_cut;
+};
+
 // evidence_records: what the statistics block keeps of the totals (chain.cc:1603-1675) -- the pyramid total_evidence_records (level 0
 // every total from the second epoch on; level i the average of the last two of level i-1 whenever evidence_count is a multiple of
 // 2^i), the "recent ev analysis" over the newest 2 (Ndim - j) + 1 entries of each level but the top one, and the smallest standard
@@ -3502,6 +3719,254 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
 };
 
 // ---- bayesian.hh:795-821 / ptmcmc.hh: the driver ------------------------------------------------------------------------------
+// ---- the proposal test (test_proposal.hh:51-348) ----------------------------------------------------------------------------------
+// proposal_tester: does a proposal leave a known target invariant?  N samples of the target are moved by Metropolis-Hastings steps of
+// the proposal until ncyc * N moves have been accepted; the transformed set is then compared with the start set and with a fresh draw
+// by kl_estimator's two statistics, each calibrated on redraws of the target (kl_verdict).  The transform is what the engine does: the
+// samples are the Nsamp replicas of a one-rung ladder whose prior is the target -- a per-dimension product such as
+// gaussian_dist_product on the tested space -- over a constant likelihood, with the prior gate out of the way; the ladder installs the
+// proposal as it does for a run (Gaussian sets natively, a device_proposal through ptm_set_proposal_device, anything else through
+// the host-proposal callback), draws the samples and the redraws (redrawn until valid: the reference's rejection loop, :90-113) and
+// counts the acceptances.  The KL estimate always uses EXACT neighbours, searched on the device (ptm_nn_dist2: the host estimator's
+// bits; PTM_HOST_KL=1 and more than 128 dimensions: kl_estimator itself).  hastings_err, the reference's way to force a failure, is
+// added where the host adds the ratio: it needs a host-side proposal.  A differential_evolution is skipped: the reference hands it an
+// empty chain and cannot draw from it.  The proposal's own intrinsic test (involutions) is out of scope.
+class proposal_tester {
+  proposal_distribution* proposal;
+  sampleable_probability_function* target_dist;
+  bool loop;
+  std::string path;
+  uint64_t seed;
+
+  // the proposal with hastings_err added to its ratio (host side only: it describes nothing to the device)
+  class with_hastings_err : public proposal_distribution {
+    proposal_distribution* inner;
+    double err;
+
+   public:
+    with_hastings_err(const proposal_distribution& p, double err) : inner(p.clone()), err(err) {}
+    with_hastings_err(const with_hastings_err& o) : proposal_distribution(o), inner(o.inner->clone()), err(o.err) {}
+    ~with_hastings_err() { delete inner; }
+    double log_hastings_ratio() override { return inner->log_hastings_ratio() + err; }
+    void set_chain(chain* c) override { inner->set_chain(c); }
+    state draw(state& s, chain* caller) override { return inner->draw(s, caller); }
+    bool is_ready() override { return inner->is_ready(); }
+    proposal_distribution* clone() const override { return new with_hastings_err(*this); }
+    std::string show() override { return inner->show(); }
+    int type() override { return inner->type(); }
+    bool support_mixing() override { return inner->support_mixing(); }
+    void accept() override { inner->accept(); }
+    void reject() override { inner->reject(); }
+    std::string report(int style = 0) override { return inner->report(style); }
+  };
+  struct constant_likelihood : public gaussian_likelihood {
+    explicit constant_likelihood(const stateSpace* sp) : gaussian_likelihood(std::vector<double>((size_t)sp->size() * sp->size(), 0.0), 0.0) {
+      nativeSpace = *sp;
+      space = &nativeSpace;
+    }
+  };
+  static bool host_kl() {
+    static const bool on = [] { const char* v = getenv("PTM_HOST_KL"); return v && *v && *v != '0'; }();   // (A/B: keep the host estimator)
+    return on;
+  }
+
+ public:
+  // A Gaussian in a WRAPPED dimension: the engine draws it and wraps the draw, but evaluates the plain Gaussian (it has no periodic sum,
+  // the reference's wrap_probability, probability_function.cc:57-78).  The samples and the density the Metropolis-Hastings steps aim at
+  // are the same distribution only while no mass reaches the seam: the target must keep seam_sigmas sigma (2e-9 of its mass beyond)
+  // inside the domain on both sides.  test() refuses a target that does not, rather than report a correct proposal FAIL.
+  static double seam_sigmas() { return 6.0; }
+  // -1, or the first wrapped Gaussian dimension of `target` that comes nearer to its seam
+  static int dimension_near_seam(const sampleable_probability_function& target) {
+    std::vector<int> types;
+    std::vector<double> c, h;
+    const stateSpace* sp = target.get_space();
+    if (!sp || !target.describe(types, c, h)) return -1;
+    for (int d = 0; d < (int)types.size() && d < sp->size(); d++) {
+      if (types[(size_t)d] != mixed_dist_product::gaussian || !sp->get_bound(d).isWrapped()) continue;
+      double xmin, xmax;
+      sp->get_bound(d).getDomainLimits(xmin, xmax);
+      if (c[(size_t)d] - seam_sigmas() * h[(size_t)d] < xmin || c[(size_t)d] + seam_sigmas() * h[(size_t)d] > xmax) return d;
+    }
+    return -1;
+  }
+  proposal_tester(proposal_distribution& proposalref, sampleable_probability_function& target, bool loop = false, std::string path_ = "",
+                  std::vector<int> index = std::vector<int>(), uint64_t seed = 0x5EED0001ull)
+      : proposal(&proposalref), target_dist(&target), loop(loop), path(path_), seed(seed) {
+    if (path != "") {   // test_proposal.hh:69-76
+      if (path.back() == '/') path = path + "test_prop";
+      if (index.size() > 0) path = path + "_" + std::to_string(index[0]);
+      for (size_t i = 1; i < index.size(); i++) path += "-" + std::to_string(index[i]);
+      std::cout << "path='" << path << "'" << std::endl;
+    }
+    while (index.size() > 0) {   // a set and an index: the member (and so on down the index)
+      proposal_distribution_set* set = dynamic_cast<proposal_distribution_set*>(proposal);
+      if (!set) break;
+      proposal = set->members()[(size_t)index[0]];
+      index.erase(index.begin());
+    }
+  }
+  void write_samples(const std::vector<double>& X, int dim, const std::string& tag) const {
+    if (path == "") return;
+    const std::string file = path + "_" + tag + ".dat";
+    std::cout << "Will write to " << file << std::endl;
+    std::ofstream out(file);
+    for (size_t i = 0; i * dim < X.size(); i++) out << state::from_engine(target_dist->get_space(), X.data() + i * dim, dim).get_string() << std::endl;
+  }
+  // test_proposal.hh:604-615: the variances, the means in out_mean
+  static std::vector<double> sample_var(const std::vector<double>& X, int dim, std::vector<double>& out_mean) {
+    const size_t N = X.size() / dim;
+    out_mean.assign((size_t)dim, 0.0);
+    for (size_t i = 0; i < N; i++) for (int j = 0; j < dim; j++) out_mean[(size_t)j] += X[i * dim + j];
+    for (auto& x : out_mean) x /= N;
+    std::vector<double> sum((size_t)dim, 0.0);
+    for (size_t i = 0; i < N; i++)
+      for (int j = 0; j < dim; j++) {
+        const double diff = X[i * dim + j] - out_mean[(size_t)j];
+        sum[(size_t)j] += diff * diff;
+      }
+    for (auto& x : sum) x /= (N - 1.0);
+    return sum;
+  }
+  // KL_divergence(P, Q, approx_nn = false), the two searches on the device where it serves
+  double kl(const std::vector<double>& P, const std::vector<double>& Q, int dim) const {
+    const stateSpace* sp = target_dist->get_space();
+    const long long N = (long long)(P.size() / dim), M = (long long)(Q.size() / dim);
+    if (host_kl() || dim > 128) return kl_estimator::kl(P.data(), N, Q.data(), M, dim, sp).value;
+    kl_estimator::check_sizes(N, M);
+    std::vector<int32_t> wrapped((size_t)dim, 0);
+    std::vector<double> xmin((size_t)dim, 0.0), xmax((size_t)dim, 0.0), r((size_t)N), s((size_t)N);
+    for (int d = 0; sp && d < dim; d++)
+      if (sp->get_bound(d).isWrapped()) { wrapped[(size_t)d] = 1; sp->get_bound(d).getDomainLimits(xmin[(size_t)d], xmax[(size_t)d]); }
+    ptm_check(ptm_nn_dist2(-1, P.data(), N, P.data(), N, dim, wrapped.data(), xmin.data(), xmax.data(), 1, r.data()), "proposal_tester (ptm_nn_dist2)");
+    ptm_check(ptm_nn_dist2(-1, P.data(), N, Q.data(), M, dim, wrapped.data(), xmin.data(), xmax.data(), 0, s.data()), "proposal_tester (ptm_nn_dist2)");
+    return kl_estimator::combine(r, s, dim, M);
+  }
+  bool test(int Nsamp = 10000, double ncyc = 5, int ntry = 10, double hastings_err = 0, double min_accept = 0) {
+    std::cout << "\n\nTesting proposal: " << proposal->show() << std::endl;
+    std::cout << "ncyc=" << ncyc << std::endl;
+    if (loop) {   // test_proposal.hh:206-225: every member of a set in turn
+      proposal_distribution_set* set = dynamic_cast<proposal_distribution_set*>(proposal);
+      if (set) {
+        const std::vector<proposal_distribution*> members = set->members();
+        const int n = (int)members.size();
+        std::cout << n << " members in proposal set" << std::endl;
+        for (int i = 0; i < n; i++) {
+          std::cout << "Preparing and testing member " << i + 1 << " of " << n << std::endl;
+          std::string subpath = path;
+          if (path != "") subpath = subpath + "-" + std::to_string(i);
+          std::cout << "subpath='" << subpath << "'" << std::endl;
+          proposal_tester subtest(*members[(size_t)i], *target_dist, true, subpath, std::vector<int>(), seed);
+          if (!subtest.test(Nsamp, ncyc, ntry, hastings_err, min_accept)) return false;
+        }
+        return true;
+      }
+    }
+    if (dynamic_cast<differential_evolution*>(proposal)) {
+      std::cout << "Skipping differential evolution: it draws from a chain's history, and the test has none to give it." << std::endl;
+      return true;
+    }
+    const int dim = target_dist->getDim();
+    const int near = dimension_near_seam(*target_dist);
+    if (near >= 0) {
+      std::cout << "The test distribution comes within " << seam_sigmas() << " sigma of the seam of wrapped dimension " << near
+                << ": its samples wrap around, the density the steps aim at does not.  Not tested; move the centre inside or shrink sigma." << std::endl;
+      return false;
+    }
+    std::unique_ptr<proposal_distribution> wrapped_prop;
+    proposal_distribution* under_test = proposal;
+    if (hastings_err != 0) {
+      int kind = 0;
+      double odf = 0;
+      std::vector<double> f;
+      if (device_proposal::taken_by_device(proposal) || proposal->device_describe(dim, kind, f, odf)) {
+        std::cout << "hastings_err is added to the ratio on the host: it needs a host-side proposal, and this one is drawn on the device." << std::endl;
+        return false;
+      }
+      wrapped_prop.reset(new with_hastings_err(*proposal, hastings_err));
+      under_test = wrapped_prop.get();
+    }
+    // the test engine: one rung, Nsamp replicas, the target as the prior over a constant likelihood, no prior gate
+    constant_likelihood like(target_dist->get_space());
+    parallel_tempering_chains ptc(1, 1.0, 0.0, 1, false, false, -1e300);
+    ptc.set_replicas(Nsamp);
+    ptc.initialize(&like, target_dist, 1, seed);
+    ptc.set_proposal(*under_test);
+    ptm_engine* eng = ptc.engine();
+    const size_t NX = (size_t)Nsamp * dim;
+    std::vector<double> target_samples(NX), transformed(NX), alt_samples(NX), ll((size_t)Nsamp), lp((size_t)Nsamp);
+    ptm_check(ptm_get_states(eng, target_samples.data()), "proposal_tester");
+    write_samples(target_samples, dim, "target");
+    int redraws = 0;   // draw 0 of every chain is the target sample, draw k > 0 the k-th redraw
+    auto redraw = [&]() { ptm_check(ptm_draw_prior_rows(eng, ++redraws, 1, alt_samples.data(), ll.data(), lp.data()), "proposal_tester (redraw)"); };
+    int64_t tries = 0, acc0 = 0, acc1 = 0;
+    int Naccept_cum = 0, Ngoal = (int)(ncyc * Nsamp), icyc = 1, Naccept_last = 0;
+    std::cout << "Applying transform:" << std::endl;
+    ptm_check(ptm_get_counter_sums(eng, &tries, &acc0), "proposal_tester");
+    while (Naccept_cum < Ngoal) {
+      ptc.step_n(1);
+      eng = ptc.engine();
+      ptm_check(ptm_get_counter_sums(eng, &tries, &acc1), "proposal_tester");
+      const int Naccept = (int)(acc1 - acc0);
+      acc0 = acc1;
+      Naccept_cum += Naccept;
+      Naccept_last = Naccept;
+      if (icyc % int(ncyc + 1) == 0) std::cout << 100.0 * Naccept / Nsamp << "% accepted,  " << 100.0 * Naccept_cum / Ngoal << " percent done." << std::endl;
+      if (icyc == 2000 && Naccept_cum < Ngoal * 0.01) {   // not sampling fast enough: halve the goal
+        ncyc = ncyc / 2.0;
+        if (Naccept * 1.0 / Nsamp < min_accept) {
+          std::cout << "Acceptance rate too low. Giving up." << std::endl;
+          return false;
+        }
+        std::cout << "Sampling poorly.  Reducing to ncyc=" << ncyc << std::endl;
+        Ngoal = (int)(ncyc * Nsamp);
+        icyc = 0;
+        Naccept_cum = 0;
+      }
+      icyc++;
+    }
+    ptm_check(ptm_get_states(eng, transformed.data()), "proposal_tester");
+    write_samples(transformed, dim, "transformed");
+
+    std::vector<double> mean, var;
+    var = sample_var(target_samples, dim, mean);
+    std::cout << "target mean:      "; for (auto x : mean) std::cout << x << " "; std::cout << std::endl;
+    std::cout << "target var:       "; for (auto x : var) std::cout << x << " "; std::cout << std::endl;
+    var = sample_var(transformed, dim, mean);
+    std::cout << "transformed mean: "; for (auto x : mean) std::cout << x << " "; std::cout << std::endl;
+    std::cout << "transformed var:  "; for (auto x : var) std::cout << x << " "; std::cout << std::endl;
+
+    std::cout << "Computing KL divergences:" << std::endl;
+    if (Nsamp * std::pow((double)dim, 0.7) > 4500)
+      std::cout << "(exact nearest neighbours; the reference would have used approximate ones at this size)" << std::endl;
+    auto fkl = [&](const std::vector<double>& P, const std::vector<double>& Q) { return kl_estimator::fake_kl(P.data(), Nsamp, Q.data(), Nsamp, dim); };
+    const double KLtransformed = kl(transformed, target_samples, dim), KLtransformedX = kl(target_samples, transformed, dim);
+    const double fKLtransformed = fkl(transformed, target_samples), fKLtransformedX = fkl(target_samples, transformed);
+    const int fntry = 30 * ntry;
+    std::vector<double> KLdiffs((size_t)ntry), fKLdiffs((size_t)fntry);
+    for (int i = 0; i < ntry; i++) { redraw(); KLdiffs[(size_t)i] = kl(alt_samples, target_samples, dim); }
+    std::cout << "Computing 'fake' KL divergences:" << std::endl;
+    for (int i = 0; i < fntry; i++) { redraw(); fKLdiffs[(size_t)i] = fkl(alt_samples, target_samples); }
+    redraw();
+    const double altKLtransformed = kl(transformed, alt_samples, dim), altKLtransformedX = kl(alt_samples, transformed, dim);
+    const double altfKLtransformed = fkl(transformed, alt_samples), altfKLtransformedX = fkl(alt_samples, transformed);
+    last_kl.reset(new kl_verdict(KLdiffs, altKLtransformed));
+    last_fkl.reset(new kl_verdict(fKLdiffs, altfKLtransformed));
+    std::cout << last_kl->lines("KL", KLtransformed, KLtransformedX, altKLtransformed, altKLtransformedX, ncyc);
+    std::cout << last_fkl->lines("fKL", fKLtransformed, fKLtransformedX, altfKLtransformed, altfKLtransformedX, ncyc) << std::flush;
+    last_alt_fkl = altfKLtransformed;
+    last_fkl_redraw_max = 0;
+    for (double v : fKLdiffs) last_fkl_redraw_max = std::max(last_fkl_redraw_max, std::fabs(v));
+    last_accept = Naccept_last * 1.0 / Nsamp;
+    last_target = target_samples; last_transformed = transformed;
+    return true;
+  }
+  // what the last test() found (for callers that want more than the printed lines)
+  std::unique_ptr<kl_verdict> last_kl, last_fkl;
+  double last_alt_fkl = 0, last_fkl_redraw_max = 0, last_accept = 0;
+  std::vector<double> last_target, last_transformed;
+};
+
 class bayes_sampler : public Optioned {   // bayesian.hh:795-821
  protected:
   std::string paramfile;
@@ -3660,7 +4125,7 @@ class ptmcmc_sampler : public bayes_sampler {
         {"de_mixing", no_value, "Differential evolution: draw history states from every rung of the ladder."},
         {"de_Tmix", "300", "Differential evolution: how readily other rungs' histories are used. [300]"},
         {"de_unlikely_alpha", "0", "Differential evolution: power with which improbable history states are passed over. [0: never]"},
-        {"prop_test_index", "", "Index of a proposal to test in isolation (not built here)."},
+        {"prop_test_index", "", "Index of a proposal to test in isolation (\".\": the whole proposal; a-b-c: a member of nested sets; trailing L: loop over members; each trailing +: twice the sizes)."},
         // chains
         {"chain_init_file", "", "Take the start states from this chain file instead of the prior (not built here)."},
         {"chain_ess_stop", "-1.0", "Stop as soon as the cold chain's effective sample size exceeds this. [-1: never]"},
@@ -3882,6 +4347,77 @@ class ptmcmc_sampler : public bayes_sampler {
     return istep_;
   }
 
+  // ---- --prop_test_index (ptmcmc.cc:185-247): test the proposal, or the member of the set a multi-index names, in isolation
+  // (proposal_tester).  "." the whole proposal; "a-b-c" descends through nested sets; a trailing "L" loops over a set's members;
+  // each trailing "+" doubles the sizes.  The test distribution is a Gaussian around a draw of the prior with the prior's scales,
+  // halved until its +-1 sigma corners have log-prior > -100 and times 4 whenever the test gives up; in a wrapped dimension it is
+  // kept 6 sigma inside the domain (below).  Nothing of the run changes:
+  // the test runs on an engine of its own with a seed of its own, and no ladder seed is used up.
+  int prop_test_samples = 10000, prop_test_ncyc = 500, prop_test_tries = 10;   // (the reference's sizes; a test may shrink them)
+  void set_prop_test_sizes(int samples, int ncyc, int tries) { prop_test_samples = samples; prop_test_ncyc = ncyc; prop_test_tries = tries; }
+  void test_prop() {
+    std::string indexstring;
+    *optValue("prop_test_index") >> indexstring;
+    if (indexstring.length() == 0) return;
+    int rigor = 0;
+    while (!indexstring.empty() && indexstring.back() == '+') { rigor++; indexstring.pop_back(); }
+    bool looping = false;
+    if (!indexstring.empty() && indexstring.back() == 'L') { looping = true; indexstring.pop_back(); }
+    std::vector<int> multiindex;
+    if (indexstring != "." && !indexstring.empty()) {
+      std::stringstream ss(indexstring);
+      std::string elem;
+      while (std::getline(ss, elem, '-')) multiindex.push_back(atoi(elem.c_str()));
+      std::cout << " Testing proposal starting at multiindex:";
+      for (int i : multiindex) std::cout << " " << i;
+      std::cout << std::endl;
+    }
+    bool fits = false;
+    std::vector<double> cent, sigma;
+    chain_prior->getScales(sigma);
+    philox_random rng;
+    for (uint64_t attempt = 0; !fits; attempt++) {
+      rng.reseat(ProbabilityDist::engineSeed(), 0xFFFFFFFFu, ((uint64_t)1 << 41) + attempt);   // (a stream no chain uses)
+      state s0 = chain_prior->drawSample(rng);
+      const int n = s0.size();
+      cent = s0.get_params_vector();
+      // a wrapped dimension: the test engine evaluates the plain Gaussian where the reference sums it over the periodic images
+      // (wrap_probability, ptmcmc.cc:237), so the Gaussian is kept seam_sigmas sigma inside the domain -- sigma at most 1/24 of the
+      // width, the centre moved in from the seam if need be (proposal_tester::dimension_near_seam)
+      for (int i = 0; i < n; i++) {
+        const boundary b = s0.getSpace()->get_bound(i);
+        if (!b.isWrapped()) continue;
+        double xmin, xmax;
+        b.getDomainLimits(xmin, xmax);
+        const double smax = (xmax - xmin) / (4 * proposal_tester::seam_sigmas());
+        if (sigma[(size_t)i] > smax) sigma[(size_t)i] = smax;
+        const double lo = xmin + proposal_tester::seam_sigmas() * sigma[(size_t)i], hi = xmax - proposal_tester::seam_sigmas() * sigma[(size_t)i];
+        if (cent[(size_t)i] < lo || cent[(size_t)i] > hi) {
+          std::cout << "Wrapped dimension " << i << ": centre " << cent[(size_t)i] << " moved " << proposal_tester::seam_sigmas() << " sigma in from the seam." << std::endl;
+          cent[(size_t)i] = cent[(size_t)i] < lo ? lo : hi;
+        }
+      }
+      std::vector<double> topv((size_t)n), bottomv((size_t)n);
+      const double nsigcut = 1.0;
+      for (int i = 0; i < n; i++) { topv[(size_t)i] = cent[(size_t)i] + sigma[(size_t)i] * nsigcut; bottomv[(size_t)i] = cent[(size_t)i] - sigma[(size_t)i] * nsigcut; }
+      state top(s0.getSpace(), topv), bottom(s0.getSpace(), bottomv);
+      const double logcut = -100;
+      std::cout << "Checking limits: \ntop=" << top.get_string() << "\nbottom=" << bottom.get_string() << std::endl;
+      if (chain_prior->evaluate_log(top) > logcut && chain_prior->evaluate_log(bottom) > logcut) fits = true;
+      else for (auto& s : sigma) s /= 2;
+      if (fits) {
+        gaussian_dist_product dist(chain_prior->get_space(), std::valarray<double>(cent.data(), cent.size()), std::valarray<double>(sigma.data(), sigma.size()));
+        std::cout << "Test distribution is: " << dist.show() << std::endl;
+        const int fac = (int)std::pow(2, rigor);
+        const int samples = prop_test_samples * fac, ncyc = prop_test_ncyc * fac, tries = prop_test_tries * fac;
+        std::cout << "Testing on " << samples << " samples, applying proposal through " << ncyc << " cycles and calibrating with " << tries << " trials." << std::endl;
+        proposal_tester testprop(*cprop, dist, looping, "./", multiindex, ProbabilityDist::engineSeed() ^ 0x7E57ull);
+        fits = testprop.test(samples, ncyc, tries, 0, 0.005);
+        if (!fits) for (auto& s : sigma) s *= 4;
+      }
+    }
+  }
+
   int initialize() override {   // ptmcmc.cc:497-528
     if (!have_setup || !have_cprop) { std::cout << "ptmcmc_sampler::initialize.  Must call setup() and set proposal before initialization!" << std::endl; exit(1); }
     if (!parallel_tempering) { std::cout << "ptmcmc_sampler::initialize: this build drives parallel-tempering ladders: set --pt=N with N >= 2." << std::endl; exit(1); }
@@ -3929,6 +4465,7 @@ class ptmcmc_sampler : public bayes_sampler {
     if (dynamic_cast<device_proposal*>(cprop))
       std::cout << "ptmcmc_sampler::initialize: the device_proposal is drawn on the " << (cc->draws_user_proposal_on_device() ? "device (ptm_set_proposal_device)" : "host (the host-proposal step)")
                 << std::endl;
+    test_prop();   // ptmcmc.cc:526
     return 0;
   }
 
