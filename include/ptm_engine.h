@@ -597,6 +597,44 @@ int ptm_rhat(ptm_engine* e, int rung, int nfeat, int nrows, double* rhat /*[nfea
 int ptm_rhat_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* rhat /*[nfeat]*/, double* mean, double* within,
                     double* between /*[nfeat] or NULL*/, double* seq_mean, double* seq_var /*[2*nseries*nfeat] or NULL*/);
 
+/* ---- pooled posterior mean and covariance of a rung on the device ----------------------------------------------------------
+ * What the posterior is: the mean and the covariance of the first nfeat parameters, pooled over the W independent replicas of one
+ * recorded rung, from the saved rows of the history ring where they lie.  As the facade's moments_estimator states it
+ * (ptmcmc_amd/host/ptmcmc_gpu.hh).  The reference's write_covariance / read_covariance are empty (ptmcmc.cc:761-768): no counterpart.
+ *  - Walker w's window is its own newest nrows saved rows in ascending row order, ptm_rhat's rule: newest_w = 1 + (Nhist_w - 1) /
+ *    add_every_n, rows newest_w - nrows + 1 .. newest_w; row 0, the start state, is never part of it; each walker uses its own Nhist.
+ *    nrows >= 1; N = W * nrows samples, N >= 2.
+ *  - G = 64 walkers form a block: block b holds walkers 64 b .. min(64 b + 63, W - 1).
+ *  - Sums, in this order, every one sequential:
+ *      s_w[f] = sum over the window's rows of x[f];  S_b[f] = sum over block b's walkers of s_w[f];  S[f] = sum over the blocks of S_b[f];
+ *      mean[f] = S[f] / N;
+ *      for each pair i <= j, with d_i = x[i] - mean[i]:  c_w[i,j] = sum over the rows of d_i * d_j;  C_b[i,j] = sum over the block's
+ *      walkers of c_w[i,j];  C[i,j] = sum over the blocks of C_b[i,j];
+ *      cov[i,j] = cov[j,i] = C[i,j] / (N - 1).
+ *    The two-level order over the walkers is part of the definition: it lets the reduction run in parallel with defined bits.
+ * Operations run as written (multiply, then add; no contraction), so the answers carry the host estimator's bits.  A constant
+ * feature gives an exact zero row and column: nothing is special-cased.  Correlations and standard deviations are the caller's to
+ * form from cov.
+ * Outputs: mean[nfeat]; cov[nfeat*nfeat] (row-major, both triangles) or NULL; var[nfeat] (the diagonal of cov: the diagonal pairs'
+ * sums / (N - 1)) or NULL; walker_sum[W*nfeat] (s_w, [w*nfeat + f]) or NULL and count (N) or NULL -- with them a caller can pool
+ * walker splits that run as separate engines.  The covariance is offered for nfeat <= 128; above that cov must be NULL.
+ * ptm_moments runs on the engine's stream and waits for it; its workspace is kept between calls.  ptm_moments_series is the same on
+ * a caller's series, host array series[(t*nseries + s)*nfeat + f], t < n, with nseries in place of W and the newest nrows of the
+ * n rows as every window: no engine needed.
+ * PTM_ERR_INVALID: a null engine, series or mean, no history ring, rung >= history_rungs, nfeat < 1 or > dim, nrows < 1, N < 2, a
+ * chain with fewer than nrows saved rows behind the start state, or a window row the ring no longer holds ("history_capacity must
+ * hold the window").  PTM_ERR_UNSUPPORTED: a chain of the rung has made more than 2e9 add_state calls; cov with nfeat > 128.
+ * The outputs are left untouched on every failure.  Not between ptm_batch_begin and ptm_batch_end.  The per-walker pair sums pass
+ * through the workspace a group of whole blocks of walkers at a time (256 MiB at most); PTM_MOMENTS_GROUP=n in the environment forces
+ * the walkers of a group (tests): the bits do not depend on it. */
+int ptm_moments(ptm_engine* e, int rung, int nfeat, int nrows, double* mean /*[nfeat]*/, double* cov /*[nfeat*nfeat] or NULL*/,
+                double* var /*[nfeat] or NULL*/, double* walker_sum /*[W*nfeat] or NULL*/, int64_t* count /*N, or NULL*/);
+int ptm_moments_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* mean /*[nfeat]*/,
+                       double* cov /*[nfeat*nfeat] or NULL*/, double* var /*[nfeat] or NULL*/, double* walker_sum /*[nseries*nfeat] or NULL*/,
+                       int64_t* count /*N, or NULL*/);
+/* the rows of a window one staging tile of the covariance kernel holds (what a test builds its edge sizes around); 0: nfeat outside 1..128 */
+int ptm_moments_tile_rows(int nfeat);
+
 /* ---- exact nearest-neighbour squared distances on the device --------------------------------------------------------------
  * The search inside the k-NN Kullback-Leibler estimator of Perez-Cruz with which the reference tests a proposal's invariance
  * (test_proposal.hh:350-464), as the facade's kl_estimator states it (ptmcmc_amd/host/ptmcmc_gpu.hh): for every point i of P the

@@ -27,6 +27,7 @@
 #include "ptm_evidence_kernels.hpp"
 #include "ptm_kl_kernels.hpp"
 #include "ptm_launch.hpp"
+#include "ptm_moments_kernels.hpp"
 #include "ptm_rhat_kernels.hpp"
 #include "ptm_shard_rccl.hpp"
 
@@ -3820,6 +3821,129 @@ extern "C" int ptm_rhat_series(int device, const double* series, int64_t n, int 
   if ((rc = ess_series_source(&S, device, series, n, nseries, nfeat))) return rc;
   return rhat_run(nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, rhat, mean, within, between, seq_mean, seq_var);
 }
+
+// ---- pooled posterior mean and covariance of a rung on the device (ptm_moments_kernels.hpp) ---------------------------------
+// moments_estimator (ptmcmc_amd/host/ptmcmc_gpu.hh) on the ring where it lies, or on a caller's series.  The kernels write into the
+// workspace; the caller's arrays are filled only when no row of a window was missing.  d_nhist, wrapped: as rhat_run's.
+// The per-walker pair sums of the cross kernel are made and folded into their blocks' sums a group of walkers at a time (whole
+// blocks, MOM_WS_BYTES of workspace at most; PTM_MOMENTS_GROUP=n walkers in the environment forces the size: tests).
+static constexpr size_t MOM_WS_BYTES = (size_t)256 << 20;
+static int moments_run(const char* who, hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat,
+                       int nrows, double* mean, double* cov, double* var, double* walker_sum, int64_t* count) {
+  const int64_t N = (int64_t)W * nrows;
+  const size_t F = (size_t)nfeat, lanes = (size_t)W * F, P = cov ? F * (F + 1) / 2 : 0, nblocks = ((size_t)W + MOM_GROUP - 1) / MOM_GROUP;
+  size_t group = (size_t)W;   // walkers whose pair sums the workspace holds at a time
+  if (cov) {
+    const char* v = getenv("PTM_MOMENTS_GROUP");
+    const long long forced = v && *v ? atoll(v) : 0;
+    group = forced > 0 ? (size_t)forced : MOM_WS_BYTES / (P * 8);
+    group = std::max((size_t)MOM_GROUP, group / MOM_GROUP * MOM_GROUP);
+    group = std::min(group, nblocks * MOM_GROUP);
+  }
+  const size_t n_walker = cov ? group * P : (var ? lanes : 0), n_block = nblocks * std::max(F, P);
+  const size_t o_sw = 0, o_cw = o_sw + ess_align(lanes * 8), o_blk = o_cw + ess_align(n_walker * 8), o_mean = o_blk + ess_align(n_block * 8),
+               o_out = o_mean + ess_align(F * 8), o_flag = o_out + ess_align((cov ? F * F : F) * 8), total = o_flag + 256;
+  if (*ws_bytes < total) {
+    if (*ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
+    HIPCHK(hipMalloc(ws, total));
+    *ws_bytes = total;
+  }
+  unsigned char* b = (unsigned char*)*ws;
+  double *d_sw = (double*)(b + o_sw), *d_cw = (double*)(b + o_cw), *d_blk = (double*)(b + o_blk), *d_mean = (double*)(b + o_mean), *d_out = (double*)(b + o_out);
+  int* d_flag = (int*)(b + o_flag);
+  const dim3 T(MOM_THREADS);
+  auto blocks_of = [](size_t n) { return dim3((unsigned)((n + MOM_THREADS - 1) / MOM_THREADS)); };
+  HIPCHK(hipMemsetAsync(d_flag, 0, 4, st));
+  // the means: s_w, S_b, S / N
+  if (wrapped) hipLaunchKernelGGL(moments_sum_kernel<true>, blocks_of(lanes), T, 0, st, src, d_nhist, W, nfeat, nrows, (const double*)nullptr, d_sw, d_flag);
+  else hipLaunchKernelGGL(moments_sum_kernel<false>, blocks_of(lanes), T, 0, st, src, d_nhist, W, nfeat, nrows, (const double*)nullptr, d_sw, d_flag);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(moments_block_kernel, blocks_of(nblocks * F), T, 0, st, W, nfeat, (const double*)d_sw, d_blk);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(moments_final_kernel, blocks_of(F), T, 0, st, (int)nblocks, nfeat, (const double*)d_blk, (double)N, 0, d_mean);
+  HIPCHK(hipGetLastError());
+  if (cov) {   // c_w, C_b, C / (N - 1): every pair
+    // pairs a lane: as few as hold every pair in one chunk, MOM_PAIRS at most; then as many chunks as hold them all
+    const int np = (int)std::min((size_t)MOM_PAIRS, (P + MOM_THREADS - 1) / MOM_THREADS);
+    const unsigned chunks = (unsigned)((P + (size_t)MOM_THREADS * np - 1) / ((size_t)MOM_THREADS * np));
+    void (*const cross[2][MOM_PAIRS])(EssSrc, const unsigned int*, int, int, int, int, const double*, double*, int*) = {
+        {moments_cross_kernel<false, 1>, moments_cross_kernel<false, 2>, moments_cross_kernel<false, 3>, moments_cross_kernel<false, 4>},
+        {moments_cross_kernel<true, 1>, moments_cross_kernel<true, 2>, moments_cross_kernel<true, 3>, moments_cross_kernel<true, 4>}};
+    static_assert(MOM_PAIRS == 4, "one kernel per number of pairs a lane");
+    for (size_t w0 = 0; w0 < (size_t)W; w0 += group) {
+      const int nw = (int)std::min(group, (size_t)W - w0);
+      const dim3 grid((unsigned)nw, chunks);
+      hipLaunchKernelGGL(cross[wrapped ? 1 : 0][np - 1], grid, T, 0, st, src, d_nhist, (int)w0, nfeat, nrows, (int)P, (const double*)d_mean, d_cw, d_flag);
+      HIPCHK(hipGetLastError());
+      const size_t nb = ((size_t)nw + MOM_GROUP - 1) / MOM_GROUP;
+      hipLaunchKernelGGL(moments_block_kernel, blocks_of(nb * P), T, 0, st, nw, (int)P, (const double*)d_cw, d_blk + (w0 / MOM_GROUP) * P);
+      HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(moments_final_kernel, blocks_of(P), T, 0, st, (int)nblocks, (int)P, (const double*)d_blk, (double)(N - 1), nfeat, d_out);
+    HIPCHK(hipGetLastError());
+  } else if (var) {   // the diagonal pairs alone
+    if (wrapped) hipLaunchKernelGGL(moments_sum_kernel<true>, blocks_of(lanes), T, 0, st, src, d_nhist, W, nfeat, nrows, (const double*)d_mean, d_cw, d_flag);
+    else hipLaunchKernelGGL(moments_sum_kernel<false>, blocks_of(lanes), T, 0, st, src, d_nhist, W, nfeat, nrows, (const double*)d_mean, d_cw, d_flag);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(moments_block_kernel, blocks_of(nblocks * F), T, 0, st, W, nfeat, (const double*)d_cw, d_blk);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(moments_final_kernel, blocks_of(F), T, 0, st, (int)nblocks, nfeat, (const double*)d_blk, (double)(N - 1), 0, d_out);
+    HIPCHK(hipGetLastError());
+  }
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (flag) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, src.cap, nrows);
+  HIPCHK(hipMemcpyAsync(mean, d_mean, F * 8, hipMemcpyDeviceToHost, st));
+  if (cov) HIPCHK(hipMemcpyAsync(cov, d_out, F * F * 8, hipMemcpyDeviceToHost, st));
+  else if (var) HIPCHK(hipMemcpyAsync(var, d_out, F * 8, hipMemcpyDeviceToHost, st));
+  if (walker_sum) HIPCHK(hipMemcpyAsync(walker_sum, d_sw, lanes * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (cov && var)
+    for (size_t f = 0; f < F; ++f) var[f] = cov[f * F + f];   // (the diagonal pair's quotient: the same bits)
+  if (count) *count = N;
+  return PTM_OK;
+}
+static int moments_shape(const char* who, int nfeat_max, int nfeat, int nrows, const double* cov) {
+  if (nfeat < 1 || nfeat > nfeat_max) return fail(PTM_ERR_INVALID, "%s: nfeat must be in 1..%d", who, nfeat_max);
+  if (nrows < 1) return fail(PTM_ERR_INVALID, "%s: nrows must be at least 1", who);
+  if (cov && nfeat > MOM_COV_NFEAT_MAX) return fail(PTM_ERR_UNSUPPORTED, "%s: the covariance is offered up to %d features (pass cov = NULL for the mean and the variances)", who, MOM_COV_NFEAT_MAX);
+  return PTM_OK;
+}
+extern "C" int ptm_moments(ptm_engine* e, int rung, int nfeat, int nrows, double* mean, double* cov, double* var, double* walker_sum, int64_t* count) {
+  if (!e || !mean) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_moments");
+  int rc = moments_shape("ptm_moments", e->D, nfeat, nrows, cov);
+  if (rc) return rc;
+  EssSrc src;
+  std::vector<int> steps_of;
+  if ((rc = ess_ring_source(e, rung, nfeat, &src, &steps_of))) return rc;   // (settles a pending ladder launch and the uncounted adds first)
+  if ((double)e->W * nfeat > 2.0e9 || (double)e->W * nrows > 4.0e18) return fail(PTM_ERR_INVALID, "ptm_moments: bad shape");
+  if ((int64_t)e->W * nrows < 2) return fail(PTM_ERR_INVALID, "ptm_moments: at least two samples are needed (walkers x nrows = %lld)", (long long)e->W * nrows);
+  long long newest_min = 0, newest_max = 0;
+  for (int w = 0; w < e->W; ++w) {
+    const long long st = steps_of.empty() ? src.steps : steps_of[(size_t)w];
+    const long long newest = st > 0 ? 1 + (st - 1) / src.add_every : 0;   // (= the saved rows behind the start state)
+    if (!w || newest < newest_min) newest_min = newest;
+    if (!w || newest > newest_max) newest_max = newest;
+  }
+  if (newest_min < nrows) return fail(PTM_ERR_INVALID, "ptm_moments: a chain of the rung has saved %lld rows behind its start state, fewer than nrows (%d)", newest_min, nrows);
+  if (nrows > src.cap) return fail(PTM_ERR_INVALID, "ptm_moments: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", src.cap, nrows);
+  return moments_run("ptm_moments", e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->nhist + (size_t)rung * e->W, newest_max >= (long long)src.cap, e->W, nfeat, nrows,
+                     mean, cov, var, walker_sum, count);
+}
+extern "C" int ptm_moments_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* mean, double* cov, double* var,
+                                  double* walker_sum, int64_t* count) {
+  if (!mean || !series) return fail(PTM_ERR_INVALID, "null argument");
+  int rc = moments_shape("ptm_moments_series", 2000000000, nfeat, nrows, cov);
+  if (rc) return rc;
+  if ((int64_t)nrows > n) return fail(PTM_ERR_INVALID, "ptm_moments_series: the series have %lld rows, fewer than nrows (%d)", (long long)n, nrows);
+  if (nseries >= 1 && (int64_t)nseries * nrows < 2) return fail(PTM_ERR_INVALID, "ptm_moments_series: at least two samples are needed (series x nrows = %lld)", (long long)nseries * nrows);
+  EssSeries S;
+  if ((rc = ess_series_source(&S, device, series, n, nseries, nfeat))) return rc;
+  return moments_run("ptm_moments_series", nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, mean, cov, var, walker_sum, count);
+}
+extern "C" int ptm_moments_tile_rows(int nfeat) { return nfeat >= 1 && nfeat <= MOM_COV_NFEAT_MAX ? moments_tile_rows(nfeat) : 0; }
 
 // ---- exact nearest-neighbour squared distances for the k-NN KL estimator (ptm_kl_kernels.hpp) --------------------------------
 // kl_estimator::one_nnd2 / all_nnd2 (ptmcmc_amd/host/ptmcmc_gpu.hh) on a caller's two sample sets.

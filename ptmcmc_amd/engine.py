@@ -36,6 +36,7 @@ EXPORTS = [
     "ptm_ess_windowed", "ptm_ess_report", "ptm_ess_series_windowed", "ptm_ess_series_report", "ptm_ess_last_on_device",
     "ptm_log_evidence",
     "ptm_rhat", "ptm_rhat_series",
+    "ptm_moments", "ptm_moments_series", "ptm_moments_tile_rows",
     "ptm_get_prefilter_counts",
     "ptm_set_proposal_device",
     "ptm_nn_dist2", "ptm_nn_dist2_tile",
@@ -206,6 +207,10 @@ def load():
     if hasattr(L, "ptm_rhat"):
         L.ptm_rhat.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
         L.ptm_rhat_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ptm_moments"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_moments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
+        L.ptm_moments_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
+        L.ptm_moments_tile_rows.argtypes = [C.c_int]
     if hasattr(L, "ptm_nn_dist2"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
         L.ptm_nn_dist2.argtypes = [C.c_int, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _i32p, _dp, _dp, C.c_int, _dp]
     _lib = L
@@ -319,6 +324,39 @@ def rhat_series(series, nrows=None, sequences=False, out=None, device=-1):
     p = [_d(v) for v in o] + [None] * (6 - len(o))
     _chk(load().ptm_rhat_series(device, _d(a), n, ns, nf, int(nrows), *p))
     return o
+
+
+def _moments_outputs(m, nfeat, cov, walker_sums, out):
+    """(mean, cov, var[, walker_sum]) to fill, cov None where it is not asked for: the caller's `out` or new arrays"""
+    if out is not None:
+        return tuple(out)
+    o = (np.empty(nfeat), np.empty((nfeat, nfeat)) if cov else None, np.empty(nfeat))
+    return o + (np.empty((m, nfeat)),) if walker_sums else o
+
+
+def _moments_call(fn, head, o):
+    count = C.c_int64(0)
+    p = [None if v is None else _d(v) for v in o] + [None] * (4 - len(o))
+    _chk(fn(*head, *p, C.byref(count)))
+    return tuple(o) + (int(count.value),)
+
+
+def moments_series(series, nrows=None, cov=True, walker_sums=False, out=None, device=-1):
+    """pooled mean and covariance across series [n, nseries, nfeat] on the device, over the newest `nrows` rows (None: all) of every
+    series: (mean[nfeat], cov[nfeat, nfeat], var[nfeat], N); cov=False (needed above 128 features): cov is None; walker_sums=True adds
+    the per-series sums [nseries, nfeat] in front of N (ptm_moments_series).  out: arrays to fill instead, (mean, cov or None, var
+    [, walker_sum]) (they keep their contents when the call fails)."""
+    a = _series3(series)
+    n, ns, nf = a.shape
+    if nrows is None:
+        nrows = n
+    o = _moments_outputs(ns, nf, cov, walker_sums, out)
+    return _moments_call(load().ptm_moments_series, (device, _d(a), n, ns, nf, int(nrows)), o)
+
+
+def moments_tile_rows(nfeat):
+    """the rows of a window one staging tile of the covariance kernel holds (ptm_moments_tile_rows)"""
+    return int(load().ptm_moments_tile_rows(int(nfeat)))
 
 
 SEAM_SIGMAS = 6.0   # a wrapped dimension's Gaussian target keeps this many sigma inside its domain (proposal_invariance)
@@ -1015,6 +1053,24 @@ class Engine:
         p = [_d(v) for v in o] + [None] * (6 - len(o))
         _chk(self.L.ptm_rhat(self.h, int(rung), nf, int(nrows), *p))
         return o
+
+    def posterior_moments(self, rung=0, nfeat=None, nrows=None, walker_sums=False, out=None, cov=None):
+        """pooled mean and covariance of the first `nfeat` parameters over the walkers of local rung `rung`, from the history ring, on
+        the device: every walker's newest `nrows` saved rows (None: the largest window every walker of the rung still has):
+        (mean[nfeat], cov[nfeat, nfeat], var[nfeat], N) (ptm_moments).  cov=False (None: above 128 features, where no covariance is
+        offered): cov is None.  walker_sums=True adds the walkers' sums [W, nfeat] in front of N.  out: arrays to fill instead,
+        (mean, cov or None, var[, walker_sum]) (they keep their contents when the call fails)."""
+        nf = self.D if nfeat is None else int(nfeat)
+        if nrows is None:
+            if not (0 <= int(rung) < self.hist_rungs):
+                raise PtmError("rung %d keeps no history (history_rungs = %d)" % (rung, self.hist_rungs))
+            nh = self.nhist.reshape(self.nloc, self.W)[int(rung)].astype(np.int64)
+            newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
+            nrows = min(int(newest.min()), self.hist_cap)                      # (a wrapped ring holds its newest `capacity` rows)
+        if cov is None:
+            cov = nf <= 128
+        o = _moments_outputs(self.W, max(nf, 0), cov, walker_sums, out)
+        return _moments_call(self.L.ptm_moments, (self.h, int(rung), nf, int(nrows)), o)
 
     @property
     def exchange_row_capacity(self):

@@ -1873,6 +1873,152 @@ class rhat_estimator {
   }
 };
 
+// ---- pooled posterior mean and covariance across independent chains -----------------------------------------------------------------
+// moments_estimator: what the posterior is -- the mean and the covariance of the first nfeat parameters, pooled over W independent
+// replicas of one chain, on plain rows.  The reference's write_covariance / read_covariance are empty (ptmcmc.cc:761-768).
+//   * chain w's window is its own newest nrows saved rows (nrows >= 1) in ascending order, rhat_estimator's rule; N = W nrows >= 2;
+//   * group = 64 chains form a block: block b holds chains 64 b .. min(64 b + 63, W - 1);
+//   * s_w[f] = sum over the window's rows of x[f], S_b[f] = sum over the block's chains of s_w[f], S[f] = sum over the blocks of
+//     S_b[f], mean[f] = S[f] / N;
+//   * for each pair i <= j with d_i = x[i] - mean[i], in a second walk over the same rows: c_w[i,j] = sum over the rows of d_i * d_j,
+//     C_b[i,j] = sum over the block's chains, C[i,j] = sum over the blocks, cov[i,j] = cov[j,i] = C[i,j] / (N - 1);
+//   * every sum sequential, in that order; a constant feature gives an exact zero row and column.
+// The engine's kernels run the same operations in the same order on the device's own ring (ptm_moments): same bits.
+class moments_estimator {
+ public:
+  typedef rhat_estimator::reader reader;
+  enum { group = 64 };
+  struct result {
+    int nfeat;
+    long long count;                        // N
+    std::vector<double> mean, var;          // [nfeat]; var: the diagonal of cov
+    std::vector<double> cov;                // [nfeat * nfeat], row-major, both triangles (empty: not asked for)
+    std::vector<double> walker_sum;         // [W * nfeat]: s_w
+    bool complete;                          // false: a row of a window was missing (nothing else is to be believed then)
+  };
+  // W chains; newest[W]: each chain's newest saved row.  want_cov false: the mean and the variances (the diagonal pairs) alone
+  static result estimate(int W, int nfeat, int nrows, const long long* newest, const reader& read, bool want_cov = true) {
+    result r;
+    r.nfeat = nfeat; r.count = (long long)W * nrows; r.complete = true;
+    const size_t F = (size_t)nfeat, P = want_cov ? F * (F + 1) / 2 : F;
+    const double Nd = (double)r.count, N1 = (double)(r.count - 1);
+    r.walker_sum.assign((size_t)W * F, 0.0);
+    r.mean.assign(F, 0.0); r.var = r.mean;
+    std::vector<double> v, total(F, 0.0), block(F);
+    auto row = [&](int w, int i) {   // row i of chain w's window into v
+      if (!read(w, newest[w] - nrows + 1 + i, v) || v.size() < F) { r.complete = false; v.assign(F, 0.0); }
+    };
+    for (int w0 = 0; w0 < W; w0 += group) {
+      block.assign(F, 0.0);
+      for (int w = w0; w < W && w < w0 + group; w++) {
+        double* s = r.walker_sum.data() + (size_t)w * F;
+        for (int i = 0; i < nrows; i++) {
+          row(w, i);
+          for (size_t f = 0; f < F; f++) s[f] += v[f];
+        }
+        for (size_t f = 0; f < F; f++) block[f] += s[f];
+      }
+      for (size_t f = 0; f < F; f++) total[f] += block[f];
+    }
+    for (size_t f = 0; f < F; f++) r.mean[f] = total[f] / Nd;
+    // the pairs along the rows of the upper triangle: (0,0) (0,1) .. (0,F-1) (1,1) ..; without the covariance the diagonal alone
+    std::vector<double> d(F), cw(P), cb(P), c(P, 0.0);
+    for (int w0 = 0; w0 < W; w0 += group) {
+      cb.assign(P, 0.0);
+      for (int w = w0; w < W && w < w0 + group; w++) {
+        cw.assign(P, 0.0);
+        for (int i = 0; i < nrows; i++) {
+          row(w, i);
+          for (size_t f = 0; f < F; f++) d[f] = v[f] - r.mean[f];
+          size_t p = 0;
+          for (size_t a = 0; a < F; a++)
+            for (size_t b = a; b < (want_cov ? F : a + 1); b++, p++) {
+              volatile double dd = d[a] * d[b];   // (the product rounded before the sum, whatever the compiler's contraction rule)
+              cw[p] += dd;
+            }
+        }
+        for (size_t p = 0; p < P; p++) cb[p] += cw[p];
+      }
+      for (size_t p = 0; p < P; p++) c[p] += cb[p];
+    }
+    if (want_cov) {
+      r.cov.assign(F * F, 0.0);
+      size_t p = 0;
+      for (size_t a = 0; a < F; a++)
+        for (size_t b = a; b < F; b++, p++) r.cov[a * F + b] = r.cov[b * F + a] = c[p] / N1;
+      for (size_t f = 0; f < F; f++) r.var[f] = r.cov[f * F + f];
+    } else
+      for (size_t f = 0; f < F; f++) r.var[f] = c[f] / N1;
+    return r;
+  }
+};
+
+// ---- the covariance file (--covariance_out writes it, --covariance_file reads it) ---------------------------------------------------
+// Text.  "#" lines in front: the dimension, N and replicas x rows, then the parameter names; one line with the D means; D lines with
+// the rows of the D x D matrix.  Every number with 17 significant digits: reading it back gives the bits that were written.
+struct covariance_data {
+  int dim = 0;
+  std::vector<double> mean, cov;   // [dim], [dim * dim] row-major
+};
+inline void write_covariance(const std::string& file, const std::vector<double>& mean, const std::vector<double>& cov, long long count, int replicas, int rows,
+                             const std::vector<std::string>& names) {
+  const size_t D = mean.size();
+  if (cov.size() != D * D) { std::cout << "write_covariance: the matrix must be " << D << " x " << D << std::endl; exit(1); }
+  std::ofstream out(file.c_str());
+  out << "# posterior moments: dim " << D << " N " << count << " replicas " << replicas << " x rows " << rows << "\n# parameters:";
+  for (size_t i = 0; i < names.size(); i++) out << " " << names[i];
+  out << "\n";
+  char buf[40];
+  for (size_t i = 0; i < D; i++) { snprintf(buf, sizeof buf, "%.17g", mean[i]); out << (i ? " " : "") << buf; }
+  out << "\n";
+  for (size_t i = 0; i < D; i++) {
+    for (size_t j = 0; j < D; j++) { snprintf(buf, sizeof buf, "%.17g", cov[i * D + j]); out << (j ? " " : "") << buf; }
+    out << "\n";
+  }
+  out.close();
+  if (!out) { std::cout << "write_covariance: cannot write '" << file << "'" << std::endl; exit(1); }
+}
+// refuses, with a message and exit(1): a missing file, another dimension than `dim`, a value that is not a finite number, too few or
+// too many values, a matrix that is not symmetric
+inline covariance_data read_covariance(const std::string& file, int dim) {
+  auto refuse = [&](const std::string& why) { std::cout << "read_covariance: '" << file << "': " << why << std::endl; exit(1); };
+  std::ifstream in(file.c_str());
+  if (!in) refuse("cannot open the file");
+  std::vector<std::vector<double> > lines;
+  std::string line;
+  while (std::getline(in, line)) {
+    const size_t at = line.find_first_not_of(" \t\r");
+    if (at == std::string::npos || line[at] == '#') continue;
+    std::vector<double> vals;
+    const char* p = line.c_str() + at;
+    while (*p) {
+      char* end = nullptr;
+      const double x = strtod(p, &end);
+      if (end == p) refuse("not a number: '" + std::string(p).substr(0, 20) + "'");
+      if (!(x - x == 0)) refuse("a value is not finite");
+      vals.push_back(x);
+      p = end;
+      while (*p == ' ' || *p == '\t' || *p == '\r') p++;
+    }
+    lines.push_back(vals);
+  }
+  if (lines.empty() || (int)lines[0].size() != dim) {
+    std::ostringstream ss; ss << "the mean line holds " << (lines.empty() ? 0 : lines[0].size()) << " values; the parameter space has " << dim;
+    refuse(ss.str());
+  }
+  if ((int)lines.size() != dim + 1) { std::ostringstream ss; ss << "expected " << dim << " matrix rows, found " << lines.size() - 1; refuse(ss.str()); }
+  covariance_data c;
+  c.dim = dim; c.mean = lines[0];
+  for (int i = 0; i < dim; i++) {
+    if ((int)lines[(size_t)i + 1].size() != dim) { std::ostringstream ss; ss << "matrix row " << i << " holds " << lines[(size_t)i + 1].size() << " values, not " << dim; refuse(ss.str()); }
+    c.cov.insert(c.cov.end(), lines[(size_t)i + 1].begin(), lines[(size_t)i + 1].end());
+  }
+  for (int i = 0; i < dim; i++)
+    for (int j = 0; j < i; j++)
+      if (c.cov[(size_t)i * dim + j] != c.cov[(size_t)j * dim + i]) { std::ostringstream ss; ss << "the matrix is not symmetric at (" << i << "," << j << ")"; refuse(ss.str()); }
+  return c;
+}
+
 // ---- the statistics of the proposal test (test_proposal.hh:350-502, 592-644) ------------------------------------------------------
 // kl_estimator: the k-NN Kullback-Leibler estimator of Perez-Cruz with k = 1 and the Gaussian "fake KL" from means and covariances,
 // on plain rows (sample i of a set at x + i * dim), as test_proposal states them with approx_nn = false.
@@ -3682,6 +3828,70 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
   bool rhat_dev_last = false;
   bool rhat_ran_on_device() const { return rhat_dev_last; }   // the last split_rhat of this ladder ran the device's kernels
+  // ---- pooled posterior mean and covariance over the replicas of rung `rung` (moments_estimator above; the reference's covariance
+  // reader and writer are empty): every replica's newest `nrows` saved rows (< 0: all that every replica has), the first `nfeat`
+  // parameters.  The device estimates from its own ring (ptm_moments: the host estimator's bits) when the ring is there; with
+  // host-side proposals (the history is the host mirror) and with PTM_HOST_MOMENTS=1 the estimate is made here.  Above 128
+  // parameters the mean and the variances alone (result::cov stays empty).
+  bool moments_on_device_possible() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_MOMENTS"); return v && *v && *v != '0'; }();   // (A/B: keep the host path)
+    return !(off || host_mode || hist_rows <= 0);
+  }
+  moments_estimator::result posterior_moments(int rung = 0, int nfeat = -1, int nrows = -1) {
+    if (nfeat < 0 || nfeat > dim) nfeat = dim;
+    if (nrows < 0) nrows = rhat_rows_available(rung);
+    const bool want_cov = nfeat <= 128;
+    moments_dev_last = false;
+    moments_estimator::result r;
+    if (moments_on_device_possible()) {
+      const size_t nf = (size_t)(nfeat > 0 ? nfeat : 0);
+      r.nfeat = nfeat; r.count = 0;
+      r.mean.assign(nf, 0.0); r.var = r.mean;
+      if (want_cov) r.cov.assign(nf * nf, 0.0);
+      r.walker_sum.assign((size_t)W * nf, 0.0);
+      int64_t count = 0;
+      ptm_check(ptm_moments(eng, rung, nfeat, nrows, r.mean.data(), want_cov ? r.cov.data() : nullptr, r.var.data(), r.walker_sum.data(), &count), "posterior_moments");
+      r.count = count;
+      r.complete = true;
+      moments_dev_last = true;
+      return r;
+    }
+    if (rung < 0 || rung >= (host_mode ? Ntemps : history_rungs()) || nfeat < 1 || nrows < 1 || (long long)W * nrows < 2) {
+      std::cout << "parallel_tempering_chains::posterior_moments: rung " << rung << ", nfeat " << nfeat << ", nrows " << nrows << " (a recorded rung, 1..dim, at least 1 and two samples in all)" << std::endl;
+      exit(1);
+    }
+    std::vector<int64_t> nh((size_t)Ntemps * W);
+    ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "posterior_moments");
+    std::vector<long long> newest((size_t)W);
+    for (int w = 0; w < W; w++) {
+      const long long st = nh[(size_t)rung * W + w];
+      newest[(size_t)w] = st > 0 ? rhat_estimator::newest_row(st, add_every_N) : 0;
+      if (newest[(size_t)w] < nrows) { std::cout << "parallel_tempering_chains::posterior_moments: replica " << w << " has saved " << newest[(size_t)w] << " rows behind its start state, fewer than nrows (" << nrows << ")" << std::endl; exit(1); }
+    }
+    moments_estimator::reader read;
+    if (host_mode) read = [this, rung](int w, long long row, std::vector<double>& v) {   // (the mirror counts its initial draws in front)
+      const mirror_t& m = mirror[(size_t)rung * W + w];
+      const long long at = row - 1 + Ninit_rows;
+      if (row < 1 || (size_t)at >= m.rows()) return false;
+      v.assign(m.x.begin() + (size_t)at * dim, m.x.begin() + ((size_t)at + 1) * dim);
+      return true;
+    };
+    else {
+      read_history((size_t)rung * W + W - 1, "posterior_moments");
+      read = [this, rung](int w, long long row, std::vector<double>& v) {
+        const size_t HC = (size_t)history_rungs() * W, cap = hist_rows;
+        const size_t o = (size_t)(row % (long long)cap) * HC + (size_t)rung * W + w;
+        if (row < 1 || hmeta[4 * o + 3] != (int32_t)row) return false;
+        v.assign(hx.begin() + o * dim, hx.begin() + (o + 1) * dim);
+        return true;
+      };
+    }
+    r = moments_estimator::estimate(W, nfeat, nrows, newest.data(), read, want_cov);
+    if (!r.complete) { std::cout << "parallel_tempering_chains::posterior_moments: the saved history no longer holds the window (" << nrows << " rows)" << std::endl; exit(1); }
+    return r;
+  }
+  bool moments_dev_last = false;
+  bool moments_ran_on_device() const { return moments_dev_last; }   // the last posterior_moments of this ladder ran the device's kernels
   // swap_count / swap_accept_count (chain.hh:244-245)
   void swap_counts(std::vector<int64_t>& tries, std::vector<int64_t>& accepts) {
     std::vector<int64_t> t((size_t)W * (Ntemps > 1 ? Ntemps - 1 : 1)), a(t.size());
@@ -4021,6 +4231,7 @@ class ptmcmc_sampler : public bayes_sampler {
   int checkp_at_step;
   double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0, rhat_stop = -1;
   int nreplicas, replica_begin = 0, device = -1;
+  std::string covariance_out;
 
   // every flag read into a typed value (a flag without a value reads as T())
   template <class T> T flag(const std::string& name) { T v = T(); *optValue(name) >> v; return v; }
@@ -4048,6 +4259,7 @@ class ptmcmc_sampler : public bayes_sampler {
     prop_adapt_rate = flag<double>("prop_adapt_rate");
     ess_stop = flag<double>("chain_ess_stop");
     rhat_stop = flag<double>("chain_rhat_stop");
+    covariance_out = flag<std::string>("covariance_out");
     pt_stop_evid_err = flag<double>("pt_stop_evid_err");
     dpriormin = flag<double>("chain_dprior_min");
     nreplicas = optSet("replicas") ? flag<int>("replicas") : 1;
@@ -4138,6 +4350,7 @@ class ptmcmc_sampler : public bayes_sampler {
         {"replica_begin", "0", "Global index of this process's first replica (one process per GPU, disjoint ranges). [0]"},
         {"device", "-1", "GPU of this process. [-1: the current device, e.g. by HIP_VISIBLE_DEVICES]"},
         {"chain_rhat_stop", "-1.0", "Stop as soon as the split R-hat of the cold chains across the replicas, the largest over the parameters, is below this. [-1: never]"},
+        {"covariance_out", "", "At the end of the run write the cold chains' pooled posterior mean and covariance to this file (what --covariance_file reads)."},
     };
     for (size_t i = 0; i < sizeof flags / sizeof flags[0]; i++) addOption(flags[i].name, flags[i].about, flags[i].preset);
   }
@@ -4201,13 +4414,16 @@ class ptmcmc_sampler : public bayes_sampler {
   //                            de_eps, ignore_frac 0, de_unlikely_alpha), reduce_gamma(de_reduce_gamma), optional rung mixing;
   //                            its history is seeded with de_ni initial draws per parameter
   //   prior draws              share prior_draw_frac (hot share 1, power prior_draw_Tpow), when asked for
+  //   a covariance Gaussian    share cov_draw_frac, when --covariance_file names a file (read_covariance): gaussian_prop(covar,
+  //                            gauss_1d_frac, gauss_temp_scaled); the reference's reader is an empty stub (ptmcmc.cc:761-764)
   //   six Gaussian steps       share gauss_draw_frac split 2 : 4 : ... : 64; widths scale_i / 100 / f with
   //                            f = (2/s)^4 s, (2/s)^4 s^2, ..., s = gauss_step_fac (2: f = 2, 4, ..., 64); each moves a single
   //                            random parameter with probability gauss_1d_frac.  With prop_adapt_rate > 0 the six form a set
   //                            of their own whose inner shares adapt.
   // and, around that, the likelihood's own proposals with share like_prop_frac.
   struct recipe {
-    double gauss, gauss_1d, gauss_ratio, prior, prior_power, like_share, de_unit_frac, de_noise, de_divisor, de_mix, de_alpha;
+    double gauss, gauss_1d, gauss_ratio, prior, prior_power, like_share, de_unit_frac, de_noise, de_divisor, de_mix, de_alpha, cov = 0;
+    std::string cov_file;
     int de_rows_per_dim;
     bool de_mixing, adapt_all, gauss_temp_scaled;
   };
@@ -4229,10 +4445,16 @@ class ptmcmc_sampler : public bayes_sampler {
     r.de_mixing = optSet("de_mixing");
     r.adapt_all = optSet("prop_adapt_more");
     r.gauss_temp_scaled = optSet("gauss_temp_scaled");   // (without effect in the reference as well: quirk Q4)
-    // a covariance file is read by a function that is empty in the reference (ptmcmc.cc:761-764): its share is always 0 here
-    if (!flag<std::string>("covariance_file").empty())
-      std::cout << "ptmcmc_sampler::select_proposal: --covariance_file is not read (nor is it by the reference, whose reader is an empty stub); no covariance steps." << std::endl;
-    if (r.prior + r.gauss > 1) r.gauss = 1.0;   // over-subscribed: the Gaussian share is renormalised against itself
+    // the covariance Gaussian's share: none without a file (ptmcmc.cc:46-48)
+    r.cov_file = flag<std::string>("covariance_file");
+    r.cov = r.cov_file.empty() ? 0.0 : unit_interval(flag<double>("cov_draw_frac"));
+    if (r.cov > 0) {
+      if (r.prior + r.gauss + r.cov > 1) {   // ptmcmc.cc:49-53
+        const double scale = r.gauss + r.cov;
+        r.gauss /= scale;
+        r.cov /= scale;
+      }
+    } else if (r.prior + r.gauss > 1) r.gauss = 1.0;   // over-subscribed: the Gaussian share is renormalised against itself
     if (flag<double>("sym_prop_frac") > 0)
       std::cout << "ptmcmc_sampler::select_proposal: state-space symmetry moves (--sym_prop_frac) are outside this build's scope; none are added." << std::endl;
     return r;
@@ -4262,7 +4484,7 @@ class ptmcmc_sampler : public bayes_sampler {
     double thermal_power = 0;
     // A differential-evolution member with share 0 is never picked (no uniform lies below a threshold of 0) and draws nothing:
     // leaving it out gives the same chain, and an all-Gaussian recipe can then run on the device.
-    const double de_share = std::max(0.0, 1 - r.gauss - r.prior);
+    const double de_share = r.cov > 0 ? std::max(0.0, 1 - r.gauss - r.cov - r.prior) : std::max(0.0, 1 - r.gauss - r.prior);
     if (de_share > 0) {
       differential_evolution* de = new differential_evolution(0.1, r.de_unit_frac, r.de_noise, 0.0, r.de_alpha);
       de->reduce_gamma(r.de_divisor);
@@ -4274,6 +4496,10 @@ class ptmcmc_sampler : public bayes_sampler {
     if (r.prior > 0) {
       members.push_back(new draw_from_dist(*chain_prior)); cold.push_back(r.prior); hot.push_back(1.0);
       thermal_power = r.prior_power;
+    }
+    if (!r.cov_file.empty()) {   // ptmcmc.cc:105-116: read whenever a file is named, a member when its share is above 0
+      const covariance_data c = ptmgpu::read_covariance(r.cov_file, npar);
+      if (r.cov > 0) { members.push_back(new gaussian_prop(c.cov, npar, r.gauss_1d, r.gauss_temp_scaled)); cold.push_back(r.cov); hot.push_back(0.0); }
     }
     std::vector<proposal_distribution*> gaussians;
     std::vector<double> gweights;
@@ -4452,7 +4678,7 @@ class ptmcmc_sampler : public bayes_sampler {
       cc->keep_history((int)de_rows, Nptc);
       cc->use_device_de(true);
     } else {
-      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
+      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0 || !covariance_out.empty()) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
     }
     cc->set_replica_range(replica_begin, nreplicas, device);
     if (pt_evolve_rate > 0) cc->evolve_temps(pt_evolve_rate, pt_evolve_lpost_cut);   // ptmcmc.cc:512
@@ -4560,9 +4786,32 @@ class ptmcmc_sampler : public bayes_sampler {
       if (stop) break;
     }
     for (size_t k = 0; k < out.size(); k++) *out[k] << "\n" << std::endl;   // ptmcmc.cc:665
+    if (!covariance_out.empty()) write_covariance(covariance_out);
     std::cout << "Finished running chain " << ic << "." << std::endl;
     return 0;
   }
+  // ptmcmc_sampler::write_covariance / read_covariance (ptmcmc.cc:761-768, empty there).  The cold rung's pooled moments over the
+  // newest (1 - burn_frac) share of the saved rows every replica has, in the format read_covariance reads.
+  void write_covariance(const std::string& file) {
+    const int nrep = cc->replicas();
+    int nrows = (int)((1.0 - nburn_frac) * cc->rhat_rows_available(0));
+    if (nrows < 1 || (long long)nrep * nrows < 2) { std::cout << "ptmcmc_sampler::write_covariance: too few saved rows (" << nrows << " of " << nrep << " replicas); '" << file << "' is not written." << std::endl; return; }
+    const int npar = chain_prior->getDim();
+    if (npar > 128) { std::cout << "ptmcmc_sampler::write_covariance: a covariance is estimated for up to 128 parameters; '" << file << "' is not written." << std::endl; return; }
+    const moments_estimator::result r = cc->posterior_moments(0, -1, nrows);
+    std::vector<std::string> names;
+    for (int i = 0; i < npar; i++) names.push_back(chain_prior->get_space() ? chain_prior->get_space()->get_name(i) : std::string("[unnamed]"));
+    ptmgpu::write_covariance(file, r.mean, r.cov, r.count, nrep, nrows, names);
+    double smin = 0, smax = 0;
+    for (int i = 0; i < npar; i++) {
+      const double sd = std::sqrt(r.var[(size_t)i]);
+      if (!i || sd < smin) smin = sd;
+      if (!i || sd > smax) smax = sd;
+    }
+    std::cout << "Posterior moments over " << nrep << " replicas, " << nrows << " rows: " << npar << " parameters, standard deviations " << smin << " .. " << smax
+              << (cc->moments_ran_on_device() ? " (device)" : " (host)") << ", written to " << file << std::endl;
+  }
+  covariance_data read_covariance(const std::string& file) { return ptmgpu::read_covariance(file, chain_prior->getDim()); }
   // ptmcmc_sampler::analyze (ptmcmc.cc:681-755): the 1-sigma sample files of the reference need bayes_likelihood::write /
   // writeFine (signal / data modelling, out of this build's scope); what remains is its summary line
   int analyze(const std::string& base, int ic, int Nsigma, int Nbest, bayes_likelihood& like) override {
