@@ -635,6 +635,47 @@ int ptm_moments_series(int device, const double* series, int64_t n, int nseries,
 /* the rows of a window one staging tile of the covariance kernel holds (what a test builds its edge sizes around); 0: nfeat outside 1..128 */
 int ptm_moments_tile_rows(int nfeat);
 
+/* ---- exact posterior quantiles of a rung on the device ----------------------------------------------------------------------
+ * What every user writes down at the end of a run: the median and the credible interval of each parameter -- the right summary of
+ * a skewed or two-humped marginal, where the mean and the variance are not.  As the facade's quantile_estimator states it
+ * (ptmcmc_amd/host/ptmcmc_gpu.hh).  The reference runs one ladder and writes no quantiles: no counterpart.
+ *  - Sample.  The sample of feature f (f < nfeat, the first nfeat parameters) of one recorded rung is pooled over its W walkers:
+ *    walker w contributes its own newest nrows saved rows, ptm_moments' window: newest_w = 1 + (Nhist_w - 1) / add_every_n, rows
+ *    newest_w - nrows + 1 .. newest_w; row 0, the start state, is never part of it; each walker uses its own Nhist.  nrows >= 1;
+ *    N = W * nrows >= 1 samples.  A single sample is its own every quantile.
+ *  - Order.  Values are ordered by the 64-bit key  u ^ (u >> 63 ? ~0 : 1 << 63)  of their bit pattern u: the usual order of the
+ *    reals, with -0 before +0 and -inf / +inf at the ends.  The sorted sample is s_0 <= ... <= s_{N-1}.  Equal keys are equal bits,
+ *    so ties are no problem.
+ *  - Quantile.  For a probability p in [0, 1], in double arithmetic as written:
+ *      h = (double)(N - 1) * p;  lo = floor(h);  hi = min(lo + 1, N - 1);  g = h - lo;
+ *      q = (g == 0) ? s_lo : s_lo + g * (s_hi - s_lo)      (multiply, then add; no contraction)
+ *    the linear rule, numpy's default (Hyndman and Fan type 7).  x_lo = s_lo and x_hi = s_hi are returned beside it: the exact
+ *    order statistics are x_lo, and the bracket is what a caller needs to pool or to check.  p = 0 and p = 1 give the minimum and
+ *    the maximum.  Nothing is special-cased: an infinite bracket gives the formula's IEEE result.
+ * nq in 1..32; probs need not be sorted or distinct.  Outputs: q[nq*nfeat] ([k*nfeat + f]); x_lo, x_hi [nq*nfeat] or NULL; count
+ * (N) or NULL.  Every output carries the bits of quantile_estimator, which sorts the keys with std::sort and applies the formula;
+ * the device selects by radix digits (ptm_quantiles_kernels.hpp) -- the definition has no summation order in it, an order statistic
+ * is a value of the sample, so the algorithm is free.  Counts and ranks are 64-bit everywhere.
+ * ptm_quantiles runs on the engine's stream and waits for it; its workspace is kept between calls.  ptm_quantiles_series is the
+ * same on a caller's series, host array series[(t*nseries + s)*nfeat + f], t < n, with nseries in place of W and the newest nrows
+ * of the n rows as every window: no engine needed.
+ * PTM_ERR_INVALID: a null engine, series, probs or q, no history ring, rung >= history_rungs, nfeat < 1 or > dim, nrows < 1, nq
+ * outside 1..32, a p outside [0, 1] or NaN, a chain with fewer than nrows saved rows behind the start state, a window row the ring
+ * no longer holds ("history_capacity must hold the window"), and for the series call a NaN in the series (looked for on the host
+ * before anything is queued; infinities are allowed).  PTM_ERR_UNSUPPORTED: a chain of the rung has made more than 2e9 add_state
+ * calls.  The outputs are left untouched on every failure.  Not between ptm_batch_begin and ptm_batch_end.
+ * In the environment (tests, tools/quantiles_probe.py), PTM_QUANTILES_PATH=ring|packed chooses whether every pass walks the ring (the default)
+ * or the remaining candidates are copied into the workspace once they fit, PTM_QUANTILES_PACK_BYTES=n bounds that copy (256 MiB at
+ * most; candidates that do not fit keep the passes on the ring) and PTM_QUANTILES_TILE=n sets the features of an LDS tile: the
+ * bits do not depend on them. */
+int ptm_quantiles(ptm_engine* e, int rung, int nfeat, int nrows, int nq, const double* probs /*[nq]*/,
+                  double* q /*[nq*nfeat], [k*nfeat + f]*/, double* x_lo, double* x_hi /*[nq*nfeat] or NULL*/, int64_t* count /*N, or NULL*/);
+int ptm_quantiles_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, int nq, const double* probs,
+                         double* q, double* x_lo, double* x_hi, int64_t* count);
+/* the passes of the last call that walked the ring and that walked the packed copy (what a test of a forced path looks at);
+ * returns 1 if the call packed */
+int ptm_quantiles_last_path(int* ring_passes, int* packed_passes);
+
 /* ---- exact nearest-neighbour squared distances on the device --------------------------------------------------------------
  * The search inside the k-NN Kullback-Leibler estimator of Perez-Cruz with which the reference tests a proposal's invariance
  * (test_proposal.hh:350-464), as the facade's kl_estimator states it (ptmcmc_amd/host/ptmcmc_gpu.hh): for every point i of P the

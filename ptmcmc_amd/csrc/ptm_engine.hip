@@ -28,6 +28,7 @@
 #include "ptm_kl_kernels.hpp"
 #include "ptm_launch.hpp"
 #include "ptm_moments_kernels.hpp"
+#include "ptm_quantiles_kernels.hpp"
 #include "ptm_rhat_kernels.hpp"
 #include "ptm_shard_rccl.hpp"
 
@@ -3944,6 +3945,214 @@ extern "C" int ptm_moments_series(int device, const double* series, int64_t n, i
   return moments_run("ptm_moments_series", nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, mean, cov, var, walker_sum, count);
 }
 extern "C" int ptm_moments_tile_rows(int nfeat) { return nfeat >= 1 && nfeat <= MOM_COV_NFEAT_MAX ? moments_tile_rows(nfeat) : 0; }
+
+// ---- exact posterior quantiles of a rung on the device (ptm_quantiles_kernels.hpp) -------------------------------------------
+// quantile_estimator (ptmcmc_amd/host/ptmcmc_gpu.hh) on the ring where it lies, or on a caller's series: radix selection of the
+// order statistics, the interpolation formed here from them.  d_nhist, wrapped: as rhat_run's.  The caller's arrays are filled
+// only when no row of a window was missing.
+// Choices, every one forceable from the environment (tests, the probe); the bits do not depend on them:
+//   PTM_QUANTILES_PATH=ring|packed   ring (the default): every pass walks the ring.  packed: after a pass the keys that are still
+//       candidates are copied into the workspace as soon as they fit, and the passes after that read the copy.  Measured
+//       (profiles/quantiles_device.json), the copy costs more than the walks it saves -- its kernel draws every position from one
+//       counter per feature, and those returning atomics serialise -- so nothing packs unless it is asked to.
+//   PTM_QUANTILES_PACK_BYTES=n       the room of the copy (QNT_PACK_BYTES at most).  Candidates that do not fit -- ties can keep
+//       every key a candidate -- stay where they are: the passes go on walking the ring.
+//   PTM_QUANTILES_TILE=n             features of a tile of the LDS histogram (QNT_STATE_MAX / slots at most).
+// Features pass through the workspace a group at a time: QNT_HIST_BYTES of global histograms at most.
+static constexpr size_t QNT_PACK_BYTES = (size_t)256 << 20;
+static constexpr size_t QNT_HIST_BYTES = (size_t)32 << 20;
+static int g_qnt_ring_passes = 0, g_qnt_packed_passes = 0;
+static int quantiles_run(const char* who, hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat,
+                         int nrows, int nq, const double* probs, double* q, double* x_lo, double* x_hi, int64_t* count) {
+  const int64_t N = (int64_t)W * nrows;
+  // the ranks asked for, and the distinct ones among them in ascending order: the slots
+  std::vector<long long> lo_of((size_t)nq), hi_of((size_t)nq), ranks;
+  std::vector<double> g_of((size_t)nq);
+  for (int k = 0; k < nq; ++k) {
+    const double h = (double)(N - 1) * probs[k], fl = std::floor(h);
+    lo_of[(size_t)k] = (long long)fl;
+    hi_of[(size_t)k] = std::min(lo_of[(size_t)k] + 1, (long long)N - 1);
+    g_of[(size_t)k] = h - fl;
+    ranks.push_back(lo_of[(size_t)k]);
+    ranks.push_back(hi_of[(size_t)k]);
+  }
+  std::sort(ranks.begin(), ranks.end());
+  ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+  const int ns = (int)ranks.size();
+  auto slot_of = [&](long long r) { return (size_t)(std::lower_bound(ranks.begin(), ranks.end(), r) - ranks.begin()); };
+  auto env_ll = [](const char* name) { const char* v = getenv(name); return v && *v ? atoll(v) : 0ll; };
+  const char* path = getenv("PTM_QUANTILES_PATH");
+  const bool forced = path && *path, pack = forced && !strcmp(path, "packed");
+  if (forced && !pack && strcmp(path, "ring")) return fail(PTM_ERR_INVALID, "%s: PTM_QUANTILES_PATH must be ring or packed", who);
+  const int ft_max = QNT_STATE_MAX / ns;
+  const long long tile_forced = env_ll("PTM_QUANTILES_TILE");
+  const int ft = (int)std::max(1ll, std::min((long long)std::min(ft_max, nfeat), tile_forced > 0 ? tile_forced : (long long)ft_max));
+  const size_t per_feature = (size_t)ns * QNT_BINS, fg = std::min((size_t)nfeat, std::max((size_t)1, QNT_HIST_BYTES / (per_feature * 8)));
+  const long long bytes_forced = env_ll("PTM_QUANTILES_PACK_BYTES");
+  const size_t pack_bytes = pack ? (bytes_forced > 0 ? std::min((size_t)bytes_forced, QNT_PACK_BYTES) : QNT_PACK_BYTES) : 0;
+  const long long room = std::min((long long)(pack_bytes / (8 * fg)), (long long)N);   // positions of the copy
+  const size_t o_ranks = 0, o_ao = o_ranks + ess_align((size_t)QNT_SLOTS_MAX * 8), o_hb = o_ao + ess_align(2 * fg * 8), o_prefix = o_hb + ess_align(fg * 4),
+               o_rank = o_prefix + ess_align(fg * ns * 8), o_leader = o_rank + ess_align(fg * ns * 8), o_cand = o_leader + ess_align(fg * ns * 4),
+               o_fill = o_cand + ess_align(fg * 8), o_hist = o_fill + ess_align(fg * 8), o_flag = o_hist + ess_align(fg * per_feature * 8), o_packed = o_flag + 256,
+               total = o_packed + ess_align((size_t)std::max(room, 0ll) * fg * 8);
+  if (*ws_bytes < total) {
+    if (*ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
+    HIPCHK(hipMalloc(ws, total));
+    *ws_bytes = total;
+  }
+  // (every call: the attribute belongs to the current device, and a series call may name another one)
+  HIPCHK(hipFuncSetAttribute((const void*)quantiles_count_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, QNT_LDS_BYTES));
+  HIPCHK(hipFuncSetAttribute((const void*)quantiles_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, QNT_LDS_BYTES));
+  unsigned char* b = (unsigned char*)*ws;
+  int* d_flag = (int*)(b + o_flag);
+  qnt_u64* d_fill = (qnt_u64*)(b + o_fill);
+  qnt_u64* d_packed = (qnt_u64*)(b + o_packed);
+  HIPCHK(hipMemsetAsync(d_flag, 0, 4, st));
+  HIPCHK(hipMemcpyAsync(b + o_ranks, ranks.data(), (size_t)ns * 8, hipMemcpyHostToDevice, st));
+  std::vector<qnt_u64> keys((size_t)nfeat * ns);
+  std::vector<int> hb;
+  std::vector<long long> cand;
+  const dim3 T(QNT_THREADS);
+  // the grid of a walk: lanes (walkers x features of a tile), chunks of rows (about 2048 workgroups in all), tiles
+  auto grid_of = [&](QntWalk* k) {
+    const unsigned tiles = (unsigned)((k->nf + k->ft - 1) / k->ft);
+    const unsigned bx = (unsigned)(((size_t)k->W * std::min(k->ft, k->nf) + QNT_THREADS - 1) / QNT_THREADS);
+    long long chunks = std::max(1ll, std::min({(long long)k->nrows, 65535ll, 2048ll / ((long long)bx * tiles)}));
+    k->rows_per_chunk = (int)((k->nrows + chunks - 1) / chunks);
+    chunks = (k->nrows + (long long)k->rows_per_chunk - 1) / k->rows_per_chunk;
+    return dim3(bx, (unsigned)chunks, tiles);
+  };
+  int ring_passes = 0, packed_passes = 0;
+  for (size_t f0 = 0; f0 < (size_t)nfeat; f0 += fg) {
+    const int nf = (int)std::min(fg, (size_t)nfeat - f0);
+    QntState s;
+    s.ranks = (const long long*)(b + o_ranks); s.and_or = (qnt_u64*)(b + o_ao); s.hb = (int*)(b + o_hb); s.prefix = (qnt_u64*)(b + o_prefix);
+    s.rank = (long long*)(b + o_rank); s.leader = (int*)(b + o_leader); s.hist = (qnt_u64*)(b + o_hist); s.cand = (long long*)(b + o_cand);
+    s.nf = nf; s.ns = ns;
+    HIPCHK(hipMemsetAsync(s.and_or, 0xFF, (size_t)nf * 8, st));
+    HIPCHK(hipMemsetAsync(s.and_or + nf, 0, (size_t)nf * 8, st));
+    HIPCHK(hipMemsetAsync(s.hist, 0, (size_t)nf * per_feature * 8, st));
+    QntWalk ring;
+    ring.src = src; ring.nhist = d_nhist; ring.valid = nullptr; ring.room = 0; ring.W = W; ring.f0 = (int)f0; ring.nf = nf; ring.ft = ft; ring.nrows = nrows;
+    const dim3 ring_grid = grid_of(&ring);
+    if (wrapped) hipLaunchKernelGGL(quantiles_bits_kernel<true>, ring_grid, T, 0, st, ring, s.and_or, d_flag);
+    else hipLaunchKernelGGL(quantiles_bits_kernel<false>, ring_grid, T, 0, st, ring, s.and_or, d_flag);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(quantiles_update_kernel, dim3((unsigned)nf), dim3(QNT_SLOTS_MAX), 0, st, s, -1, d_flag);
+    HIPCHK(hipGetLastError());
+    int flag = 0;
+    hb.resize((size_t)nf);
+    HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hb.data(), s.hb, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (flag) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, src.cap, nrows);
+    int npass = 0;
+    for (int f = 0; f < nf; ++f)
+      if (hb[(size_t)f] >= 0) npass = std::max(npass, hb[(size_t)f] / QNT_BITS + 1);
+    QntWalk cur = ring;
+    dim3 cur_grid = ring_grid;
+    bool packed = false;
+    for (int p = 0; p < npass; ++p) {
+      const size_t lds = (size_t)std::min(cur.ft, nf) * per_feature * 4;
+      if (wrapped && !packed) hipLaunchKernelGGL(quantiles_count_kernel<true>, cur_grid, T, lds, st, cur, s, p, d_flag);
+      else hipLaunchKernelGGL(quantiles_count_kernel<false>, cur_grid, T, lds, st, cur, s, p, d_flag);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(quantiles_update_kernel, dim3((unsigned)nf), dim3(QNT_SLOTS_MAX), 0, st, s, p, d_flag);
+      HIPCHK(hipGetLastError());
+      ++(packed ? packed_passes : ring_passes);
+      if (packed || room < 1 || p + 1 >= npass) continue;
+      // do the candidates fit the copy?
+      cand.resize((size_t)nf);
+      HIPCHK(hipMemcpyAsync(cand.data(), s.cand, (size_t)nf * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      const long long cmax = *std::max_element(cand.begin(), cand.end());
+      if (cmax < 1 || cmax > room) continue;
+      HIPCHK(hipMemsetAsync(d_fill, 0, (size_t)nf * 8, st));
+      if (wrapped) hipLaunchKernelGGL(quantiles_pack_kernel<true>, ring_grid, T, 0, st, ring, s, p + 1, d_fill, room, d_packed, d_flag);
+      else hipLaunchKernelGGL(quantiles_pack_kernel<false>, ring_grid, T, 0, st, ring, s, p + 1, d_fill, room, d_packed, d_flag);
+      HIPCHK(hipGetLastError());
+      const long long rows = (cmax + QNT_PACK_WALKERS - 1) / QNT_PACK_WALKERS;
+      cur.src.x = (const double*)d_packed; cur.src.meta = nullptr;
+      cur.src.slot_stride = (long long)QNT_PACK_WALKERS * nf; cur.src.meta_stride = 0; cur.src.series_stride = nf;
+      cur.src.cap = (int)rows; cur.src.add_every = 1; cur.src.first_row = 0; cur.src.permuted = 0; cur.src.steps = (int)rows;
+      cur.nhist = nullptr; cur.valid = (const long long*)d_fill; cur.room = room; cur.W = QNT_PACK_WALKERS; cur.f0 = 0; cur.nrows = (int)rows;
+      cur_grid = grid_of(&cur);
+      packed = true;
+    }
+    HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(keys.data() + f0 * ns, s.prefix, (size_t)nf * ns * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (flag == 1) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, src.cap, nrows);
+    if (flag) return fail(PTM_ERR_HIP, "%s: the selection lost a rank (an error of the kernels)", who);
+  }
+  g_qnt_ring_passes = ring_passes; g_qnt_packed_passes = packed_passes;
+  auto value_of = [&](int f, size_t slot) {
+    const qnt_u64 u = quantiles_unkey(keys[(size_t)f * ns + slot]);
+    double v;
+    memcpy(&v, &u, 8);
+    return v;
+  };
+  for (int k = 0; k < nq; ++k) {
+    const size_t sl = slot_of(lo_of[(size_t)k]), sh = slot_of(hi_of[(size_t)k]);
+    const double g = g_of[(size_t)k];
+    for (int f = 0; f < nfeat; ++f) {
+      const double a = value_of(f, sl), c = value_of(f, sh);
+      volatile double step = g * (c - a);   // (the product rounded before the sum, whatever the compiler's contraction rule)
+      q[(size_t)k * nfeat + f] = g == 0 ? a : a + step;
+      if (x_lo) x_lo[(size_t)k * nfeat + f] = a;
+      if (x_hi) x_hi[(size_t)k * nfeat + f] = c;
+    }
+  }
+  if (count) *count = N;
+  return PTM_OK;
+}
+static int quantiles_shape(const char* who, int nfeat_max, int nfeat, int nrows, int nq, const double* probs) {
+  if (nfeat < 1 || nfeat > nfeat_max) return fail(PTM_ERR_INVALID, "%s: nfeat must be in 1..%d", who, nfeat_max);
+  if (nrows < 1) return fail(PTM_ERR_INVALID, "%s: nrows must be at least 1", who);
+  if (nq < 1 || nq > QNT_SLOTS_MAX / 2) return fail(PTM_ERR_INVALID, "%s: nq must be in 1..%d", who, QNT_SLOTS_MAX / 2);
+  for (int k = 0; k < nq; ++k)
+    if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return fail(PTM_ERR_INVALID, "%s: probability %d is outside [0, 1]", who, k);
+  return PTM_OK;
+}
+extern "C" int ptm_quantiles(ptm_engine* e, int rung, int nfeat, int nrows, int nq, const double* probs, double* q, double* x_lo, double* x_hi, int64_t* count) {
+  if (!e || !probs || !q) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_quantiles");
+  int rc = quantiles_shape("ptm_quantiles", e->D, nfeat, nrows, nq, probs);
+  if (rc) return rc;
+  EssSrc src;
+  std::vector<int> steps_of;
+  if ((rc = ess_ring_source(e, rung, nfeat, &src, &steps_of))) return rc;   // (settles a pending ladder launch and the uncounted adds first)
+  if ((double)e->W * nfeat > 2.0e9 || (double)e->W * nrows > 9.0e15) return fail(PTM_ERR_INVALID, "ptm_quantiles: bad shape");
+  long long newest_min = 0, newest_max = 0;
+  for (int w = 0; w < e->W; ++w) {
+    const long long st = steps_of.empty() ? src.steps : steps_of[(size_t)w];
+    const long long newest = st > 0 ? 1 + (st - 1) / src.add_every : 0;   // (= the saved rows behind the start state)
+    if (!w || newest < newest_min) newest_min = newest;
+    if (!w || newest > newest_max) newest_max = newest;
+  }
+  if (newest_min < nrows) return fail(PTM_ERR_INVALID, "ptm_quantiles: a chain of the rung has saved %lld rows behind its start state, fewer than nrows (%d)", newest_min, nrows);
+  if (nrows > src.cap) return fail(PTM_ERR_INVALID, "ptm_quantiles: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", src.cap, nrows);
+  return quantiles_run("ptm_quantiles", e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->nhist + (size_t)rung * e->W, newest_max >= (long long)src.cap, e->W, nfeat, nrows,
+                       nq, probs, q, x_lo, x_hi, count);
+}
+extern "C" int ptm_quantiles_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, int nq, const double* probs, double* q,
+                                    double* x_lo, double* x_hi, int64_t* count) {
+  if (!probs || !q || !series) return fail(PTM_ERR_INVALID, "null argument");
+  int rc = quantiles_shape("ptm_quantiles_series", 2000000000, nfeat, nrows, nq, probs);
+  if (rc) return rc;
+  if ((int64_t)nrows > n) return fail(PTM_ERR_INVALID, "ptm_quantiles_series: the series have %lld rows, fewer than nrows (%d)", (long long)n, nrows);
+  if (n > 2000000000 || nseries < 1 || (double)nseries * nfeat > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_quantiles_series: bad shape");
+  for (size_t i = 0, end = (size_t)n * nseries * nfeat; i < end; ++i)   // (before anything is queued; infinities are values like any other)
+    if (series[i] != series[i]) return fail(PTM_ERR_INVALID, "ptm_quantiles_series: the series hold a NaN (row %lld)", (long long)(i / ((size_t)nseries * nfeat)));
+  EssSeries S;
+  if ((rc = ess_series_source(&S, device, series, n, nseries, nfeat))) return rc;
+  return quantiles_run("ptm_quantiles_series", nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, nq, probs, q, x_lo, x_hi, count);
+}
+extern "C" int ptm_quantiles_last_path(int* ring_passes, int* packed_passes) {
+  if (ring_passes) *ring_passes = g_qnt_ring_passes;
+  if (packed_passes) *packed_passes = g_qnt_packed_passes;
+  return g_qnt_packed_passes > 0 ? 1 : 0;
+}
 
 // ---- exact nearest-neighbour squared distances for the k-NN KL estimator (ptm_kl_kernels.hpp) --------------------------------
 // kl_estimator::one_nnd2 / all_nnd2 (ptmcmc_amd/host/ptmcmc_gpu.hh) on a caller's two sample sets.

@@ -37,6 +37,7 @@ EXPORTS = [
     "ptm_log_evidence",
     "ptm_rhat", "ptm_rhat_series",
     "ptm_moments", "ptm_moments_series", "ptm_moments_tile_rows",
+    "ptm_quantiles", "ptm_quantiles_series", "ptm_quantiles_last_path",
     "ptm_get_prefilter_counts",
     "ptm_set_proposal_device",
     "ptm_nn_dist2", "ptm_nn_dist2_tile",
@@ -211,6 +212,10 @@ def load():
         L.ptm_moments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_moments_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_moments_tile_rows.argtypes = [C.c_int]
+    if hasattr(L, "ptm_quantiles"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_quantiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
+        L.ptm_quantiles_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
+        L.ptm_quantiles_last_path.argtypes = [_i32p, _i32p]
     if hasattr(L, "ptm_nn_dist2"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
         L.ptm_nn_dist2.argtypes = [C.c_int, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _i32p, _dp, _dp, C.c_int, _dp]
     _lib = L
@@ -357,6 +362,35 @@ def moments_series(series, nrows=None, cov=True, walker_sums=False, out=None, de
 def moments_tile_rows(nfeat):
     """the rows of a window one staging tile of the covariance kernel holds (ptm_moments_tile_rows)"""
     return int(load().ptm_moments_tile_rows(int(nfeat)))
+
+
+def _quantiles_call(fn, head, probs, nfeat, brackets, out):
+    """(q[nq, nfeat][, x_lo, x_hi], N): the caller's `out` arrays or new ones"""
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    o = tuple(out) if out is not None else tuple(np.empty((p.size, nfeat)) for _ in range(3 if brackets else 1))
+    count = C.c_int64(0)
+    a = [_d(v) for v in o] + [None] * (3 - len(o))
+    _chk(fn(*head, p.size, _d(p), *a, C.byref(count)))
+    return tuple(o) + (int(count.value),)
+
+
+def quantiles_series(series, probs, nrows=None, brackets=False, out=None, device=-1):
+    """exact pooled quantiles across series [n, nseries, nfeat] on the device, over the newest `nrows` rows (None: all) of every
+    series, at the probabilities `probs` (numpy's linear rule): (q[nq, nfeat], N); brackets=True: (q, x_lo, x_hi, N) with the two
+    order statistics each quantile lies between (ptm_quantiles_series).  out: arrays to fill instead, (q[, x_lo, x_hi]) (they
+    keep their contents when the call fails)."""
+    a = _series3(series)
+    n, ns, nf = a.shape
+    if nrows is None:
+        nrows = n
+    return _quantiles_call(load().ptm_quantiles_series, (device, _d(a), n, ns, nf, int(nrows)), probs, nf, brackets, out)
+
+
+def quantiles_last_path():
+    """(packed, ring_passes, packed_passes) of the last quantiles call of this process (ptm_quantiles_last_path)"""
+    r, k = C.c_int32(0), C.c_int32(0)
+    packed = load().ptm_quantiles_last_path(C.byref(r), C.byref(k))
+    return bool(packed), int(r.value), int(k.value)
 
 
 SEAM_SIGMAS = 6.0   # a wrapped dimension's Gaussian target keeps this many sigma inside its domain (proposal_invariance)
@@ -1071,6 +1105,21 @@ class Engine:
             cov = nf <= 128
         o = _moments_outputs(self.W, max(nf, 0), cov, walker_sums, out)
         return _moments_call(self.L.ptm_moments, (self.h, int(rung), nf, int(nrows)), o)
+
+    def posterior_quantiles(self, probs, rung=0, nfeat=None, nrows=None, brackets=False, out=None):
+        """exact quantiles of the first `nfeat` parameters pooled over the walkers of local rung `rung`, from the history ring, on the
+        device: every walker's newest `nrows` saved rows (None: the largest window every walker of the rung still has), at the
+        probabilities `probs` (numpy's linear rule): (q[nq, nfeat], N); brackets=True: (q, x_lo, x_hi, N) with the two order
+        statistics each quantile lies between (ptm_quantiles).  out: arrays to fill instead, (q[, x_lo, x_hi]) (they keep their
+        contents when the call fails)."""
+        nf = self.D if nfeat is None else int(nfeat)
+        if nrows is None:
+            if not (0 <= int(rung) < self.hist_rungs):
+                raise PtmError("rung %d keeps no history (history_rungs = %d)" % (rung, self.hist_rungs))
+            nh = self.nhist.reshape(self.nloc, self.W)[int(rung)].astype(np.int64)
+            newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
+            nrows = min(int(newest.min()), self.hist_cap)                      # (a wrapped ring holds its newest `capacity` rows)
+        return _quantiles_call(self.L.ptm_quantiles, (self.h, int(rung), nf, int(nrows)), probs, max(nf, 0), brackets, out)
 
     @property
     def exchange_row_capacity(self):

@@ -2019,6 +2019,148 @@ inline covariance_data read_covariance(const std::string& file, int dim) {
   return c;
 }
 
+// ---- exact pooled quantiles across independent chains --------------------------------------------------------------------------------
+// quantile_estimator: the median and the credible interval of each of the first nfeat parameters, pooled over W independent
+// replicas of one chain, on plain rows.  The reference writes no quantiles.
+//   * chain w's window is its own newest nrows saved rows (nrows >= 1), rhat_estimator's rule; the sample of a feature is the
+//     N = W nrows values of the windows (N >= 1: a single sample is its own every quantile);
+//   * values are ordered by the 64-bit key  u ^ (u >> 63 ? ~0 : 1 << 63)  of their bit pattern u: the order of the reals, -0 before
+//     +0, -inf / +inf at the ends; sorted: s_0 <= ... <= s_{N-1};
+//   * for a probability p in [0, 1]:  h = (double)(N - 1) * p,  lo = floor(h),  hi = min(lo + 1, N - 1),  g = h - lo,
+//     q = (g == 0) ? s_lo : s_lo + g * (s_hi - s_lo)  (multiply, then add): the linear rule, numpy's default (Hyndman and Fan
+//     type 7); x_lo = s_lo and x_hi = s_hi beside it.  Nothing is special-cased.
+// The engine's kernels select the same order statistics by radix digits on the device's own ring (ptm_quantiles): an order
+// statistic is a value of the sample, so the bits are the same.
+class quantile_estimator {
+ public:
+  typedef rhat_estimator::reader reader;
+  struct result {
+    int nfeat;
+    long long count;                   // N
+    std::vector<double> probs;         // [nq]
+    std::vector<double> q, x_lo, x_hi; // [nq * nfeat], [k * nfeat + f]
+    bool complete;                     // false: a row of a window was missing (nothing else is to be believed then)
+  };
+  static uint64_t key(double x) { uint64_t u; memcpy(&u, &x, 8); return u ^ ((u >> 63) ? ~(uint64_t)0 : ((uint64_t)1 << 63)); }
+  static double value(uint64_t k) { const uint64_t u = k ^ ((k >> 63) ? ((uint64_t)1 << 63) : ~(uint64_t)0); double x; memcpy(&x, &u, 8); return x; }
+  // q, x_lo, x_hi [probs.size()] of one sample (keys: sorted here)
+  static void of_sample(std::vector<uint64_t>& keys, const std::vector<double>& probs, double* q, double* x_lo, double* x_hi, size_t stride = 1) {
+    std::sort(keys.begin(), keys.end());
+    const long long N = (long long)keys.size();
+    for (size_t k = 0; k < probs.size(); k++) {
+      const double h = (double)(N - 1) * probs[k], fl = std::floor(h), g = h - fl;
+      const long long lo = (long long)fl, hi = std::min(lo + 1, N - 1);
+      const double a = value(keys[(size_t)lo]), c = value(keys[(size_t)hi]);
+      volatile double step = g * (c - a);   // (the product rounded before the sum, whatever the compiler's contraction rule)
+      q[k * stride] = g == 0 ? a : a + step;
+      x_lo[k * stride] = a;
+      x_hi[k * stride] = c;
+    }
+  }
+  // W chains; newest[W]: each chain's newest saved row
+  static result estimate(int W, int nfeat, int nrows, const long long* newest, const reader& read, const std::vector<double>& probs) {
+    result r;
+    r.nfeat = nfeat; r.count = (long long)W * nrows; r.complete = true; r.probs = probs;
+    const size_t F = (size_t)nfeat, Q = probs.size(), N = (size_t)r.count;
+    r.q.assign(Q * F, 0.0); r.x_lo = r.q; r.x_hi = r.q;
+    std::vector<uint64_t> keys(N * F);   // [f * N + sample]
+    std::vector<double> v;
+    size_t at = 0;
+    for (int w = 0; w < W; w++)
+      for (int i = 0; i < nrows; i++, at++) {
+        if (!read(w, newest[w] - nrows + 1 + i, v) || v.size() < F) { r.complete = false; v.assign(F, 0.0); }
+        for (size_t f = 0; f < F; f++) keys[f * N + at] = key(v[f]);
+      }
+    std::vector<uint64_t> one(N);
+    for (size_t f = 0; f < F; f++) {
+      one.assign(keys.begin() + f * N, keys.begin() + (f + 1) * N);
+      of_sample(one, probs, r.q.data() + f, r.x_lo.data() + f, r.x_hi.data() + f, F);
+    }
+    return r;
+  }
+};
+
+// ---- the quantile file (--quantiles_out writes it) -----------------------------------------------------------------------------------
+// Text.  One "#" line in front: the dimension, N, replicas x rows and the probabilities; then one line per parameter: its name and
+// its quantile at each probability.  Every number with 17 significant digits: reading it back gives the bits that were written.
+struct quantiles_data {
+  int dim = 0;
+  long long count = 0;
+  int replicas = 0, rows = 0;
+  std::vector<double> probs, q;   // [nq], [nq * dim] as quantile_estimator::result::q
+  std::vector<std::string> names;
+};
+inline void write_quantiles(const std::string& file, const quantile_estimator::result& r, int replicas, int rows, const std::vector<std::string>& names) {
+  const size_t D = (size_t)r.nfeat, Q = r.probs.size();
+  if (r.q.size() != Q * D || names.size() != D) { std::cout << "write_quantiles: " << Q << " quantiles of " << D << " named parameters are needed" << std::endl; exit(1); }
+  for (size_t i = 0; i < D; i++)
+    if (names[i].empty() || names[i].find_first_of(" \t\r\n#") != std::string::npos) { std::cout << "write_quantiles: parameter name '" << names[i] << "' must be one word without '#'" << std::endl; exit(1); }
+  std::ofstream out(file.c_str());
+  char buf[40];
+  out << "# posterior quantiles: dim " << D << " N " << r.count << " replicas " << replicas << " x rows " << rows << " probs";
+  for (size_t k = 0; k < Q; k++) { snprintf(buf, sizeof buf, "%.17g", r.probs[k]); out << " " << buf; }
+  out << "\n";
+  for (size_t i = 0; i < D; i++) {
+    out << names[i];
+    for (size_t k = 0; k < Q; k++) { snprintf(buf, sizeof buf, "%.17g", r.q[k * D + i]); out << " " << buf; }
+    out << "\n";
+  }
+  out.close();
+  if (!out) { std::cout << "write_quantiles: cannot write '" << file << "'" << std::endl; exit(1); }
+}
+// refuses, with a message and exit(1): a missing file, a missing or malformed header, a probability outside [0, 1], another number
+// of parameter lines than the header's dimension, a line with too few or too many values, a value that is not a number (an
+// infinite quantile is a value like any other; a NaN is refused)
+inline quantiles_data read_quantiles(const std::string& file) {
+  auto refuse = [&](const std::string& why) { std::cout << "read_quantiles: '" << file << "': " << why << std::endl; exit(1); };
+  std::ifstream in(file.c_str());
+  if (!in) refuse("cannot open the file");
+  quantiles_data d;
+  std::string line, word;
+  if (!std::getline(in, line)) refuse("the file is empty");
+  {
+    std::istringstream ss(line);
+    std::string w[4];
+    if (!(ss >> w[0] >> w[1] >> w[2] >> w[3]) || w[0] != "#" || w[1] != "posterior" || w[2] != "quantiles:" || w[3] != "dim") refuse("the header line is missing");
+    std::string sN, srep, sx, srows, sprobs;
+    if (!(ss >> d.dim >> sN >> d.count >> srep >> d.replicas >> sx >> srows >> d.rows >> sprobs) || sN != "N" || srep != "replicas" || sx != "x" || srows != "rows" || sprobs != "probs" || d.dim < 1)
+      refuse("the header line is malformed");
+    while (ss >> word) {
+      char* end = nullptr;
+      const double p = strtod(word.c_str(), &end);
+      if (end == word.c_str() || *end) refuse("not a number: '" + word + "'");
+      if (!(p >= 0.0 && p <= 1.0)) refuse("a probability is outside [0, 1]");
+      d.probs.push_back(p);
+    }
+    if (d.probs.empty()) refuse("the header names no probability");
+  }
+  const size_t Q = d.probs.size();
+  std::vector<std::vector<double> > rows;
+  while (std::getline(in, line)) {
+    const size_t at = line.find_first_not_of(" \t\r");
+    if (at == std::string::npos || line[at] == '#') continue;
+    std::istringstream ss(line);
+    std::string name;
+    ss >> name;
+    std::vector<double> vals;
+    while (ss >> word) {
+      char* end = nullptr;
+      const double x = strtod(word.c_str(), &end);
+      if (end == word.c_str() || *end) refuse("not a number: '" + word + "'");
+      if (x != x) refuse("a value is not a number");
+      vals.push_back(x);
+    }
+    if (vals.size() != Q) { std::ostringstream m; m << "the line of '" << name << "' holds " << vals.size() << " values, not " << Q; refuse(m.str()); }
+    d.names.push_back(name);
+    rows.push_back(vals);
+  }
+  if ((int)rows.size() != d.dim) { std::ostringstream m; m << "expected " << d.dim << " parameter lines, found " << rows.size(); refuse(m.str()); }
+  d.q.assign(Q * (size_t)d.dim, 0.0);
+  for (size_t i = 0; i < rows.size(); i++)
+    for (size_t k = 0; k < Q; k++) d.q[k * (size_t)d.dim + i] = rows[i][k];
+  return d;
+}
+
 // ---- the statistics of the proposal test (test_proposal.hh:350-502, 592-644) ------------------------------------------------------
 // kl_estimator: the k-NN Kullback-Leibler estimator of Perez-Cruz with k = 1 and the Gaussian "fake KL" from means and covariances,
 // on plain rows (sample i of a set at x + i * dim), as test_proposal states them with approx_nn = false.
@@ -3892,6 +4034,68 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
   bool moments_dev_last = false;
   bool moments_ran_on_device() const { return moments_dev_last; }   // the last posterior_moments of this ladder ran the device's kernels
+  // ---- exact pooled quantiles over the replicas of rung `rung` (quantile_estimator above): every replica's newest `nrows` saved
+  // rows (< 0: all that every replica has), the first `nfeat` parameters, at the probabilities `probs`.  The device selects from its
+  // own ring (ptm_quantiles: the host estimator's bits) when the ring is there; with host-side proposals (the history is the host
+  // mirror) and with PTM_HOST_QUANTILES=1 the estimate is made here.
+  bool quantiles_on_device_possible() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_QUANTILES"); return v && *v && *v != '0'; }();   // (A/B: keep the host path)
+    return !(off || host_mode || hist_rows <= 0);
+  }
+  quantile_estimator::result posterior_quantiles(const std::vector<double>& probs, int rung = 0, int nfeat = -1, int nrows = -1) {
+    if (nfeat < 0 || nfeat > dim) nfeat = dim;
+    if (nrows < 0) nrows = rhat_rows_available(rung);
+    quantiles_dev_last = false;
+    quantile_estimator::result r;
+    if (quantiles_on_device_possible()) {
+      const size_t nf = (size_t)(nfeat > 0 ? nfeat : 0);
+      r.nfeat = nfeat; r.count = 0; r.probs = probs;
+      r.q.assign(probs.size() * nf, 0.0); r.x_lo = r.q; r.x_hi = r.q;
+      int64_t count = 0;
+      ptm_check(ptm_quantiles(eng, rung, nfeat, nrows, (int)probs.size(), probs.data(), r.q.data(), r.x_lo.data(), r.x_hi.data(), &count), "posterior_quantiles");
+      r.count = count;
+      r.complete = true;
+      quantiles_dev_last = true;
+      return r;
+    }
+    bool probs_ok = !probs.empty() && probs.size() <= 32;
+    for (size_t k = 0; k < probs.size(); k++) probs_ok = probs_ok && probs[k] >= 0.0 && probs[k] <= 1.0;
+    if (rung < 0 || rung >= (host_mode ? Ntemps : history_rungs()) || nfeat < 1 || nrows < 1 || !probs_ok) {
+      std::cout << "parallel_tempering_chains::posterior_quantiles: rung " << rung << ", nfeat " << nfeat << ", nrows " << nrows << ", " << probs.size() << " probabilities (a recorded rung, 1..dim, at least 1, 1..32 values in [0, 1])" << std::endl;
+      exit(1);
+    }
+    std::vector<int64_t> nh((size_t)Ntemps * W);
+    ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "posterior_quantiles");
+    std::vector<long long> newest((size_t)W);
+    for (int w = 0; w < W; w++) {
+      const long long st = nh[(size_t)rung * W + w];
+      newest[(size_t)w] = st > 0 ? rhat_estimator::newest_row(st, add_every_N) : 0;
+      if (newest[(size_t)w] < nrows) { std::cout << "parallel_tempering_chains::posterior_quantiles: replica " << w << " has saved " << newest[(size_t)w] << " rows behind its start state, fewer than nrows (" << nrows << ")" << std::endl; exit(1); }
+    }
+    quantile_estimator::reader read;
+    if (host_mode) read = [this, rung](int w, long long row, std::vector<double>& v) {   // (the mirror counts its initial draws in front)
+      const mirror_t& m = mirror[(size_t)rung * W + w];
+      const long long at = row - 1 + Ninit_rows;
+      if (row < 1 || (size_t)at >= m.rows()) return false;
+      v.assign(m.x.begin() + (size_t)at * dim, m.x.begin() + ((size_t)at + 1) * dim);
+      return true;
+    };
+    else {
+      read_history((size_t)rung * W + W - 1, "posterior_quantiles");
+      read = [this, rung](int w, long long row, std::vector<double>& v) {
+        const size_t HC = (size_t)history_rungs() * W, cap = hist_rows;
+        const size_t o = (size_t)(row % (long long)cap) * HC + (size_t)rung * W + w;
+        if (row < 1 || hmeta[4 * o + 3] != (int32_t)row) return false;
+        v.assign(hx.begin() + o * dim, hx.begin() + (o + 1) * dim);
+        return true;
+      };
+    }
+    r = quantile_estimator::estimate(W, nfeat, nrows, newest.data(), read, probs);
+    if (!r.complete) { std::cout << "parallel_tempering_chains::posterior_quantiles: the saved history no longer holds the window (" << nrows << " rows)" << std::endl; exit(1); }
+    return r;
+  }
+  bool quantiles_dev_last = false;
+  bool quantiles_ran_on_device() const { return quantiles_dev_last; }   // the last posterior_quantiles of this ladder ran the device's kernels
   // swap_count / swap_accept_count (chain.hh:244-245)
   void swap_counts(std::vector<int64_t>& tries, std::vector<int64_t>& accepts) {
     std::vector<int64_t> t((size_t)W * (Ntemps > 1 ? Ntemps - 1 : 1)), a(t.size());
@@ -4231,7 +4435,8 @@ class ptmcmc_sampler : public bayes_sampler {
   int checkp_at_step;
   double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0, rhat_stop = -1;
   int nreplicas, replica_begin = 0, device = -1;
-  std::string covariance_out;
+  std::string covariance_out, quantiles_out;
+  std::vector<double> quantile_probs;
 
   // every flag read into a typed value (a flag without a value reads as T())
   template <class T> T flag(const std::string& name) { T v = T(); *optValue(name) >> v; return v; }
@@ -4260,6 +4465,8 @@ class ptmcmc_sampler : public bayes_sampler {
     ess_stop = flag<double>("chain_ess_stop");
     rhat_stop = flag<double>("chain_rhat_stop");
     covariance_out = flag<std::string>("covariance_out");
+    quantiles_out = flag<std::string>("quantiles_out");
+    if (!quantiles_out.empty()) quantile_probs = parse_quantile_probs(flag<std::string>("quantile_probs"));
     pt_stop_evid_err = flag<double>("pt_stop_evid_err");
     dpriormin = flag<double>("chain_dprior_min");
     nreplicas = optSet("replicas") ? flag<int>("replicas") : 1;
@@ -4351,6 +4558,8 @@ class ptmcmc_sampler : public bayes_sampler {
         {"device", "-1", "GPU of this process. [-1: the current device, e.g. by HIP_VISIBLE_DEVICES]"},
         {"chain_rhat_stop", "-1.0", "Stop as soon as the split R-hat of the cold chains across the replicas, the largest over the parameters, is below this. [-1: never]"},
         {"covariance_out", "", "At the end of the run write the cold chains' pooled posterior mean and covariance to this file (what --covariance_file reads)."},
+        {"quantiles_out", "", "At the end of the run write the cold chains' pooled posterior quantiles of every parameter to this file."},
+        {"quantile_probs", "0.05,0.5,0.95", "The probabilities of --quantiles_out, separated by commas (1 to 32 values in [0, 1]). [0.05,0.5,0.95]"},
     };
     for (size_t i = 0; i < sizeof flags / sizeof flags[0]; i++) addOption(flags[i].name, flags[i].about, flags[i].preset);
   }
@@ -4678,7 +4887,7 @@ class ptmcmc_sampler : public bayes_sampler {
       cc->keep_history((int)de_rows, Nptc);
       cc->use_device_de(true);
     } else {
-      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0 || !covariance_out.empty()) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
+      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0 || !covariance_out.empty() || !quantiles_out.empty()) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
     }
     cc->set_replica_range(replica_begin, nreplicas, device);
     if (pt_evolve_rate > 0) cc->evolve_temps(pt_evolve_rate, pt_evolve_lpost_cut);   // ptmcmc.cc:512
@@ -4787,6 +4996,7 @@ class ptmcmc_sampler : public bayes_sampler {
     }
     for (size_t k = 0; k < out.size(); k++) *out[k] << "\n" << std::endl;   // ptmcmc.cc:665
     if (!covariance_out.empty()) write_covariance(covariance_out);
+    if (!quantiles_out.empty()) write_quantiles(quantiles_out);
     std::cout << "Finished running chain " << ic << "." << std::endl;
     return 0;
   }
@@ -4812,6 +5022,39 @@ class ptmcmc_sampler : public bayes_sampler {
               << (cc->moments_ran_on_device() ? " (device)" : " (host)") << ", written to " << file << std::endl;
   }
   covariance_data read_covariance(const std::string& file) { return ptmgpu::read_covariance(file, chain_prior->getDim()); }
+  // --quantile_probs: numbers separated by commas; refuses, with a message and exit(1), an empty list, more than 32 values, a value
+  // that is not a number or lies outside [0, 1]
+  static std::vector<double> parse_quantile_probs(const std::string& text) {
+    auto refuse = [&](const std::string& why) { std::cout << "ptmcmc_sampler: --quantile_probs='" << text << "': " << why << std::endl; exit(1); };
+    std::vector<double> probs;
+    size_t at = 0;
+    while (at <= text.size()) {
+      const size_t comma = std::min(text.find(',', at), text.size());
+      const std::string word = text.substr(at, comma - at);
+      char* end = nullptr;
+      const double p = strtod(word.c_str(), &end);
+      if (word.empty() || end == word.c_str() || *end) refuse("not a number: '" + word + "'");
+      if (!(p >= 0.0 && p <= 1.0)) refuse("a probability is outside [0, 1]");
+      probs.push_back(p);
+      at = comma + 1;
+    }
+    if (probs.size() > 32) refuse("at most 32 probabilities");
+    return probs;
+  }
+  // The cold rung's pooled quantiles over the newest (1 - burn_frac) share of the saved rows every replica has, in the format
+  // read_quantiles reads.
+  void write_quantiles(const std::string& file) {
+    const int nrep = cc->replicas();
+    const int nrows = (int)((1.0 - nburn_frac) * cc->rhat_rows_available(0));
+    if (nrows < 1) { std::cout << "ptmcmc_sampler::write_quantiles: too few saved rows (" << nrows << " of " << nrep << " replicas); '" << file << "' is not written." << std::endl; return; }
+    const int npar = chain_prior->getDim();
+    const quantile_estimator::result r = cc->posterior_quantiles(quantile_probs, 0, -1, nrows);
+    std::vector<std::string> names;
+    for (int i = 0; i < npar; i++) names.push_back(chain_prior->get_space() ? chain_prior->get_space()->get_name(i) : std::string("[unnamed]"));
+    ptmgpu::write_quantiles(file, r, nrep, nrows, names);
+    std::cout << "Posterior quantiles over " << nrep << " replicas, " << nrows << " rows: " << npar << " parameters at " << quantile_probs.size() << " probabilities"
+              << (cc->quantiles_ran_on_device() ? " (device)" : " (host)") << ", written to " << file << std::endl;
+  }
   // ptmcmc_sampler::analyze (ptmcmc.cc:681-755): the 1-sigma sample files of the reference need bayes_likelihood::write /
   // writeFine (signal / data modelling, out of this build's scope); what remains is its summary line
   int analyze(const std::string& base, int ic, int Nsigma, int Nbest, bayes_likelihood& like) override {
