@@ -676,6 +676,48 @@ int ptm_quantiles_series(int device, const double* series, int64_t n, int nserie
  * returns 1 if the call packed */
 int ptm_quantiles_last_path(int* ring_passes, int* packed_passes);
 
+/* ---- corner-plot histograms of a rung on the device ---------------------------------------------------------------------------
+ * What every user looks at at the end of a run: the corner plot -- the 1-D marginal histogram of every parameter and the 2-D
+ * histogram of every pair of parameters.  As the facade's histogram_estimator states it (ptmcmc_amd/host/ptmcmc_gpu.hh).  The
+ * reference bins on the host (python/corner_with_covar.py: np.histogram, np.histogram2d); the counts here are numpy's.
+ *  - Sample.  ptm_quantiles' sample: the first nfeat parameters of one recorded rung, pooled over its W walkers; walker w
+ *    contributes its own newest nrows saved rows: newest_w = 1 + (Nhist_w - 1) / add_every_n, rows newest_w - nrows + 1 .. newest_w;
+ *    row 0, the start state, is never part of it; each walker uses its own Nhist.  nrows >= 1; N = W * nrows >= 1 samples.
+ *  - Edges.  For feature f with lo[f] < hi[f], in double arithmetic as written (multiply, then add; no contraction):
+ *      step = (hi - lo) / (double)nbins;   edge_k = lo + (double)k * step  for k < nbins;   edge_nbins = hi
+ *    np.linspace(lo, hi, nbins + 1) bit for bit.  The edges must be finite and strictly increasing: otherwise "the range cannot
+ *    hold nbins bins" (numpy's own refusal).
+ *  - Bin.  x lies in bin k if and only if edge_k <= x < edge_{k+1}, the last bin closed: x == hi lies in bin nbins - 1.  -0.0
+ *    compares as 0.  x < lo adds to below[f], x > hi to above[f], a NaN to neither.  The definition is the edges: any algorithm
+ *    that lands every double in the bin the edges give is correct.
+ *  - h1[f*nbins + k]: the samples of feature f in bin k.
+ *  - h2.  Pairs i < j in row-major order of the upper triangle: p = i*nfeat - i*(i+1)/2 + (j - i - 1), npairs = nfeat*(nfeat-1)/2.
+ *    h2[(p*nbins + ki)*nbins + kj]: the rows whose feature i lies in bin ki and whose feature j lies in bin kj.  A row with
+ *    either of the two values outside its range is left out of that pair only (np.histogram2d's rule).  nfeat == 1 has no pairs:
+ *    h2 is not touched.
+ * Counts are 64-bit.  They are integers, so there is no order of summation in the definition and every output is the host
+ * estimator's to the last unit; counts from walker splits that run as separate engines with the same lo, hi and nbins simply add.
+ * Outputs: h1[nfeat*nbins]; h2[npairs*nbins*nbins] or NULL (no pairs asked for); below, above [nfeat] or NULL; count (N) or NULL.
+ * ptm_histograms runs on the engine's stream and waits for it; its workspace is kept between calls.  ptm_histograms_series is the
+ * same on a caller's series, host array series[(t*nseries + s)*nfeat + f], t < n, with nseries in place of W and the newest nrows
+ * of the n rows as every window: no engine needed.
+ * PTM_ERR_INVALID: a null engine, series, lo, hi or h1, no history ring, rung >= history_rungs, nfeat < 1 or > dim, nrows < 1,
+ * nbins outside 1..128, a range that is not finite or not lo < hi, edges that are not finite and strictly increasing, a chain with
+ * fewer than nrows saved rows behind the start state, a window row the ring no longer holds ("history_capacity must hold the
+ * window"), and for the series call a NaN in the series (looked for on the host before anything is queued; infinities are
+ * allowed).  PTM_ERR_UNSUPPORTED: npairs * nbins * nbins > 2^25 with h2 asked for (256 MiB of counters), a chain of the rung with
+ * more than 2e9 add_state calls.  The outputs are left untouched on every failure.  Not between ptm_batch_begin and ptm_batch_end.
+ * In the environment (tests, tools/histograms_probe.py), PTM_HIST_TILE=n sets the pairs of an LDS tile of the 2-D kernel and
+ * PTM_HIST_MAP=pairs|rows how its adds are dealt to the lanes (ptm_histograms_kernels.hpp): the counts do not depend on them. */
+int ptm_histograms(ptm_engine* e, int rung, int nfeat, int nrows, int nbins, const double* lo /*[nfeat]*/, const double* hi /*[nfeat]*/,
+                   int64_t* h1 /*[nfeat*nbins]*/, int64_t* h2 /*[npairs*nbins*nbins] or NULL*/,
+                   int64_t* below, int64_t* above /*[nfeat] or NULL*/, int64_t* count /*N, or NULL*/);
+int ptm_histograms_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, int nbins, const double* lo, const double* hi,
+                          int64_t* h1, int64_t* h2, int64_t* below, int64_t* above, int64_t* count);
+/* the pairs of a tile, the tiles and the mapping (0: pairs, 1: rows) of the 2-D kernel in the last call (what a test of a forced
+ * tile looks at); returns the tiles, 0 if the call counted no pairs */
+int ptm_histograms_last_launch(int* tile_pairs, int* tiles, int* map);
+
 /* ---- exact nearest-neighbour squared distances on the device --------------------------------------------------------------
  * The search inside the k-NN Kullback-Leibler estimator of Perez-Cruz with which the reference tests a proposal's invariance
  * (test_proposal.hh:350-464), as the facade's kl_estimator states it (ptmcmc_amd/host/ptmcmc_gpu.hh): for every point i of P the

@@ -25,6 +25,7 @@
 #include "ptm_devprop_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
+#include "ptm_histograms_kernels.hpp"
 #include "ptm_kl_kernels.hpp"
 #include "ptm_launch.hpp"
 #include "ptm_moments_kernels.hpp"
@@ -4152,6 +4153,160 @@ extern "C" int ptm_quantiles_last_path(int* ring_passes, int* packed_passes) {
   if (ring_passes) *ring_passes = g_qnt_ring_passes;
   if (packed_passes) *packed_passes = g_qnt_packed_passes;
   return g_qnt_packed_passes > 0 ? 1 : 0;
+}
+
+// ---- corner-plot histograms of a rung on the device (ptm_histograms_kernels.hpp) ---------------------------------------------
+// histogram_estimator (ptmcmc_amd/host/ptmcmc_gpu.hh) on the ring where it lies, or on a caller's series.  d_nhist, wrapped: as
+// rhat_run's.  The caller's arrays are filled only when no row of a window was missing.
+// Forceable from the environment (tests, the probe); the counts do not depend on them:
+//   PTM_HIST_TILE=n          pairs of a tile of the 2-D kernel's LDS tables (what HIST_TABLE_BYTES hold at most)
+//   PTM_HIST_MAP=pairs|rows  how the 2-D kernel deals its adds to the lanes (pairs: the default)
+static int g_hist_tile = 0, g_hist_tiles = 0, g_hist_map = 0;
+// the ranges as the kernels read them, [HIST_PAR * f]: lo, hi, step, nbins / (hi - lo); refuses what the definition refuses
+static int histograms_shape(const char* who, int nfeat_max, int nfeat, int nrows, int nbins, const double* lo, const double* hi, bool pairs, std::vector<double>* par) {
+  if (nfeat < 1 || nfeat > nfeat_max) return fail(PTM_ERR_INVALID, "%s: nfeat must be in 1..%d", who, nfeat_max);
+  if (nrows < 1) return fail(PTM_ERR_INVALID, "%s: nrows must be at least 1", who);
+  if (nbins < 1 || nbins > HIST_BINS_MAX) return fail(PTM_ERR_INVALID, "%s: nbins must be in 1..%d", who, HIST_BINS_MAX);
+  par->resize((size_t)HIST_PAR * nfeat);
+  for (int f = 0; f < nfeat; ++f) {
+    const double a = lo[f], b = hi[f];
+    if (!(std::isfinite(a) && std::isfinite(b) && a < b)) return fail(PTM_ERR_INVALID, "%s: the range of feature %d is not finite with lo < hi", who, f);
+    const double width = b - a, step = width / (double)nbins;
+    bool ok = std::isfinite(step);
+    for (int k = 0; ok && k < nbins; ++k) {
+      const double e0 = histograms_edge(a, b, step, nbins, k), e1 = histograms_edge(a, b, step, nbins, k + 1);
+      ok = std::isfinite(e0) && e0 < e1;
+    }
+    if (!ok) return fail(PTM_ERR_INVALID, "%s: the range cannot hold nbins bins (feature %d: the %d edges from %.17g to %.17g are not finite and strictly increasing)", who, f, nbins + 1, a, b);
+    double* pf = par->data() + (size_t)HIST_PAR * f;
+    pf[0] = a; pf[1] = b; pf[2] = step; pf[3] = (double)nbins / width;
+  }
+  if (pairs && nfeat > 1 && (double)nfeat * (nfeat - 1) / 2.0 * nbins * nbins > (double)HIST_CELLS_MAX)
+    return fail(PTM_ERR_UNSUPPORTED, "%s: %d features and %d bins need more than 2^25 pair counters", who, nfeat, nbins);
+  return PTM_OK;
+}
+static int histograms_run(const char* who, hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat,
+                          int nrows, int nbins, const std::vector<double>& par, int64_t* h1, int64_t* h2, int64_t* below, int64_t* above, int64_t* count) {
+  const int64_t N = (int64_t)W * nrows;
+  const bool pairs = h2 && nfeat > 1;
+  const long long npairs = (long long)nfeat * (nfeat - 1) / 2, nb2 = (long long)nbins * nbins;
+  const size_t cells1 = (size_t)nfeat * (nbins + 2), cells2 = pairs ? (size_t)(npairs * nb2) : 0;
+  auto env_ll = [](const char* name) { const char* v = getenv(name); return v && *v ? atoll(v) : 0ll; };
+  const char* map_env = getenv("PTM_HIST_MAP");
+  const bool map_forced = map_env && *map_env, map_rows = map_forced && !strcmp(map_env, "rows");
+  if (map_forced && !map_rows && strcmp(map_env, "pairs")) return fail(PTM_ERR_INVALID, "%s: PTM_HIST_MAP must be pairs or rows", who);
+  const size_t o_par = 0, o_flag = o_par + ess_align(par.size() * 8), o_h1 = o_flag + 256, o_h2 = o_h1 + ess_align(cells1 * 8), total = o_h2 + ess_align(cells2 * 8);
+  if (*ws_bytes < total) {
+    if (*ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
+    HIPCHK(hipMalloc(ws, total));
+    *ws_bytes = total;
+  }
+  unsigned char* b = (unsigned char*)*ws;
+  const double* d_par = (const double*)(b + o_par);
+  int* d_flag = (int*)(b + o_flag);
+  qnt_u64 *d_h1 = (qnt_u64*)(b + o_h1), *d_h2 = (qnt_u64*)(b + o_h2);
+  HIPCHK(hipMemcpyAsync(b + o_par, par.data(), par.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(d_flag, 0, total - o_flag, st));   // the flag and every counter
+  // the 1-D kernel: quantiles_run's grid -- lanes (walkers x features of a tile), chunks of rows, tiles
+  {
+    QntWalk q;
+    q.src = src; q.nhist = d_nhist; q.valid = nullptr; q.room = 0; q.W = W; q.f0 = 0; q.nf = nfeat; q.ft = std::min(nfeat, HIST_FEATS); q.nrows = nrows;
+    const unsigned tiles = (unsigned)((nfeat + q.ft - 1) / q.ft);
+    const unsigned bx = (unsigned)(((size_t)W * q.ft + QNT_THREADS - 1) / QNT_THREADS);
+    long long chunks = std::max(1ll, std::min({(long long)nrows, 65535ll, std::max(2ll * HIST_BLOCKS / ((long long)bx * tiles), ((long long)nrows * QNT_THREADS >> 31) + 1)}));
+    q.rows_per_chunk = (int)((nrows + chunks - 1) / chunks);
+    chunks = (nrows + (long long)q.rows_per_chunk - 1) / q.rows_per_chunk;
+    const dim3 grid(bx, (unsigned)chunks, tiles);
+    const size_t lds = (size_t)q.ft * (nbins + 2) * 4;
+    if (wrapped) hipLaunchKernelGGL(histograms_1d_kernel<true>, grid, dim3(QNT_THREADS), lds, st, q, d_par, nbins, d_h1, d_flag);
+    else hipLaunchKernelGGL(histograms_1d_kernel<false>, grid, dim3(QNT_THREADS), lds, st, q, d_par, nbins, d_h1, d_flag);
+    HIPCHK(hipGetLastError());
+  }
+  int tile = 0, tiles = 0;
+  if (pairs) {
+    // tiles of pairs (grid.z), blocks of walkers (grid.x), chunks of rows (grid.y): HIST_BLOCKS workgroups, about, and fewer than
+    // 2^31 samples a workgroup
+    tile = HistLds::tile_pairs(nbins, npairs, env_ll("PTM_HIST_TILE"));
+    if ((npairs + tile - 1) / tile > 65535) tile = (int)((npairs + 65534) / 65535);
+    tiles = (int)((npairs + tile - 1) / tile);
+    HistWalk q;
+    q.src = src; q.nhist = d_nhist; q.W = W; q.nfeat = nfeat; q.nbins = nbins; q.nrows = nrows; q.tp = tile; q.map = map_rows ? HIST_MAP_ROWS : HIST_MAP_PAIRS; q.npairs = npairs;
+    const long long bx = ((long long)W + HIST_WALKERS - 1) / HIST_WALKERS;
+    long long chunks = std::max({1ll, (long long)HIST_BLOCKS / (bx * tiles), ((long long)nrows * HIST_WALKERS >> 30) + 1});
+    chunks = std::min({chunks, (long long)nrows, 65535ll});
+    q.rows_per_chunk = (int)((nrows + chunks - 1) / chunks);
+    chunks = (nrows + (long long)q.rows_per_chunk - 1) / q.rows_per_chunk;
+    const dim3 grid((unsigned)bx, (unsigned)chunks, (unsigned)tiles);
+    const size_t lds = HistLds(nullptr, nfeat, nbins, tile).bytes;
+    // (every call: the attribute belongs to the current device, and a series call may name another one)
+    HIPCHK(hipFuncSetAttribute((const void*)histograms_2d_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HistLds(nullptr, 2, 1, HIST_PAIRS_MAX).bytes));
+    HIPCHK(hipFuncSetAttribute((const void*)histograms_2d_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HistLds(nullptr, 2, 1, HIST_PAIRS_MAX).bytes));
+    if (wrapped) hipLaunchKernelGGL(histograms_2d_kernel<true>, grid, dim3(HIST_THREADS), lds, st, q, d_par, d_h2, d_flag);
+    else hipLaunchKernelGGL(histograms_2d_kernel<false>, grid, dim3(HIST_THREADS), lds, st, q, d_par, d_h2, d_flag);
+    HIPCHK(hipGetLastError());
+  }
+  int flag = 0;
+  std::vector<qnt_u64> c1(cells1);
+  HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(c1.data(), d_h1, cells1 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (flag) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, src.cap, nrows);
+  if (pairs) {
+    HIPCHK(hipMemcpyAsync(h2, d_h2, cells2 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int f = 0; f < nfeat; ++f) {
+    const qnt_u64* c = c1.data() + (size_t)f * (nbins + 2);
+    for (int k = 0; k < nbins; ++k) h1[(size_t)f * nbins + k] = (int64_t)c[k];
+    if (below) below[f] = (int64_t)c[nbins];
+    if (above) above[f] = (int64_t)c[nbins + 1];
+  }
+  if (count) *count = N;
+  g_hist_tile = tile; g_hist_tiles = tiles; g_hist_map = map_rows ? 1 : 0;
+  return PTM_OK;
+}
+extern "C" int ptm_histograms(ptm_engine* e, int rung, int nfeat, int nrows, int nbins, const double* lo, const double* hi, int64_t* h1, int64_t* h2, int64_t* below,
+                              int64_t* above, int64_t* count) {
+  if (!e || !lo || !hi || !h1) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_histograms");
+  std::vector<double> par;
+  int rc = histograms_shape("ptm_histograms", e->D, nfeat, nrows, nbins, lo, hi, h2 != nullptr, &par);
+  if (rc) return rc;
+  EssSrc src;
+  std::vector<int> steps_of;
+  if ((rc = ess_ring_source(e, rung, nfeat, &src, &steps_of))) return rc;   // (settles a pending ladder launch and the uncounted adds first)
+  if ((double)e->W * nfeat > 2.0e9 || (double)e->W * nrows > 9.0e15) return fail(PTM_ERR_INVALID, "ptm_histograms: bad shape");
+  long long newest_min = 0, newest_max = 0;
+  for (int w = 0; w < e->W; ++w) {
+    const long long st = steps_of.empty() ? src.steps : steps_of[(size_t)w];
+    const long long newest = st > 0 ? 1 + (st - 1) / src.add_every : 0;   // (= the saved rows behind the start state)
+    if (!w || newest < newest_min) newest_min = newest;
+    if (!w || newest > newest_max) newest_max = newest;
+  }
+  if (newest_min < nrows) return fail(PTM_ERR_INVALID, "ptm_histograms: a chain of the rung has saved %lld rows behind its start state, fewer than nrows (%d)", newest_min, nrows);
+  if (nrows > src.cap) return fail(PTM_ERR_INVALID, "ptm_histograms: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", src.cap, nrows);
+  return histograms_run("ptm_histograms", e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->nhist + (size_t)rung * e->W, newest_max >= (long long)src.cap, e->W, nfeat, nrows,
+                        nbins, par, h1, h2, below, above, count);
+}
+extern "C" int ptm_histograms_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, int nbins, const double* lo, const double* hi,
+                                     int64_t* h1, int64_t* h2, int64_t* below, int64_t* above, int64_t* count) {
+  if (!lo || !hi || !h1 || !series) return fail(PTM_ERR_INVALID, "null argument");
+  std::vector<double> par;
+  int rc = histograms_shape("ptm_histograms_series", 2000000000, nfeat, nrows, nbins, lo, hi, h2 != nullptr, &par);
+  if (rc) return rc;
+  if ((int64_t)nrows > n) return fail(PTM_ERR_INVALID, "ptm_histograms_series: the series have %lld rows, fewer than nrows (%d)", (long long)n, nrows);
+  if (n > 2000000000 || nseries < 1 || (double)nseries * nfeat > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_histograms_series: bad shape");
+  for (size_t i = 0, end = (size_t)n * nseries * nfeat; i < end; ++i)   // (before anything is queued; infinities are values like any other)
+    if (series[i] != series[i]) return fail(PTM_ERR_INVALID, "ptm_histograms_series: the series hold a NaN (row %lld)", (long long)(i / ((size_t)nseries * nfeat)));
+  EssSeries S;
+  if ((rc = ess_series_source(&S, device, series, n, nseries, nfeat))) return rc;
+  return histograms_run("ptm_histograms_series", nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, nbins, par, h1, h2, below, above, count);
+}
+extern "C" int ptm_histograms_last_launch(int* tile_pairs, int* tiles, int* map) {
+  if (tile_pairs) *tile_pairs = g_hist_tile;
+  if (tiles) *tiles = g_hist_tiles;
+  if (map) *map = g_hist_map;
+  return g_hist_tiles;
 }
 
 // ---- exact nearest-neighbour squared distances for the k-NN KL estimator (ptm_kl_kernels.hpp) --------------------------------

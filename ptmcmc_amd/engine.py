@@ -38,6 +38,7 @@ EXPORTS = [
     "ptm_rhat", "ptm_rhat_series",
     "ptm_moments", "ptm_moments_series", "ptm_moments_tile_rows",
     "ptm_quantiles", "ptm_quantiles_series", "ptm_quantiles_last_path",
+    "ptm_histograms", "ptm_histograms_series", "ptm_histograms_last_launch",
     "ptm_get_prefilter_counts",
     "ptm_set_proposal_device",
     "ptm_nn_dist2", "ptm_nn_dist2_tile",
@@ -216,6 +217,10 @@ def load():
         L.ptm_quantiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_quantiles_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_quantiles_last_path.argtypes = [_i32p, _i32p]
+    if hasattr(L, "ptm_histograms"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_histograms.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _i64p, _i64p, _i64p, _i64p, _i64p]
+        L.ptm_histograms_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _i64p, _i64p, _i64p, _i64p, _i64p]
+        L.ptm_histograms_last_launch.argtypes = [_i32p, _i32p, _i32p]
     if hasattr(L, "ptm_nn_dist2"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
         L.ptm_nn_dist2.argtypes = [C.c_int, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _i32p, _dp, _dp, C.c_int, _dp]
     _lib = L
@@ -391,6 +396,87 @@ def quantiles_last_path():
     r, k = C.c_int32(0), C.c_int32(0)
     packed = load().ptm_quantiles_last_path(C.byref(r), C.byref(k))
     return bool(packed), int(r.value), int(k.value)
+
+
+def _i64(a):
+    return a.ctypes.data_as(_i64p)
+
+
+def histogram_edges(lo, hi, nbins):
+    """the nbins + 1 edges of the range [lo, hi] as ptm_histograms defines them: lo + k * ((hi - lo) / nbins), the last one hi
+    itself -- np.linspace(lo, hi, nbins + 1) bit for bit.  lo, hi: numbers or arrays [nfeat] (the edges: [nfeat, nbins + 1])"""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    step = (hi - lo) / np.float64(nbins)
+    e = lo[..., None] + np.arange(nbins + 1, dtype=np.float64) * step[..., None]
+    e[..., nbins] = hi
+    return e
+
+
+def _histograms_call(fn, head, lo, hi, nbins, nfeat, pairs, out):
+    """(h1[nfeat, nbins], h2[npairs, nbins, nbins] or None, below, above, N): the caller's `out` arrays or new ones"""
+    lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1)
+    if lo.size != nfeat or hi.size != nfeat:
+        raise ValueError("lo and hi must hold one value for each of the %d features" % nfeat)
+    nb, npairs = max(int(nbins), 0), nfeat * (nfeat - 1) // 2
+    if out is not None:
+        h1, h2, below, above = out
+    else:
+        if pairs and npairs * nb * nb > 1 << 25:
+            h2 = np.zeros((0, nb, nb), dtype=np.int64)   # (refused by the call: nothing that large is allocated for it)
+        else:
+            h2 = np.zeros((npairs, nb, nb), dtype=np.int64) if pairs else None
+        h1, below, above = np.zeros((nfeat, nb), dtype=np.int64), np.zeros(nfeat, dtype=np.int64), np.zeros(nfeat, dtype=np.int64)
+    count = C.c_int64(0)
+    _chk(fn(*head, int(nbins), _d(lo), _d(hi), _i64(h1), _i64(h2) if h2 is not None else None, _i64(below), _i64(above), C.byref(count)))
+    return h1, h2, below, above, int(count.value)
+
+
+def histograms_series(series, lo, hi, nbins, nrows=None, pairs=True, out=None, device=-1):
+    """the corner plot's counts across series [n, nseries, nfeat] on the device, over the newest `nrows` rows (None: all) of every
+    series: (h1[nfeat, nbins], h2[npairs, nbins, nbins] or None, below[nfeat], above[nfeat], N), int64; the bins of feature f are
+    histogram_edges(lo[f], hi[f], nbins), the last one closed (np.histogram's counts), the pairs i < j in row-major order
+    (np.histogram2d's counts); pairs=False: no h2 (ptm_histograms_series).  out: arrays to fill instead, (h1, h2 or None, below,
+    above) (they keep their contents when the call fails)."""
+    a = _series3(series)
+    n, ns, nf = a.shape
+    if nrows is None:
+        nrows = n
+    return _histograms_call(load().ptm_histograms_series, (device, _d(a), n, ns, nf, int(nrows)), lo, hi, nbins, nf, pairs, out)
+
+
+def histograms_last_launch():
+    """(tiles, pairs of a tile, mapping) of the 2-D kernel in the last histograms call of this process (ptm_histograms_last_launch)"""
+    t, n, m = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load().ptm_histograms_last_launch(C.byref(t), C.byref(n), C.byref(m))
+    return int(n.value), int(t.value), "rows" if m.value else "pairs"
+
+
+def read_corner(path):
+    """the corner file --corner_out writes (the facade's write_corner): a dict with dim, nbins, count, replicas, rows, names, lo, hi,
+    below, above [dim], h1 [dim, nbins] and h2 [npairs, nbins, nbins] (int64; the pairs i < j in row-major order)"""
+    lines = [ln.split() for ln in open(path) if ln.strip()]
+    head = lines[0]
+    if head[:4] != ["#", "posterior", "histograms:", "dim"]:
+        raise ValueError("%s: the header line is missing" % path)
+    keys = dict(zip(head[3::2], head[4::2]))
+    dim, nbins = int(keys["dim"]), int(keys["nbins"])
+    body = [ln for ln in lines[1:] if not ln[0].startswith("#")]
+    npairs = int(keys["pairs"])                                        # (0: written without the pairs)
+    if npairs not in (0, dim * (dim - 1) // 2) or len(body) != dim + npairs:
+        raise ValueError("%s: expected %d lines, found %d" % (path, dim + npairs, len(body)))
+    one, two = body[:dim], body[dim:]
+    if any(len(ln) != 5 + nbins for ln in one) or any(len(ln) != 2 + nbins * nbins for ln in two):
+        raise ValueError("%s: a line holds another number of values than its bins" % path)
+    return {
+        "dim": dim, "nbins": nbins, "count": int(keys["N"]), "replicas": int(keys["replicas"]), "rows": int(keys["rows"]),
+        "names": [ln[0] for ln in one],
+        "lo": np.array([float(ln[1]) for ln in one]), "hi": np.array([float(ln[2]) for ln in one]),
+        "below": np.array([int(ln[3]) for ln in one], dtype=np.int64), "above": np.array([int(ln[4]) for ln in one], dtype=np.int64),
+        "h1": np.array([[int(v) for v in ln[5:]] for ln in one], dtype=np.int64).reshape(dim, nbins),
+        "h2": np.array([[int(v) for v in ln[2:]] for ln in two], dtype=np.int64).reshape(npairs, nbins, nbins),
+        "pairs": [(ln[0], ln[1]) for ln in two],
+    }
 
 
 SEAM_SIGMAS = 6.0   # a wrapped dimension's Gaussian target keeps this many sigma inside its domain (proposal_invariance)
@@ -1120,6 +1206,22 @@ class Engine:
             newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
             nrows = min(int(newest.min()), self.hist_cap)                      # (a wrapped ring holds its newest `capacity` rows)
         return _quantiles_call(self.L.ptm_quantiles, (self.h, int(rung), nf, int(nrows)), probs, max(nf, 0), brackets, out)
+
+    def posterior_histograms(self, lo, hi, nbins=20, rung=0, nfeat=None, nrows=None, pairs=True, out=None):
+        """the corner plot's counts of the first `nfeat` parameters pooled over the walkers of local rung `rung`, from the history
+        ring, on the device: every walker's newest `nrows` saved rows (None: the largest window every walker of the rung still has):
+        (h1[nfeat, nbins], h2[npairs, nbins, nbins] or None, below[nfeat], above[nfeat], N), int64; the bins of feature f are
+        histogram_edges(lo[f], hi[f], nbins), the last one closed (np.histogram's counts), the pairs i < j in row-major order
+        (np.histogram2d's counts); pairs=False: no h2 (ptm_histograms).  out: arrays to fill instead, (h1, h2 or None, below, above)
+        (they keep their contents when the call fails)."""
+        nf = self.D if nfeat is None else int(nfeat)
+        if nrows is None:
+            if not (0 <= int(rung) < self.hist_rungs):
+                raise PtmError("rung %d keeps no history (history_rungs = %d)" % (rung, self.hist_rungs))
+            nh = self.nhist.reshape(self.nloc, self.W)[int(rung)].astype(np.int64)
+            newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
+            nrows = min(int(newest.min()), self.hist_cap)                      # (a wrapped ring holds its newest `capacity` rows)
+        return _histograms_call(self.L.ptm_histograms, (self.h, int(rung), nf, int(nrows)), lo, hi, nbins, max(nf, 0), pairs, out)
 
     @property
     def exchange_row_capacity(self):

@@ -27,6 +27,7 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2161,6 +2162,199 @@ inline quantiles_data read_quantiles(const std::string& file) {
   return d;
 }
 
+// ---- corner-plot histograms across independent chains -----------------------------------------------------------------------------------
+// histogram_estimator: the counts of a corner plot -- the 1-D histogram of each of the first nfeat parameters and the 2-D histogram
+// of each pair of them -- pooled over W independent replicas of one chain, on plain rows.  The reference bins on the host with numpy
+// (python/corner_with_covar.py: np.histogram, np.histogram2d); these are numpy's counts.
+//   * chain w's window is its own newest nrows saved rows (nrows >= 1), rhat_estimator's rule; the sample is the N = W nrows rows
+//     of the windows (quantile_estimator's sample);
+//   * the edges of feature f, lo < hi:  step = (hi - lo) / (double)nbins,  edge_k = lo + (double)k * step  (multiply, then add) for
+//     k < nbins,  edge_nbins = hi: np.linspace(lo, hi, nbins + 1) bit for bit.  They must be finite and strictly increasing;
+//   * x lies in bin k iff edge_k <= x < edge_{k+1} (std::upper_bound on the edges), the last bin closed: x == hi lies in bin
+//     nbins - 1; -0.0 compares as 0; x < lo counts as below, x > hi as above, a NaN as neither;
+//   * h1[f * nbins + k]: the samples of feature f in bin k;  h2[(p * nbins + ki) * nbins + kj]: the rows whose feature i lies in bin
+//     ki and whose feature j in bin kj, pairs i < j in row-major order, p = i nfeat - i (i + 1) / 2 + (j - i - 1); a row with either
+//     value outside its range is left out of that pair only.
+// The engine's kernels count the same on the device's own ring (ptm_histograms): integers, so the same to the last unit.  Counts of
+// walker splits with the same lo, hi and nbins simply add.
+class histogram_estimator {
+ public:
+  typedef rhat_estimator::reader reader;
+  struct result {
+    int nfeat = 0, nbins = 0;
+    long long count = 0;               // N
+    std::vector<double> lo, hi;        // [nfeat]
+    std::vector<int64_t> h1, h2;       // [nfeat * nbins], [npairs * nbins * nbins] (empty: no pairs were asked for)
+    std::vector<int64_t> below, above; // [nfeat]
+    bool complete = true;              // false: a row of a window was missing (nothing else is to be believed then)
+  };
+  enum { BELOW = -1, ABOVE = -2, NOT_A_NUMBER = -3 };
+  static std::vector<double> edges(double lo, double hi, int nbins) {
+    std::vector<double> e((size_t)nbins + 1);
+    const double step = (hi - lo) / (double)nbins;
+    for (int k = 0; k < nbins; k++) {
+      volatile double up = (double)k * step;   // (the product rounded before the sum, whatever the compiler's contraction rule)
+      e[(size_t)k] = lo + up;
+    }
+    e[(size_t)nbins] = hi;
+    return e;
+  }
+  // finite, lo < hi, strictly increasing: what a range must give to hold nbins bins
+  static bool edges_ok(double lo, double hi, int nbins) {
+    if (!(std::isfinite(lo) && std::isfinite(hi) && lo < hi) || nbins < 1) return false;
+    const std::vector<double> e = edges(lo, hi, nbins);
+    for (size_t k = 0; k + 1 < e.size(); k++)
+      if (!(std::isfinite(e[k]) && e[k] < e[k + 1])) return false;
+    return true;
+  }
+  // the bin of x among nbins + 1 edges, or BELOW, ABOVE, NOT_A_NUMBER
+  static int bin(const std::vector<double>& e, double x) {
+    const int nbins = (int)e.size() - 1;
+    if (x != x) return NOT_A_NUMBER;
+    if (x < e[0]) return BELOW;
+    if (x > e[(size_t)nbins]) return ABOVE;
+    if (x == e[(size_t)nbins]) return nbins - 1;
+    return (int)(std::upper_bound(e.begin(), e.end(), x) - e.begin()) - 1;
+  }
+  static size_t npairs(int nfeat) { return (size_t)nfeat * (size_t)(nfeat - 1) / 2; }
+  static size_t pair_index(int nfeat, int i, int j) { return (size_t)i * nfeat - (size_t)i * (i + 1) / 2 + (size_t)(j - i - 1); }
+  // W chains; newest[W]: each chain's newest saved row.  Every range must pass edges_ok.
+  static result estimate(int W, int nfeat, int nrows, const long long* newest, const reader& read, const std::vector<double>& lo, const std::vector<double>& hi,
+                         int nbins, bool pairs = true) {
+    result r;
+    r.nfeat = nfeat; r.nbins = nbins; r.count = (long long)W * nrows; r.lo = lo; r.hi = hi;
+    const size_t F = (size_t)nfeat, B = (size_t)nbins;
+    r.h1.assign(F * B, 0); r.below.assign(F, 0); r.above.assign(F, 0);
+    if (pairs) r.h2.assign(npairs(nfeat) * B * B, 0);
+    std::vector<std::vector<double> > e;
+    for (size_t f = 0; f < F; f++) e.push_back(edges(lo[f], hi[f], nbins));
+    std::vector<double> v;
+    std::vector<int> k(F);
+    for (int w = 0; w < W; w++)
+      for (int i = 0; i < nrows; i++) {
+        if (!read(w, newest[w] - nrows + 1 + i, v) || v.size() < F) { r.complete = false; continue; }
+        for (size_t f = 0; f < F; f++) {
+          k[f] = bin(e[f], v[f]);
+          if (k[f] >= 0) r.h1[f * B + (size_t)k[f]]++;
+          else if (k[f] == BELOW) r.below[f]++;
+          else if (k[f] == ABOVE) r.above[f]++;
+        }
+        if (!pairs) continue;
+        size_t p = 0;
+        for (size_t a = 0; a < F; a++)
+          for (size_t b = a + 1; b < F; b++, p++)
+            if (k[a] >= 0 && k[b] >= 0) r.h2[(p * B + (size_t)k[a]) * B + (size_t)k[b]]++;
+      }
+    return r;
+  }
+};
+
+// ---- the corner file (--corner_out writes it) ---------------------------------------------------------------------------------------------
+// Text.  One "#" line in front: the dimension, the bins, N, the replicas, the rows and the number of pair lines; then one line per
+// parameter: its name, lo, hi, below, above and its nbins counts; then one line per pair i < j, in row-major order: the two names
+// and the nbins * nbins counts, the first parameter's bin the slower index.  Doubles with 17 significant digits: reading them back
+// gives the bits that were written.
+struct corner_data {
+  int dim = 0, nbins = 0;
+  long long count = 0;
+  int replicas = 0, rows = 0;
+  std::vector<std::string> names;
+  histogram_estimator::result hist;   // lo, hi, h1, h2, below, above
+};
+inline void write_corner(const std::string& file, const histogram_estimator::result& r, int replicas, int rows, const std::vector<std::string>& names) {
+  const size_t D = (size_t)r.nfeat, B = (size_t)r.nbins, P = r.h2.empty() ? 0 : histogram_estimator::npairs(r.nfeat);
+  if (r.nfeat < 1 || r.nbins < 1 || r.h1.size() != D * B || r.h2.size() != P * B * B || r.lo.size() != D || r.hi.size() != D || r.below.size() != D || r.above.size() != D || names.size() != D) {
+    std::cout << "write_corner: " << B << " bins of " << D << " named parameters and of their pairs are needed" << std::endl; exit(1);
+  }
+  for (size_t i = 0; i < D; i++)
+    if (names[i].empty() || names[i].find_first_of(" \t\r\n#") != std::string::npos) { std::cout << "write_corner: parameter name '" << names[i] << "' must be one word without '#'" << std::endl; exit(1); }
+  std::ofstream out(file.c_str());
+  char buf[40];
+  out << "# posterior histograms: dim " << D << " nbins " << B << " N " << r.count << " replicas " << replicas << " rows " << rows << " pairs " << P << "\n";
+  for (size_t i = 0; i < D; i++) {
+    out << names[i];
+    snprintf(buf, sizeof buf, "%.17g", r.lo[i]); out << " " << buf;
+    snprintf(buf, sizeof buf, "%.17g", r.hi[i]); out << " " << buf;
+    out << " " << r.below[i] << " " << r.above[i];
+    for (size_t k = 0; k < B; k++) out << " " << r.h1[i * B + k];
+    out << "\n";
+  }
+  if (P) {
+    size_t p = 0;
+    for (size_t i = 0; i < D; i++)
+      for (size_t j = i + 1; j < D; j++, p++) {
+        out << names[i] << " " << names[j];
+        for (size_t k = 0; k < B * B; k++) out << " " << r.h2[p * B * B + k];
+        out << "\n";
+      }
+  }
+  out.close();
+  if (!out) { std::cout << "write_corner: cannot write '" << file << "'" << std::endl; exit(1); }
+}
+// refuses, with a message and exit(1): a missing file, a missing or malformed header, bins outside 1..128, another number of
+// parameter or pair lines than the header's, a line with too few or too many values, a range that is not two finite numbers with
+// lo < hi, a count that is not a non-negative whole number
+inline corner_data read_corner(const std::string& file) {
+  auto refuse = [&](const std::string& why) { std::cout << "read_corner: '" << file << "': " << why << std::endl; exit(1); };
+  std::ifstream in(file.c_str());
+  if (!in) refuse("cannot open the file");
+  corner_data d;
+  std::string line, word;
+  if (!std::getline(in, line)) refuse("the file is empty");
+  long long P = 0;
+  {
+    std::istringstream ss(line);
+    std::string w[4];
+    if (!(ss >> w[0] >> w[1] >> w[2] >> w[3]) || w[0] != "#" || w[1] != "posterior" || w[2] != "histograms:" || w[3] != "dim") refuse("the header line is missing");
+    std::string sb, sN, srep, srows, sp;
+    if (!(ss >> d.dim >> sb >> d.nbins >> sN >> d.count >> srep >> d.replicas >> srows >> d.rows >> sp >> P) || sb != "nbins" || sN != "N" || srep != "replicas" || srows != "rows" || sp != "pairs" || d.dim < 1 || (ss >> word))
+      refuse("the header line is malformed");
+    if (d.nbins < 1 || d.nbins > 128) refuse("the bins are outside 1..128");
+    if (P != 0 && P != (long long)histogram_estimator::npairs(d.dim)) refuse("the pairs are not those of the dimension");
+  }
+  const size_t D = (size_t)d.dim, B = (size_t)d.nbins;
+  histogram_estimator::result& r = d.hist;
+  r.nfeat = d.dim; r.nbins = d.nbins; r.count = d.count;
+  auto count_of = [&](const std::string& text) {
+    char* end = nullptr;
+    errno = 0;
+    const long long c = strtoll(text.c_str(), &end, 10);
+    if (end == text.c_str() || *end || errno || c < 0) refuse("not a count: '" + text + "'");
+    return (int64_t)c;
+  };
+  auto number_of = [&](const std::string& text) {
+    char* end = nullptr;
+    const double x = strtod(text.c_str(), &end);
+    if (end == text.c_str() || *end) refuse("not a number: '" + text + "'");
+    if (!std::isfinite(x)) refuse("an end of a range is not finite");
+    return x;
+  };
+  size_t lines = 0;
+  while (std::getline(in, line)) {
+    const size_t at = line.find_first_not_of(" \t\r");
+    if (at == std::string::npos || line[at] == '#') continue;
+    std::istringstream ss(line);
+    std::vector<std::string> words;
+    while (ss >> word) words.push_back(word);
+    if (lines < D) {
+      if (words.size() != 5 + B) { std::ostringstream m; m << "the line of '" << words[0] << "' holds " << words.size() << " words, not " << 5 + B; refuse(m.str()); }
+      d.names.push_back(words[0]);
+      r.lo.push_back(number_of(words[1]));
+      r.hi.push_back(number_of(words[2]));
+      if (!(r.lo.back() < r.hi.back())) refuse("a range is not lo < hi");
+      r.below.push_back(count_of(words[3]));
+      r.above.push_back(count_of(words[4]));
+      for (size_t k = 0; k < B; k++) r.h1.push_back(count_of(words[5 + k]));
+    } else {
+      if (words.size() != 2 + B * B) { std::ostringstream m; m << "the line of pair '" << words[0] << "' holds " << words.size() << " words, not " << 2 + B * B; refuse(m.str()); }
+      for (size_t k = 0; k < B * B; k++) r.h2.push_back(count_of(words[2 + k]));
+    }
+    lines++;
+  }
+  if (lines != D + (size_t)P) { std::ostringstream m; m << "expected " << D << " parameter lines and " << P << " pair lines, found " << lines; refuse(m.str()); }
+  return d;
+}
+
 // ---- the statistics of the proposal test (test_proposal.hh:350-502, 592-644) ------------------------------------------------------
 // kl_estimator: the k-NN Kullback-Leibler estimator of Perez-Cruz with k = 1 and the Gaussian "fake KL" from means and covariances,
 // on plain rows (sample i of a set at x + i * dim), as test_proposal states them with approx_nn = false.
@@ -3146,6 +3340,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     hist_rows = rows_per_chain;
     hist_rungs = coldest_rungs > 0 && coldest_rungs < Ntemps ? coldest_rungs : 0;
   }
+  int history_rows() const { return hist_rows; }   // the slots of the history ring (ptm_get_history's capacity)
   int history_rungs() const { return hist_rows > 0 ? ((hist_rungs > 0 && !de_built) ? hist_rungs : Ntemps) : 0; }   // (differential evolution on the device: every rung's ring)
   // Run `n` independent replicas of the ladder in one engine (call before initialize()).  Replica w uses the random
   // streams of walker w; every accessor below takes the replica as an optional last argument (default 0).  Multiples
@@ -4096,6 +4291,85 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
   bool quantiles_dev_last = false;
   bool quantiles_ran_on_device() const { return quantiles_dev_last; }   // the last posterior_quantiles of this ladder ran the device's kernels
+  // ---- the corner plot's counts over the replicas of rung `rung` (histogram_estimator above): every replica's newest `nrows` saved
+  // rows (< 0: all that every replica has), the first `nfeat` parameters, nbins bins between lo[f] and hi[f]; pairs: the 2-D
+  // histograms too.  The device counts on its own ring (ptm_histograms: the host estimator's integers) when the ring is there; with
+  // host-side proposals (the history is the host mirror) and with PTM_HOST_HISTOGRAMS=1 the counting is done here.
+  bool histograms_on_device_possible() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_HISTOGRAMS"); return v && *v && *v != '0'; }();   // (A/B: keep the host path)
+    return !(off || host_mode || hist_rows <= 0);
+  }
+  histogram_estimator::result posterior_histograms(const std::vector<double>& lo, const std::vector<double>& hi, int nbins, int rung = 0, int nfeat = -1, int nrows = -1,
+                                                   bool pairs = true) {
+    if (nfeat < 0 || nfeat > dim) nfeat = dim;
+    if (nrows < 0) nrows = rhat_rows_available(rung);
+    histograms_dev_last = false;
+    const size_t nf = (size_t)(nfeat > 0 ? nfeat : 0);
+    if (lo.size() < nf || hi.size() < nf) {
+      std::cout << "parallel_tempering_chains::posterior_histograms: lo and hi must hold a value for each of the " << nf << " parameters" << std::endl;
+      exit(1);
+    }
+    histogram_estimator::result r;
+    if (histograms_on_device_possible()) {
+      const size_t nb = (size_t)(nbins > 0 && nbins <= 128 ? nbins : 0), np = pairs && nf > 1 ? histogram_estimator::npairs(nfeat) : 0;
+      r.nfeat = nfeat; r.nbins = nbins; r.lo.assign(lo.begin(), lo.begin() + nf); r.hi.assign(hi.begin(), hi.begin() + nf);
+      r.h1.assign(nf * nb, 0); r.below.assign(nf, 0); r.above.assign(nf, 0);
+      if ((double)np * nb * nb <= 33554432.0) r.h2.assign(np * nb * nb, 0);   // (more than that is refused by the call)
+      int64_t count = 0, none = 0;
+      ptm_check(ptm_histograms(eng, rung, nfeat, nrows, nbins, lo.data(), hi.data(), r.h1.data(), pairs ? (r.h2.empty() ? &none : r.h2.data()) : nullptr, r.below.data(),
+                               r.above.data(), &count), "posterior_histograms");
+      r.count = count;
+      r.complete = true;
+      histograms_dev_last = true;
+      return r;
+    }
+    if (rung < 0 || rung >= (host_mode ? Ntemps : history_rungs()) || nfeat < 1 || nrows < 1 || nbins < 1 || nbins > 128) {
+      std::cout << "parallel_tempering_chains::posterior_histograms: rung " << rung << ", nfeat " << nfeat << ", nrows " << nrows << ", " << nbins << " bins (a recorded rung, 1..dim, at least 1, 1..128)" << std::endl;
+      exit(1);
+    }
+    for (size_t f = 0; f < nf; f++)
+      if (!histogram_estimator::edges_ok(lo[f], hi[f], nbins)) {
+        char buf[120];
+        snprintf(buf, sizeof buf, "%.17g to %.17g", lo[f], hi[f]);
+        std::cout << "parallel_tempering_chains::posterior_histograms: the range cannot hold nbins bins (parameter " << f << ": " << nbins + 1 << " edges from " << buf << " are not finite and strictly increasing)" << std::endl;
+        exit(1);
+      }
+    if (pairs && (double)histogram_estimator::npairs(nfeat) * nbins * nbins > 33554432.0) {
+      std::cout << "parallel_tempering_chains::posterior_histograms: " << nfeat << " parameters and " << nbins << " bins need more than 2^25 pair counters" << std::endl;
+      exit(1);
+    }
+    std::vector<int64_t> nh((size_t)Ntemps * W);
+    ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "posterior_histograms");
+    std::vector<long long> newest((size_t)W);
+    for (int w = 0; w < W; w++) {
+      const long long st = nh[(size_t)rung * W + w];
+      newest[(size_t)w] = st > 0 ? rhat_estimator::newest_row(st, add_every_N) : 0;
+      if (newest[(size_t)w] < nrows) { std::cout << "parallel_tempering_chains::posterior_histograms: replica " << w << " has saved " << newest[(size_t)w] << " rows behind its start state, fewer than nrows (" << nrows << ")" << std::endl; exit(1); }
+    }
+    histogram_estimator::reader read;
+    if (host_mode) read = [this, rung](int w, long long row, std::vector<double>& v) {   // (the mirror counts its initial draws in front)
+      const mirror_t& m = mirror[(size_t)rung * W + w];
+      const long long at = row - 1 + Ninit_rows;
+      if (row < 1 || (size_t)at >= m.rows()) return false;
+      v.assign(m.x.begin() + (size_t)at * dim, m.x.begin() + ((size_t)at + 1) * dim);
+      return true;
+    };
+    else {
+      read_history((size_t)rung * W + W - 1, "posterior_histograms");
+      read = [this, rung](int w, long long row, std::vector<double>& v) {
+        const size_t HC = (size_t)history_rungs() * W, cap = hist_rows;
+        const size_t o = (size_t)(row % (long long)cap) * HC + (size_t)rung * W + w;
+        if (row < 1 || hmeta[4 * o + 3] != (int32_t)row) return false;
+        v.assign(hx.begin() + o * dim, hx.begin() + (o + 1) * dim);
+        return true;
+      };
+    }
+    r = histogram_estimator::estimate(W, nfeat, nrows, newest.data(), read, std::vector<double>(lo.begin(), lo.begin() + nf), std::vector<double>(hi.begin(), hi.begin() + nf), nbins, pairs && nfeat > 1);
+    if (!r.complete) { std::cout << "parallel_tempering_chains::posterior_histograms: the saved history no longer holds the window (" << nrows << " rows)" << std::endl; exit(1); }
+    return r;
+  }
+  bool histograms_dev_last = false;
+  bool histograms_ran_on_device() const { return histograms_dev_last; }   // the last posterior_histograms of this ladder ran the device's kernels
   // swap_count / swap_accept_count (chain.hh:244-245)
   void swap_counts(std::vector<int64_t>& tries, std::vector<int64_t>& accepts) {
     std::vector<int64_t> t((size_t)W * (Ntemps > 1 ? Ntemps - 1 : 1)), a(t.size());
@@ -4435,8 +4709,10 @@ class ptmcmc_sampler : public bayes_sampler {
   int checkp_at_step;
   double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0, rhat_stop = -1;
   int nreplicas, replica_begin = 0, device = -1;
-  std::string covariance_out, quantiles_out;
+  std::string covariance_out, quantiles_out, corner_out;
   std::vector<double> quantile_probs;
+  int corner_bins = 20;
+  double corner_range = 1.0;
 
   // every flag read into a typed value (a flag without a value reads as T())
   template <class T> T flag(const std::string& name) { T v = T(); *optValue(name) >> v; return v; }
@@ -4467,6 +4743,11 @@ class ptmcmc_sampler : public bayes_sampler {
     covariance_out = flag<std::string>("covariance_out");
     quantiles_out = flag<std::string>("quantiles_out");
     if (!quantiles_out.empty()) quantile_probs = parse_quantile_probs(flag<std::string>("quantile_probs"));
+    corner_out = flag<std::string>("corner_out");
+    if (!corner_out.empty()) {
+      corner_bins = parse_corner_bins(flag<std::string>("corner_bins"));
+      corner_range = parse_corner_range(flag<std::string>("corner_range"));
+    }
     pt_stop_evid_err = flag<double>("pt_stop_evid_err");
     dpriormin = flag<double>("chain_dprior_min");
     nreplicas = optSet("replicas") ? flag<int>("replicas") : 1;
@@ -4560,6 +4841,9 @@ class ptmcmc_sampler : public bayes_sampler {
         {"covariance_out", "", "At the end of the run write the cold chains' pooled posterior mean and covariance to this file (what --covariance_file reads)."},
         {"quantiles_out", "", "At the end of the run write the cold chains' pooled posterior quantiles of every parameter to this file."},
         {"quantile_probs", "0.05,0.5,0.95", "The probabilities of --quantiles_out, separated by commas (1 to 32 values in [0, 1]). [0.05,0.5,0.95]"},
+        {"corner_out", "", "At the end of the run write the cold chains' corner-plot counts -- the histogram of every parameter and of every pair of parameters -- to this file."},
+        {"corner_bins", "20", "The bins of each axis of --corner_out (1 to 128). [20]"},
+        {"corner_range", "1", "The share of each parameter's samples the axes of --corner_out span, centred (corner's range fraction; 1: minimum to maximum). [1]"},
     };
     for (size_t i = 0; i < sizeof flags / sizeof flags[0]; i++) addOption(flags[i].name, flags[i].about, flags[i].preset);
   }
@@ -4887,7 +5171,7 @@ class ptmcmc_sampler : public bayes_sampler {
       cc->keep_history((int)de_rows, Nptc);
       cc->use_device_de(true);
     } else {
-      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0 || !covariance_out.empty() || !quantiles_out.empty()) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
+      cc->keep_history(2 + 2 * ((ess_stop > 0 || rhat_stop > 0 || !covariance_out.empty() || !quantiles_out.empty() || !corner_out.empty()) ? std::max(Nevery, Nstep) : Nevery) / std::max(1, save_every), dn);
     }
     cc->set_replica_range(replica_begin, nreplicas, device);
     if (pt_evolve_rate > 0) cc->evolve_temps(pt_evolve_rate, pt_evolve_lpost_cut);   // ptmcmc.cc:512
@@ -4997,6 +5281,7 @@ class ptmcmc_sampler : public bayes_sampler {
     for (size_t k = 0; k < out.size(); k++) *out[k] << "\n" << std::endl;   // ptmcmc.cc:665
     if (!covariance_out.empty()) write_covariance(covariance_out);
     if (!quantiles_out.empty()) write_quantiles(quantiles_out);
+    if (!corner_out.empty()) write_corner(corner_out);
     std::cout << "Finished running chain " << ic << "." << std::endl;
     return 0;
   }
@@ -5054,6 +5339,46 @@ class ptmcmc_sampler : public bayes_sampler {
     ptmgpu::write_quantiles(file, r, nrep, nrows, names);
     std::cout << "Posterior quantiles over " << nrep << " replicas, " << nrows << " rows: " << npar << " parameters at " << quantile_probs.size() << " probabilities"
               << (cc->quantiles_ran_on_device() ? " (device)" : " (host)") << ", written to " << file << std::endl;
+  }
+  // --corner_bins: a whole number in 1..128; --corner_range: a number in (0, 1].  Refused with a message and exit(1) otherwise
+  static int parse_corner_bins(const std::string& text) {
+    char* end = nullptr;
+    const long n = strtol(text.c_str(), &end, 10);
+    if (text.empty() || end == text.c_str() || *end || n < 1 || n > 128) { std::cout << "ptmcmc_sampler: --corner_bins='" << text << "': a whole number in 1..128 is needed" << std::endl; exit(1); }
+    return (int)n;
+  }
+  static double parse_corner_range(const std::string& text) {
+    char* end = nullptr;
+    const double c = strtod(text.c_str(), &end);
+    if (text.empty() || end == text.c_str() || *end || !(c > 0.0 && c <= 1.0)) { std::cout << "ptmcmc_sampler: --corner_range='" << text << "': a number in (0, 1] is needed" << std::endl; exit(1); }
+    return c;
+  }
+  // the probabilities whose quantiles are the ends of an axis that spans the share c of the samples: 0 and 1 for c = 1
+  static std::vector<double> corner_probs(double c) { return c >= 1.0 ? std::vector<double>{0.0, 1.0} : std::vector<double>{(1.0 - c) / 2.0, (1.0 + c) / 2.0}; }
+  // a parameter whose two ends are equal gets lo - 0.5, hi + 0.5 (numpy's rule for an empty range)
+  static void widen_equal_range(double& lo, double& hi) {
+    if (lo == hi) { lo -= 0.5; hi += 0.5; }
+  }
+  // The cold rung's corner-plot counts over the newest (1 - burn_frac) share of the saved rows every replica has, the axes from
+  // the sample's own quantiles, in the format read_corner reads.
+  void write_corner(const std::string& file) {
+    const int nrep = cc->replicas();
+    const int nrows = (int)((1.0 - nburn_frac) * cc->rhat_rows_available(0));
+    if (nrows < 1) { std::cout << "ptmcmc_sampler::write_corner: too few saved rows (" << nrows << " of " << nrep << " replicas); '" << file << "' is not written." << std::endl; return; }
+    const int npar = chain_prior->getDim();
+    const quantile_estimator::result q = cc->posterior_quantiles(corner_probs(corner_range), 0, -1, nrows);
+    std::vector<double> lo((size_t)npar), hi((size_t)npar);
+    for (int i = 0; i < npar; i++) {
+      lo[(size_t)i] = q.q[(size_t)i];
+      hi[(size_t)i] = q.q[(size_t)npar + i];
+      widen_equal_range(lo[(size_t)i], hi[(size_t)i]);
+    }
+    const histogram_estimator::result r = cc->posterior_histograms(lo, hi, corner_bins, 0, -1, nrows, true);
+    std::vector<std::string> names;
+    for (int i = 0; i < npar; i++) names.push_back(chain_prior->get_space() ? chain_prior->get_space()->get_name(i) : std::string("[unnamed]"));
+    ptmgpu::write_corner(file, r, nrep, nrows, names);
+    std::cout << "Posterior histograms over " << nrep << " replicas, " << nrows << " rows: " << npar << " parameters, " << histogram_estimator::npairs(npar) << " pairs, " << corner_bins << " bins"
+              << (cc->histograms_ran_on_device() ? " (device)" : " (host)") << ", written to " << file << std::endl;
   }
   // ptmcmc_sampler::analyze (ptmcmc.cc:681-755): the 1-sigma sample files of the reference need bayes_likelihood::write /
   // writeFine (signal / data modelling, out of this build's scope); what remains is its summary line
