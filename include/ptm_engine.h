@@ -635,6 +635,53 @@ int ptm_moments_series(int device, const double* series, int64_t n, int nseries,
 /* the rows of a window one staging tile of the covariance kernel holds (what a test builds its edge sizes around); 0: nfeat outside 1..128 */
 int ptm_moments_tile_rows(int nfeat);
 
+/* ---- every rung's Gaussian proposal from its own sampled covariance, on the device -------------------------------------------
+ * What user_gaussian_prop::check_update / reset_dist do for one chain in the reference (proposal_distribution.cc:340-441), for a
+ * range of recorded rungs at once: the moments and the eigen-decompositions do not leave the device.
+ *
+ * ptm_moments_rungs is ptm_moments for the local rungs first_rung .. first_rung + n_rungs - 1, all below history_rungs: rung r's
+ * answers at mean[r*nfeat], cov[r*nfeat*nfeat], var[r*nfeat] are the bits ptm_moments gives for that rung (the same window rule, the
+ * same three-level sequential sums, the same two passes: the same kernels, one rung after the other on the engine's stream), and the
+ * call waits once.  It refuses what ptm_moments refuses, for the whole call: when one rung's window is not there every output is
+ * left untouched.  count: N = W * nrows, the same for every rung.
+ *
+ * ptm_eigen_factors restates the facade's gaussian_prop::eigen_factor (ptmcmc_amd/host/ptmcmc_gpu.hh) for n_mat symmetric n x n
+ * matrices, row-major, one after the other in cov; no engine needed.  For every matrix:
+ *  - detail::jacobi_eigen as written there: Q = 1; at most 100 sweeps; a sweep begins with off = the sequential sum over p < q, in that
+ *    order, of A[p][q]^2 and ends the iteration when off < 1e-300; then for every p < q in that order, unless |A[p][q]| < 1e-300:
+ *      theta = (A[q][q] - A[p][p]) / (2 A[p][q]);  t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta^2 + 1));  c = 1 / sqrt(t^2 + 1);
+ *      s = t c;  for every k: (A[k][p], A[k][q]) <- (c a - s b, s a + c b);  then for every k the same on (A[p][k], A[q][k]);  then for
+ *      every k the same on (Q[k][p], Q[k][q]).  Both triangles of the full matrix are rotated: nothing is mirrored.
+ *  - its swap sort: order = 0 .. n-1; for i, for j > i: if A[order[j]][order[j]] < A[order[i]][order[i]] swap the two entries;
+ *    lambda[j] = A[order[j]][order[j]], V[i][j] = Q[i][order[j]].
+ *  - factors[i*n + j] = V[i][j] * sqrt(lambda[j] > 0 ? lambda[j] : 0).
+ * Operations run as written (correctly rounded roots and quotients, multiply then add, no contraction): factors and lambda carry the
+ * host's bits, NaN where the host has NaN.  sweeps: the sweeps that rotated (100: the limit was reached).  1 <= n <= 128, n_mat >= 1.
+ * PTM_ERR_INVALID: a null cov or factors, n or n_mat out of range.
+ *
+ * ptm_adapt_proposals replaces the Gaussian factor of every rung of the range by one made from that rung's own samples: every walker's
+ * newest nrows saved rows, all D parameters, pooled as ptm_moments pools them.
+ *  - PTM_PROP_DENSE: factor = scale * F, one multiply per element after F is formed, F the eigen factor (above) of the rung's pooled
+ *    covariance.  D <= 128.
+ *  - PTM_PROP_DIAG: sigma_d = scale * sqrt(var_d), ptm_moments' variances; no covariance is formed: any D.
+ * status[r]: 0: installed; 1: kept, an entry of the covariance (DIAG: a variance) is not finite; 2: kept, the smallest eigenvalue
+ * (DIAG: a variance) is not above 0.  A kept rung goes on with the factor it had.  An installed rung is in exactly the state
+ * ptm_set_proposal_rung(e, r, factor, -1) leaves it in (the two share their packing).  factors_out, when given, receives what was
+ * computed for every rung, kept ones included: [n_rungs][D*D] row-major (DENSE) or [n_rungs][D] (DIAG).  one_d_frac, mixtures, adaptive
+ * sets' state, differential evolution and the prior-draw member are untouched.  A common choice of scale is 2.38 / sqrt(D).
+ * PTM_ERR_INVALID: a null engine or status; no ptm_set_proposals yet; a range that is not inside history_rungs; scale not finite or not
+ * above 0; nrows < 1 or W * nrows < 2; whatever ptm_moments refuses about windows; user proposals, host-side or device, are set (the
+ * factors are not read then).  PTM_ERR_UNSUPPORTED: PTM_PROP_LOWER; DENSE with D > 128; a call between ptm_batch_begin and
+ * ptm_batch_end.  Everything is checked before anything changes: after a failure the engine steps on as before (but for a failed copy of
+ * the device runtime during the install itself, PTM_ERR_HIP: rungs installed before it stay installed and status is not written).  On a rung shard the
+ * rungs are the local ones; on a walker split every engine adapts to its own walkers. */
+int ptm_moments_rungs(ptm_engine* e, int first_rung, int n_rungs, int nfeat, int nrows, double* mean /*[n_rungs*nfeat]*/,
+                      double* cov /*[n_rungs*nfeat*nfeat] or NULL*/, double* var /*[n_rungs*nfeat] or NULL*/, int64_t* count /*N, or NULL*/);
+int ptm_eigen_factors(int device, const double* cov /*[n_mat][n*n] row-major*/, int n_mat, int n, double* factors /*[n_mat][n*n] row-major*/,
+                      double* lambda /*[n_mat][n] or NULL*/, int32_t* sweeps /*[n_mat] or NULL*/);
+int ptm_adapt_proposals(ptm_engine* e, int first_rung, int n_rungs, int nrows, double scale, int32_t* status /*[n_rungs]*/,
+                        double* factors_out /*[n_rungs][D*D | D] or NULL*/);
+
 /* ---- exact posterior quantiles of a rung on the device ----------------------------------------------------------------------
  * What every user writes down at the end of a run: the median and the credible interval of each parameter -- the right summary of
  * a skewed or two-humped marginal, where the mean and the variance are not.  As the facade's quantile_estimator states it

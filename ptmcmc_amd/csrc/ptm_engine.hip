@@ -23,6 +23,7 @@
 #include "ptm_de_mfma_kernel.hpp"
 #include "ptm_devlike_kernels.hpp"
 #include "ptm_devprop_kernels.hpp"
+#include "ptm_eigen_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
 #include "ptm_evidence_kernels.hpp"
 #include "ptm_histograms_kernels.hpp"
@@ -238,6 +239,9 @@ struct ptm_engine {
   void* ess_ws = nullptr;
   size_t ess_ws_bytes = 0;
   int ess_on_device = 0;   // the last ptm_ess_* call of this engine ran the kernels
+  // ptm_adapt_proposals: the eigen kernel's workspace (factors, eigenvalues, status, the rotations of dimensions above 64), grown on demand
+  void* eig_ws = nullptr;
+  size_t eig_ws_bytes = 0;
   // timing
   hipEvent_t t0 = nullptr, t1 = nullptr;
   std::vector<hipEvent_t> kev;  // pairs
@@ -549,7 +553,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
                   e->bhi, e->ptype, e->bmin, e->bmax, e->plo, e->phi, e->pcoef, e->P2, e->mean, e->beta, e->prop, e->prop_tiles, e->P2_tiles, e->box_row, e->onedfrac, e->mix, e->beta_w, e->betaC, e->beta_add, e->hist.beta, e->xprop, e->lprior_new, e->llike_new, e->hastings, e->htype, e->hvalid, e->acc_out, e->cidx, e->ccnt, e->pidx, e->pcnt, e->pf_flag, e->pf_counts, e->pf_margin,
                   e->pub_x, e->lad_flags, e->lad_prof, e->shard_ends, e->redo_flag, e->sums, e->de_init, e->de_hast, e->de_type,
                   e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
-                  e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws,
+                  e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws, e->eig_ws,
                   e->dp_xcur, e->dp_xnew, e->dp_hast_k, e->dp_rung, e->dp_walker, e->dp_type_k, e->dp_valid_k, e->dp_acc_k, e->dp_count, e->dp_rows, e->dp_chunks,
                   e->dp_xprop, e->dp_hastings, e->dp_htype, e->dp_hvalid, e->dp_acc_out};
   for (void* p : ptrs)
@@ -1295,14 +1299,17 @@ extern "C" int ptm_set_proposal_de(ptm_engine* e, const ptm_de_params* q, int n_
   return PTM_OK;
 }
 
-// One rung's factor replaced between steps -- what user_gaussian_prop::check_update achieves in the reference when its
-// callback returns a new covariance for a chain (proposal_distribution.cc:406-441, reset_dist :340-403).  Same kind and
-// storage as the factors set by ptm_set_proposals; one_d_frac < 0 keeps the rung's current value.
-extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double* factor, double one_d_frac) {
-  SETTLE(e);
-  if (!e || !factor) return fail(PTM_ERR_INVALID, "null argument");
-  if (!e->have_prop) return fail(PTM_ERR_INVALID, "set all proposals first (ptm_set_proposals)");
-  if (local_rung < 0 || local_rung >= e->nloc) return fail(PTM_ERR_INVALID, "rung out of the shard");
+// The packing of one rung's factor, shared by ptm_set_proposal_rung and ptm_adapt_proposals: the padded column-major copy, the
+// matrix-core tiles of the 32 / 64 / 128 padded dimensions, the box pre-pass's sigmas and margins, pf_dirty.
+// pending: null: every copy is waited for (one rung); else the copies are only enqueued and their host images are kept in *pending
+// until the caller has waited for the stream once (many rungs: no wait per rung).
+static int install_rung_factor(ptm_engine* e, int local_rung, const double* factor, std::vector<std::vector<double> >* pending = nullptr) {
+  auto put = [e, pending](double* dst, std::vector<double>& img) -> int {
+    if (!pending) return upload(dst, img.data(), img.size(), e->stream);
+    pending->emplace_back(std::move(img));   // (a vector's buffer stays where it is when the vector is moved)
+    HIPCHK(hipMemcpyAsync(dst, pending->back().data(), pending->back().size() * sizeof(double), hipMemcpyDefault, e->stream));
+    return PTM_OK;
+  };
   const int D = e->D, DP = e->DP, kind = e->prop_kind == KIND_DIAG ? PTM_PROP_DIAG : (e->prop_kind == KIND_LOWER ? PTM_PROP_LOWER : PTM_PROP_DENSE);
   std::vector<double> packed((size_t)e->prop_stride, 0.0);
   if (kind == PTM_PROP_DIAG) {
@@ -1316,7 +1323,7 @@ extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double
       }
   }
   int rc;
-  if ((rc = upload(e->prop + (size_t)local_rung * e->prop_stride, packed.data(), packed.size(), e->stream))) return rc;
+  if ((rc = put(e->prop + (size_t)local_rung * e->prop_stride, packed))) return rc;
   if (DP == 32) {
     std::vector<double> tiles(16 * 64, 0.0);
     for (int t = 0; t < 16; ++t) {
@@ -1328,7 +1335,7 @@ extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double
             tiles[(size_t)t * 64 + 16 * k + i] = kind == PTM_PROP_DIAG ? (row == col ? factor[row] : 0.0) : factor[(size_t)row * D + col];
         }
     }
-    if ((rc = upload(e->prop_tiles + (size_t)local_rung * 16 * 64, tiles.data(), tiles.size(), e->stream))) return rc;
+    if ((rc = put(e->prop_tiles + (size_t)local_rung * 16 * 64, tiles))) return rc;
   }
   if (DP == 64 || DP == 128) {
     const int NT = DP / 16, ntile = NT * NT * 4;
@@ -1342,11 +1349,23 @@ extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double
             tiles[(size_t)t * 64 + 16 * k + i] = kind == PTM_PROP_DIAG ? (row == col ? factor[row] : 0.0) : factor[(size_t)row * D + col];
         }
     }
-    if ((rc = upload(e->prop_tiles + (size_t)local_rung * ntile * 64, tiles.data(), tiles.size(), e->stream))) return rc;
+    if ((rc = put(e->prop_tiles + (size_t)local_rung * ntile * 64, tiles))) return rc;
   }
   prefilter_sigmas(kind == PTM_PROP_DIAG, factor, D, &e->pf_sigma[(size_t)local_rung * PREFILTER_DIMS]);
   prefilter_margins(kind == PTM_PROP_DIAG, factor, D, &e->pf_margin_nat[(size_t)local_rung * PREFILTER_DIMS]);
   e->pf_dirty = true;
+  return PTM_OK;
+}
+// One rung's factor replaced between steps -- what user_gaussian_prop::check_update achieves in the reference when its
+// callback returns a new covariance for a chain (proposal_distribution.cc:406-441, reset_dist :340-403).  Same kind and
+// storage as the factors set by ptm_set_proposals; one_d_frac < 0 keeps the rung's current value.
+extern "C" int ptm_set_proposal_rung(ptm_engine* e, int local_rung, const double* factor, double one_d_frac) {
+  SETTLE(e);
+  if (!e || !factor) return fail(PTM_ERR_INVALID, "null argument");
+  if (!e->have_prop) return fail(PTM_ERR_INVALID, "set all proposals first (ptm_set_proposals)");
+  if (local_rung < 0 || local_rung >= e->nloc) return fail(PTM_ERR_INVALID, "rung out of the shard");
+  int rc = install_rung_factor(e, local_rung, factor);
+  if (rc) return rc;
   if (one_d_frac >= 0) {
     if (one_d_frac > 1) return fail(PTM_ERR_INVALID, "oneDfrac must be in [0,1]");
     if ((rc = upload(e->onedfrac + local_rung, &one_d_frac, 1, e->stream))) return rc;
@@ -3576,13 +3595,16 @@ static int ess_report_run(const int* steps_of, int steps_common, int nseries, in
 }
 
 // the saved history of local rung `rung` as the kernels' source; steps_of: every walker's own count of add_state calls
-static int ess_ring_source(ptm_engine* e, int rung, int nfeat, EssSrc* src, std::vector<int>* steps_of) {
+// nh: every chain's count of add_state calls, fetched by the caller (ess_ring_counts) -- once for a call that reads many rungs
+static int ess_ring_counts(ptm_engine* e, std::vector<int64_t>* nh) {
+  if (!e->hist.rungs) return fail(PTM_ERR_INVALID, "this engine keeps no history (ptm_config.history_rungs)");
+  nh->resize((size_t)e->Nc);
+  return ptm_get_array(e, PTM_ARR_NHIST, nh->data());
+}
+static int ess_ring_source_of(ptm_engine* e, const std::vector<int64_t>& nh, int rung, int nfeat, EssSrc* src, std::vector<int>* steps_of) {
   if (!e->hist.rungs) return fail(PTM_ERR_INVALID, "this engine keeps no history (ptm_config.history_rungs)");
   if (rung < 0 || rung >= e->hist.rungs) return fail(PTM_ERR_INVALID, "rung %d keeps no history (history_rungs = %d)", rung, e->hist.rungs);
   if (nfeat < 1 || nfeat > e->D) return fail(PTM_ERR_INVALID, "nfeat must be in 1..dim (%d)", e->D);
-  std::vector<int64_t> nh((size_t)e->Nc);
-  int rc = ptm_get_array(e, PTM_ARR_NHIST, nh.data());
-  if (rc) return rc;
   steps_of->resize((size_t)e->W);
   bool same = true;
   for (int w = 0; w < e->W; ++w) {
@@ -3603,6 +3625,15 @@ static int ess_ring_source(ptm_engine* e, int rung, int nfeat, EssSrc* src, std:
   src->first_row = 1;
   src->permuted = (e->DP == 32 || e->DP == 64 || e->DP == 128) ? 1 : 0;
   return PTM_OK;
+}
+static int ess_ring_source(ptm_engine* e, int rung, int nfeat, EssSrc* src, std::vector<int>* steps_of) {
+  if (!e->hist.rungs) return fail(PTM_ERR_INVALID, "this engine keeps no history (ptm_config.history_rungs)");
+  if (rung < 0 || rung >= e->hist.rungs) return fail(PTM_ERR_INVALID, "rung %d keeps no history (history_rungs = %d)", rung, e->hist.rungs);
+  if (nfeat < 1 || nfeat > e->D) return fail(PTM_ERR_INVALID, "nfeat must be in 1..dim (%d)", e->D);
+  std::vector<int64_t> nh;
+  int rc = ess_ring_counts(e, &nh);
+  if (rc) return rc;
+  return ess_ring_source_of(e, nh, rung, nfeat, src, steps_of);
 }
 
 extern "C" int ptm_ess_windowed(ptm_engine* e, int rung, int nfeat, int width, int every, int burn, double* ess, int32_t* nwin) {
@@ -3830,10 +3861,15 @@ extern "C" int ptm_rhat_series(int device, const double* series, int64_t n, int 
 // The per-walker pair sums of the cross kernel are made and folded into their blocks' sums a group of walkers at a time (whole
 // blocks, MOM_WS_BYTES of workspace at most; PTM_MOMENTS_GROUP=n walkers in the environment forces the size: tests).
 static constexpr size_t MOM_WS_BYTES = (size_t)256 << 20;
-static int moments_run(const char* who, hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat,
-                       int nrows, double* mean, double* cov, double* var, double* walker_sum, int64_t* count) {
-  const int64_t N = (int64_t)W * nrows;
-  const size_t F = (size_t)nfeat, lanes = (size_t)W * F, P = cov ? F * (F + 1) / 2 : 0, nblocks = ((size_t)W + MOM_GROUP - 1) / MOM_GROUP;
+// One call's plan: the walkers' sums, pair sums and blocks' sums (used by one rung after the other, in stream order) and every rung's
+// own means, answers and flag, rung r at d_mean + r * F, d_out + r * out_stride, d_flag + r.
+struct MomPlan {
+  size_t F = 0, lanes = 0, P = 0, nblocks = 0, group = 0, out_stride = 0;
+  double *d_sw = nullptr, *d_cw = nullptr, *d_blk = nullptr, *d_mean = nullptr, *d_out = nullptr;
+  int* d_flag = nullptr;
+};
+static int moments_plan(hipStream_t st, void** ws, size_t* ws_bytes, int W, int nfeat, bool cov, bool var, int n_rungs, MomPlan* pl) {
+  const size_t F = (size_t)nfeat, lanes = (size_t)W * F, P = cov ? F * (F + 1) / 2 : 0, nblocks = ((size_t)W + MOM_GROUP - 1) / MOM_GROUP, R = (size_t)n_rungs;
   size_t group = (size_t)W;   // walkers whose pair sums the workspace holds at a time
   if (cov) {
     const char* v = getenv("PTM_MOMENTS_GROUP");
@@ -3842,20 +3878,30 @@ static int moments_run(const char* who, hipStream_t st, void** ws, size_t* ws_by
     group = std::max((size_t)MOM_GROUP, group / MOM_GROUP * MOM_GROUP);
     group = std::min(group, nblocks * MOM_GROUP);
   }
-  const size_t n_walker = cov ? group * P : (var ? lanes : 0), n_block = nblocks * std::max(F, P);
+  const size_t n_walker = cov ? group * P : (var ? lanes : 0), n_block = nblocks * std::max(F, P), out_stride = cov ? F * F : F;
   const size_t o_sw = 0, o_cw = o_sw + ess_align(lanes * 8), o_blk = o_cw + ess_align(n_walker * 8), o_mean = o_blk + ess_align(n_block * 8),
-               o_out = o_mean + ess_align(F * 8), o_flag = o_out + ess_align((cov ? F * F : F) * 8), total = o_flag + 256;
+               o_out = o_mean + ess_align(R * F * 8), o_flag = o_out + ess_align(R * out_stride * 8), total = o_flag + std::max((size_t)256, ess_align(R * 4));
   if (*ws_bytes < total) {
     if (*ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
     HIPCHK(hipMalloc(ws, total));
     *ws_bytes = total;
   }
   unsigned char* b = (unsigned char*)*ws;
-  double *d_sw = (double*)(b + o_sw), *d_cw = (double*)(b + o_cw), *d_blk = (double*)(b + o_blk), *d_mean = (double*)(b + o_mean), *d_out = (double*)(b + o_out);
-  int* d_flag = (int*)(b + o_flag);
+  pl->F = F; pl->lanes = lanes; pl->P = P; pl->nblocks = nblocks; pl->group = group; pl->out_stride = out_stride;
+  pl->d_sw = (double*)(b + o_sw); pl->d_cw = (double*)(b + o_cw); pl->d_blk = (double*)(b + o_blk); pl->d_mean = (double*)(b + o_mean); pl->d_out = (double*)(b + o_out);
+  pl->d_flag = (int*)(b + o_flag);
+  HIPCHK(hipMemsetAsync(pl->d_flag, 0, R * 4, st));
+  return PTM_OK;
+}
+// the kernels of rung r of the plan, on the stream
+static int moments_launch(hipStream_t st, const MomPlan& pl, int r, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat, int nrows, bool cov,
+                          bool var) {
+  const int64_t N = (int64_t)W * nrows;
+  const size_t F = pl.F, lanes = pl.lanes, P = pl.P, nblocks = pl.nblocks, group = pl.group;
+  double *d_sw = pl.d_sw, *d_cw = pl.d_cw, *d_blk = pl.d_blk, *d_mean = pl.d_mean + (size_t)r * F, *d_out = pl.d_out + (size_t)r * pl.out_stride;
+  int* d_flag = pl.d_flag + r;
   const dim3 T(MOM_THREADS);
   auto blocks_of = [](size_t n) { return dim3((unsigned)((n + MOM_THREADS - 1) / MOM_THREADS)); };
-  HIPCHK(hipMemsetAsync(d_flag, 0, 4, st));
   // the means: s_w, S_b, S / N
   if (wrapped) hipLaunchKernelGGL(moments_sum_kernel<true>, blocks_of(lanes), T, 0, st, src, d_nhist, W, nfeat, nrows, (const double*)nullptr, d_sw, d_flag);
   else hipLaunchKernelGGL(moments_sum_kernel<false>, blocks_of(lanes), T, 0, st, src, d_nhist, W, nfeat, nrows, (const double*)nullptr, d_sw, d_flag);
@@ -3892,24 +3938,54 @@ static int moments_run(const char* who, hipStream_t st, void** ws, size_t* ws_by
     hipLaunchKernelGGL(moments_final_kernel, blocks_of(F), T, 0, st, (int)nblocks, nfeat, (const double*)d_blk, (double)(N - 1), 0, d_out);
     HIPCHK(hipGetLastError());
   }
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+  return PTM_OK;
+}
+// the flags of the plan's n_rungs rungs: one wait; any raised: the window is not there
+static int moments_flags(const char* who, hipStream_t st, const MomPlan& pl, int n_rungs, int cap, int nrows) {
+  std::vector<int> flag((size_t)n_rungs, 0);
+  HIPCHK(hipMemcpyAsync(flag.data(), pl.d_flag, (size_t)n_rungs * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (flag) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, src.cap, nrows);
-  HIPCHK(hipMemcpyAsync(mean, d_mean, F * 8, hipMemcpyDeviceToHost, st));
-  if (cov) HIPCHK(hipMemcpyAsync(cov, d_out, F * F * 8, hipMemcpyDeviceToHost, st));
-  else if (var) HIPCHK(hipMemcpyAsync(var, d_out, F * 8, hipMemcpyDeviceToHost, st));
-  if (walker_sum) HIPCHK(hipMemcpyAsync(walker_sum, d_sw, lanes * 8, hipMemcpyDeviceToHost, st));
+  for (int f : flag)
+    if (f) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, cap, nrows);
+  return PTM_OK;
+}
+static int moments_run(const char* who, hipStream_t st, void** ws, size_t* ws_bytes, EssSrc src, const unsigned int* d_nhist, bool wrapped, int W, int nfeat,
+                       int nrows, double* mean, double* cov, double* var, double* walker_sum, int64_t* count) {
+  MomPlan pl;
+  int rc;
+  if ((rc = moments_plan(st, ws, ws_bytes, W, nfeat, cov != nullptr, var != nullptr, 1, &pl))) return rc;
+  if ((rc = moments_launch(st, pl, 0, src, d_nhist, wrapped, W, nfeat, nrows, cov != nullptr, var != nullptr))) return rc;
+  if ((rc = moments_flags(who, st, pl, 1, src.cap, nrows))) return rc;
+  const size_t F = pl.F;
+  HIPCHK(hipMemcpyAsync(mean, pl.d_mean, F * 8, hipMemcpyDeviceToHost, st));
+  if (cov) HIPCHK(hipMemcpyAsync(cov, pl.d_out, F * F * 8, hipMemcpyDeviceToHost, st));
+  else if (var) HIPCHK(hipMemcpyAsync(var, pl.d_out, F * 8, hipMemcpyDeviceToHost, st));
+  if (walker_sum) HIPCHK(hipMemcpyAsync(walker_sum, pl.d_sw, pl.lanes * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (cov && var)
     for (size_t f = 0; f < F; ++f) var[f] = cov[f * F + f];   // (the diagonal pair's quotient: the same bits)
-  if (count) *count = N;
+  if (count) *count = (int64_t)W * nrows;
   return PTM_OK;
 }
 static int moments_shape(const char* who, int nfeat_max, int nfeat, int nrows, const double* cov) {
   if (nfeat < 1 || nfeat > nfeat_max) return fail(PTM_ERR_INVALID, "%s: nfeat must be in 1..%d", who, nfeat_max);
   if (nrows < 1) return fail(PTM_ERR_INVALID, "%s: nrows must be at least 1", who);
   if (cov && nfeat > MOM_COV_NFEAT_MAX) return fail(PTM_ERR_UNSUPPORTED, "%s: the covariance is offered up to %d features (pass cov = NULL for the mean and the variances)", who, MOM_COV_NFEAT_MAX);
+  return PTM_OK;
+}
+// the window of one rung against its chains' counts: what ptm_moments refuses; *wrapped: the ring no longer holds every row since the start
+static int moments_window_check(const char* who, const ptm_engine* e, const EssSrc& src, const std::vector<int>& steps_of, int nrows, bool* wrapped) {
+  if ((int64_t)e->W * nrows < 2) return fail(PTM_ERR_INVALID, "%s: at least two samples are needed (walkers x nrows = %lld)", who, (long long)e->W * nrows);
+  long long newest_min = 0, newest_max = 0;
+  for (int w = 0; w < e->W; ++w) {
+    const long long st = steps_of.empty() ? src.steps : steps_of[(size_t)w];
+    const long long newest = st > 0 ? 1 + (st - 1) / src.add_every : 0;   // (= the saved rows behind the start state)
+    if (!w || newest < newest_min) newest_min = newest;
+    if (!w || newest > newest_max) newest_max = newest;
+  }
+  if (newest_min < nrows) return fail(PTM_ERR_INVALID, "%s: a chain of the rung has saved %lld rows behind its start state, fewer than nrows (%d)", who, newest_min, nrows);
+  if (nrows > src.cap) return fail(PTM_ERR_INVALID, "%s: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", who, src.cap, nrows);
+  *wrapped = newest_max >= (long long)src.cap;
   return PTM_OK;
 }
 extern "C" int ptm_moments(ptm_engine* e, int rung, int nfeat, int nrows, double* mean, double* cov, double* var, double* walker_sum, int64_t* count) {
@@ -3921,18 +3997,62 @@ extern "C" int ptm_moments(ptm_engine* e, int rung, int nfeat, int nrows, double
   std::vector<int> steps_of;
   if ((rc = ess_ring_source(e, rung, nfeat, &src, &steps_of))) return rc;   // (settles a pending ladder launch and the uncounted adds first)
   if ((double)e->W * nfeat > 2.0e9 || (double)e->W * nrows > 4.0e18) return fail(PTM_ERR_INVALID, "ptm_moments: bad shape");
-  if ((int64_t)e->W * nrows < 2) return fail(PTM_ERR_INVALID, "ptm_moments: at least two samples are needed (walkers x nrows = %lld)", (long long)e->W * nrows);
-  long long newest_min = 0, newest_max = 0;
-  for (int w = 0; w < e->W; ++w) {
-    const long long st = steps_of.empty() ? src.steps : steps_of[(size_t)w];
-    const long long newest = st > 0 ? 1 + (st - 1) / src.add_every : 0;   // (= the saved rows behind the start state)
-    if (!w || newest < newest_min) newest_min = newest;
-    if (!w || newest > newest_max) newest_max = newest;
-  }
-  if (newest_min < nrows) return fail(PTM_ERR_INVALID, "ptm_moments: a chain of the rung has saved %lld rows behind its start state, fewer than nrows (%d)", newest_min, nrows);
-  if (nrows > src.cap) return fail(PTM_ERR_INVALID, "ptm_moments: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", src.cap, nrows);
-  return moments_run("ptm_moments", e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->nhist + (size_t)rung * e->W, newest_max >= (long long)src.cap, e->W, nfeat, nrows,
+  bool wrapped = false;
+  if ((rc = moments_window_check("ptm_moments", e, src, steps_of, nrows, &wrapped))) return rc;
+  return moments_run("ptm_moments", e->stream, &e->ess_ws, &e->ess_ws_bytes, src, e->nhist + (size_t)rung * e->W, wrapped, e->W, nfeat, nrows,
                      mean, cov, var, walker_sum, count);
+}
+// ptm_moments for a range of rungs: the kernels of one rung after the other on the stream, every rung's answers kept in the workspace,
+// nothing waited for.  *plan: where they lie (ptm_adapt_proposals reads them there) and the flags the caller has to look at (a
+// raised one: a window's row was lost).  Checks every rung's window against the counts before anything is launched.
+static int moments_rungs_device(const char* who, ptm_engine* e, int first_rung, int n_rungs, int nfeat, int nrows, bool cov, bool var, MomPlan* plan) {
+  const double some = 0;
+  int rc = moments_shape(who, e->D, nfeat, nrows, cov ? &some : nullptr);
+  if (rc) return rc;
+  std::vector<int64_t> nh;
+  if ((rc = ess_ring_counts(e, &nh))) return rc;   // (settles a pending ladder launch and the uncounted adds first)
+  if (n_rungs < 1 || first_rung < 0 || first_rung > e->hist.rungs - n_rungs)
+    return fail(PTM_ERR_INVALID, "%s: rungs %d .. %d are not all recorded (history_rungs = %d)", who, first_rung, first_rung + n_rungs - 1, e->hist.rungs);
+  if ((double)e->W * nfeat > 2.0e9 || (double)e->W * nrows > 4.0e18) return fail(PTM_ERR_INVALID, "%s: bad shape", who);
+  std::vector<EssSrc> src((size_t)n_rungs);
+  std::vector<char> wrapped((size_t)n_rungs, 0);
+  std::vector<int> steps_of;
+  for (int r = 0; r < n_rungs; ++r) {
+    if ((rc = ess_ring_source_of(e, nh, first_rung + r, nfeat, &src[(size_t)r], &steps_of))) return rc;
+    bool wr = false;
+    if ((rc = moments_window_check(who, e, src[(size_t)r], steps_of, nrows, &wr))) return rc;
+    wrapped[(size_t)r] = wr ? 1 : 0;
+  }
+  if ((rc = moments_plan(e->stream, &e->ess_ws, &e->ess_ws_bytes, e->W, nfeat, cov, var, n_rungs, plan))) return rc;
+  for (int r = 0; r < n_rungs; ++r)
+    if ((rc = moments_launch(e->stream, *plan, r, src[(size_t)r], e->nhist + (size_t)(first_rung + r) * e->W, wrapped[(size_t)r] != 0, e->W, nfeat, nrows, cov, var)))
+      return rc;
+  return PTM_OK;
+}
+extern "C" int ptm_moments_rungs(ptm_engine* e, int first_rung, int n_rungs, int nfeat, int nrows, double* mean, double* cov, double* var, int64_t* count) {
+  if (!e || !mean) return fail(PTM_ERR_INVALID, "null argument");
+  NO_BATCH(e, "ptm_moments_rungs");
+  MomPlan pl;
+  int rc = moments_rungs_device("ptm_moments_rungs", e, first_rung, n_rungs, nfeat, nrows, cov != nullptr, var != nullptr, &pl);
+  if (rc) return rc;
+  const size_t F = pl.F, R = (size_t)n_rungs, n_out = cov || var ? R * pl.out_stride : 0;
+  hipStream_t st = e->stream;
+  std::vector<double> h_mean(R * F), h_out(n_out);   // (staged: the caller's arrays stay untouched when a flag is raised, and the call waits once)
+  std::vector<int> flag(R, 0);
+  HIPCHK(hipMemcpyAsync(h_mean.data(), pl.d_mean, R * F * 8, hipMemcpyDeviceToHost, st));
+  if (n_out) HIPCHK(hipMemcpyAsync(h_out.data(), pl.d_out, n_out * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(flag.data(), pl.d_flag, R * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int f : flag)
+    if (f) return fail(PTM_ERR_INVALID, "ptm_moments_rungs: history_capacity must hold the window (%d rows no longer hold the newest %d saved rows of every chain)", e->hist.cap, nrows);
+  memcpy(mean, h_mean.data(), R * F * 8);
+  if (cov) memcpy(cov, h_out.data(), n_out * 8);
+  else if (var) memcpy(var, h_out.data(), n_out * 8);
+  if (cov && var)
+    for (size_t r = 0; r < R; ++r)
+      for (size_t f = 0; f < F; ++f) var[r * F + f] = cov[(r * F + f) * F + f];   // (the diagonal pair's quotient: the same bits)
+  if (count) *count = (int64_t)e->W * nrows;
+  return PTM_OK;
 }
 extern "C" int ptm_moments_series(int device, const double* series, int64_t n, int nseries, int nfeat, int nrows, double* mean, double* cov, double* var,
                                   double* walker_sum, int64_t* count) {
@@ -3946,6 +4066,105 @@ extern "C" int ptm_moments_series(int device, const double* series, int64_t n, i
   return moments_run("ptm_moments_series", nullptr, &S.ws, &S.ws_bytes, S.src, nullptr, false, nseries, nfeat, nrows, mean, cov, var, walker_sum, count);
 }
 extern "C" int ptm_moments_tile_rows(int nfeat) { return nfeat >= 1 && nfeat <= MOM_COV_NFEAT_MAX ? moments_tile_rows(nfeat) : 0; }
+
+// ---- Gaussian proposal factors of a batch of covariances; every rung's proposal from its own samples (ptm_eigen_kernels.hpp) ----
+// gaussian_prop::eigen_factor (ptmcmc_amd/host/ptmcmc_gpu.hh) for n_mat matrices at d_cov, one workgroup each.  d_qt: [n_mat][n*n],
+// needed above EIG_Q_LDS_N_MAX dimensions.
+static int eigen_launch(hipStream_t st, const double* d_cov, int n_mat, int n, double scale, double* d_qt, double* d_fac, double* d_lam, int32_t* d_sweeps) {
+  const size_t lds = eigen_lds_bytes(n);
+  void (*const kf)(const double*, int, double, double*, double*, double*, int32_t*) = eigen_q_in_lds(n) ? eigen_factor_kernel<true> : eigen_factor_kernel<false>;
+  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kf, dim3((unsigned)n_mat), dim3((unsigned)eigen_threads(n)), lds, st, d_cov, n, scale, d_qt, d_fac, d_lam, d_sweeps);
+  HIPCHK(hipGetLastError());
+  return PTM_OK;
+}
+extern "C" int ptm_eigen_factors(int device, const double* cov, int n_mat, int n, double* factors, double* lambda, int32_t* sweeps) {
+  if (!cov || !factors) return fail(PTM_ERR_INVALID, "null argument");
+  if (n < 1 || n > EIG_N_MAX) return fail(PTM_ERR_INVALID, "ptm_eigen_factors: n must be in 1..%d", EIG_N_MAX);
+  if (n_mat < 1 || (double)n_mat * n * n > 2.0e9) return fail(PTM_ERR_INVALID, "ptm_eigen_factors: bad shape");
+  int rc = need_device();
+  if (rc) return rc;
+  struct Scope {
+    void* ws = nullptr;
+    int device_before = -1;
+    ~Scope() {
+      if (ws) (void)hipFree(ws);
+      if (device_before >= 0) (void)hipSetDevice(device_before);
+    }
+  } S;
+  if (device >= 0) {
+    int cur = -1;
+    HIPCHK(hipGetDevice(&cur));
+    if (cur != device) { HIPCHK(hipSetDevice(device)); S.device_before = cur; }
+  }
+  const size_t M = (size_t)n_mat, nn = (size_t)n * n;
+  const size_t o_cov = 0, o_fac = o_cov + ess_align(M * nn * 8), o_qt = o_fac + ess_align(M * nn * 8), o_lam = o_qt + (eigen_q_in_lds(n) ? 0 : ess_align(M * nn * 8)),
+               o_sw = o_lam + ess_align(M * n * 8), total = o_sw + ess_align(M * 4);
+  HIPCHK(hipMalloc(&S.ws, total));
+  unsigned char* b = (unsigned char*)S.ws;
+  double *d_cov = (double*)(b + o_cov), *d_fac = (double*)(b + o_fac), *d_qt = (double*)(b + o_qt), *d_lam = (double*)(b + o_lam);
+  int32_t* d_sw = (int32_t*)(b + o_sw);
+  HIPCHK(hipMemcpy(d_cov, cov, M * nn * 8, hipMemcpyHostToDevice));
+  if ((rc = eigen_launch(nullptr, d_cov, n_mat, n, 1.0, d_qt, d_fac, d_lam, d_sw))) return rc;
+  HIPCHK(hipMemcpy(factors, d_fac, M * nn * 8, hipMemcpyDeviceToHost));
+  if (lambda) HIPCHK(hipMemcpy(lambda, d_lam, M * n * 8, hipMemcpyDeviceToHost));
+  if (sweeps) HIPCHK(hipMemcpy(sweeps, d_sw, M * 4, hipMemcpyDeviceToHost));
+  return PTM_OK;
+}
+
+// Every rung's Gaussian factor from that rung's own pooled moments: moments and eigen-decompositions stay on the device; the factors
+// come back once for the packer that ptm_set_proposal_rung uses (install_rung_factor).
+extern "C" int ptm_adapt_proposals(ptm_engine* e, int first_rung, int n_rungs, int nrows, double scale, int32_t* status, double* factors_out) {
+  if (!e || !status) return fail(PTM_ERR_INVALID, "null argument");
+  if (e->fetch_depth > 0) return fail(PTM_ERR_UNSUPPORTED, "ptm_adapt_proposals between ptm_batch_begin and ptm_batch_end (only reads go there)");
+  if (!e->have_prop) return fail(PTM_ERR_INVALID, "set all proposals first (ptm_set_proposals)");
+  if (user_prop(e)) return fail(PTM_ERR_INVALID, "ptm_adapt_proposals: user proposals (host-side or device) are set: the factors are not read");
+  if (!(scale > 0) || !(scale < HUGE_VAL)) return fail(PTM_ERR_INVALID, "ptm_adapt_proposals: scale must be finite and above 0");
+  if (e->prop_kind == KIND_LOWER) return fail(PTM_ERR_UNSUPPORTED, "ptm_adapt_proposals: no Cholesky form (PTM_PROP_LOWER) is built");
+  const bool diag = e->prop_kind == KIND_DIAG;
+  const int D = e->D;
+  if (!diag && D > EIG_N_MAX) return fail(PTM_ERR_UNSUPPORTED, "ptm_adapt_proposals: dense factors are offered up to %d dimensions", EIG_N_MAX);
+  MomPlan pl;
+  int rc = moments_rungs_device("ptm_adapt_proposals", e, first_rung, n_rungs, D, nrows, !diag, diag, &pl);
+  if (rc) return rc;
+  const size_t R = (size_t)n_rungs, fsz = diag ? (size_t)D : (size_t)D * D;
+  const bool qt = !diag && !eigen_q_in_lds(D);
+  const size_t o_fac = 0, o_qt = o_fac + ess_align(R * fsz * 8), o_lam = o_qt + (qt ? ess_align(R * fsz * 8) : 0), o_st = o_lam + ess_align(R * D * 8),
+               total = o_st + ess_align(R * 4);
+  hipStream_t st = e->stream;
+  if (e->eig_ws_bytes < total) {
+    if (e->eig_ws) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(e->eig_ws)); e->eig_ws = nullptr; e->eig_ws_bytes = 0; }
+    HIPCHK(hipMalloc(&e->eig_ws, total));
+    e->eig_ws_bytes = total;
+  }
+  unsigned char* b = (unsigned char*)e->eig_ws;
+  double *d_fac = (double*)(b + o_fac), *d_qt = (double*)(b + o_qt), *d_lam = (double*)(b + o_lam);
+  int32_t* d_st = (int32_t*)(b + o_st);
+  if (diag) {
+    hipLaunchKernelGGL(diag_factor_kernel, dim3((unsigned)R), dim3(EIG_STATUS_THREADS), 0, st, (const double*)pl.d_out, D, scale, d_fac, d_st);
+    HIPCHK(hipGetLastError());
+  } else {
+    if ((rc = eigen_launch(st, pl.d_out, n_rungs, D, scale, d_qt, d_fac, d_lam, nullptr))) return rc;
+    hipLaunchKernelGGL(eigen_status_kernel, dim3((unsigned)R), dim3(EIG_STATUS_THREADS), 0, st, (const double*)pl.d_out, (const double*)d_lam, D, d_st);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> fac(R * fsz);
+  std::vector<int32_t> stat(R, 0);
+  HIPCHK(hipMemcpyAsync(fac.data(), d_fac, R * fsz * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(stat.data(), d_st, R * 4, hipMemcpyDeviceToHost, st));
+  if ((rc = moments_flags("ptm_adapt_proposals", st, pl, n_rungs, e->hist.cap, nrows))) return rc;   // (the wait; nothing has changed yet)
+  std::vector<std::vector<double> > pending;   // the host images of the enqueued copies: one wait for all the rungs
+  pending.reserve(2 * R);
+  for (size_t r = 0; r < R; ++r)
+    if (stat[r] == 0 && (rc = install_rung_factor(e, first_rung + (int)r, fac.data() + r * fsz, &pending))) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+  HIPCHK(hipStreamSynchronize(st));
+  memcpy(status, stat.data(), R * 4);
+  if (factors_out) memcpy(factors_out, fac.data(), R * fsz * 8);
+  return PTM_OK;
+}
 
 // ---- exact posterior quantiles of a rung on the device (ptm_quantiles_kernels.hpp) -------------------------------------------
 // quantile_estimator (ptmcmc_amd/host/ptmcmc_gpu.hh) on the ring where it lies, or on a caller's series: radix selection of the

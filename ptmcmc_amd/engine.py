@@ -37,6 +37,7 @@ EXPORTS = [
     "ptm_log_evidence",
     "ptm_rhat", "ptm_rhat_series",
     "ptm_moments", "ptm_moments_series", "ptm_moments_tile_rows",
+    "ptm_moments_rungs", "ptm_eigen_factors", "ptm_adapt_proposals",
     "ptm_quantiles", "ptm_quantiles_series", "ptm_quantiles_last_path",
     "ptm_histograms", "ptm_histograms_series", "ptm_histograms_last_launch",
     "ptm_get_prefilter_counts",
@@ -213,6 +214,10 @@ def load():
         L.ptm_moments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_moments_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_moments_tile_rows.argtypes = [C.c_int]
+    if hasattr(L, "ptm_adapt_proposals"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_moments_rungs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _i64p]
+        L.ptm_eigen_factors.argtypes = [C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _i32p]
+        L.ptm_adapt_proposals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, _i32p, _dp]
     if hasattr(L, "ptm_quantiles"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
         L.ptm_quantiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
         L.ptm_quantiles_series.argtypes = [C.c_int, _dp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _i64p]
@@ -362,6 +367,23 @@ def moments_series(series, nrows=None, cov=True, walker_sums=False, out=None, de
         nrows = n
     o = _moments_outputs(ns, nf, cov, walker_sums, out)
     return _moments_call(load().ptm_moments_series, (device, _d(a), n, ns, nf, int(nrows)), o)
+
+
+def eigen_factors(cov, lambdas=False, sweeps=False, device=-1):
+    """the Gaussian proposal factors F = V diag(sqrt(max(lambda, 0))) of symmetric matrices cov [n_mat, n, n] (or one, [n, n]) by the
+    facade's cyclic Jacobi, on the device, with the host's bits (ptm_eigen_factors): F shaped like cov; lambdas=True adds the ascending
+    eigenvalues [n_mat, n], sweeps=True the sweeps that rotated [n_mat] (a tuple then)."""
+    a = np.ascontiguousarray(cov, dtype=np.float64)
+    if a.ndim not in (2, 3) or a.shape[-1] != a.shape[-2]:
+        raise PtmError("eigen_factors: cov must be [n, n] or [n_mat, n, n]")
+    n = a.shape[-1]
+    m = 1 if a.ndim == 2 else a.shape[0]
+    f = np.empty_like(a)
+    lam = np.empty(a.shape[:-1]) if lambdas else None
+    sw = np.empty(a.shape[:-2], dtype=np.int32) if sweeps else None
+    _chk(load().ptm_eigen_factors(device, _d(a), m, n, _d(f), None if lam is None else _d(lam), None if sw is None else sw.ctypes.data_as(_i32p)))
+    o = (f,) + ((lam,) if lambdas else ()) + ((sw,) if sweeps else ())
+    return f if len(o) == 1 else o
 
 
 def moments_tile_rows(nfeat):
@@ -688,6 +710,7 @@ class Engine:
         cfg.exchange_row_capacity = exchange_row_capacity
         cfg.history_rungs, cfg.history_capacity = history_rungs, history_capacity
         self.hist_rungs, self.hist_cap = history_rungs, history_capacity
+        self.prop_kind = None   # the kind of the factors set_proposals installed (adapt_proposals sizes its factors by it)
         self.add_every_n = add_every_n
         cfg.map_rungs = map_rungs
         self.map_rungs = map_rungs
@@ -923,6 +946,7 @@ class Engine:
         assert f.size == self.nloc * per, (f.size, self.nloc, per)
         o = None if one_d_frac is None else np.ascontiguousarray(one_d_frac, dtype=np.float64)
         _chk(self.L.ptm_set_proposals(self.h, kind, _d(f), None if o is None else _d(o)))
+        self.prop_kind = kind
 
     # -- state
     def set_states(self, X, llike=None):
@@ -1222,6 +1246,51 @@ class Engine:
             newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
             nrows = min(int(newest.min()), self.hist_cap)                      # (a wrapped ring holds its newest `capacity` rows)
         return _histograms_call(self.L.ptm_histograms, (self.h, int(rung), nf, int(nrows)), lo, hi, nbins, max(nf, 0), pairs, out)
+
+    def _common_window(self, first_rung, n_rungs):
+        """the largest window every walker of every rung of the range still has (posterior_moments' rule)"""
+        if not (0 <= first_rung and n_rungs >= 1 and first_rung + n_rungs <= self.hist_rungs):
+            raise PtmError("rungs %d .. %d are not all recorded (history_rungs = %d)" % (first_rung, first_rung + n_rungs - 1, self.hist_rungs))
+        nh = self.nhist.reshape(self.nloc, self.W)[first_rung:first_rung + n_rungs].astype(np.int64)
+        newest = np.where(nh > 0, 1 + (nh - 1) // self.add_every_n, 0)    # = the saved rows behind the start state
+        return min(int(newest.min()), self.hist_cap)                      # (a wrapped ring holds its newest `capacity` rows)
+
+    def moments_rungs(self, first_rung=0, n_rungs=None, nfeat=None, nrows=None, cov=None):
+        """posterior_moments for the local rungs first_rung .. first_rung + n_rungs - 1 (None: up to the last recorded rung) with one
+        wait and every rung's bits (ptm_moments_rungs): (mean[n_rungs, nfeat], cov[n_rungs, nfeat, nfeat] or None, var[n_rungs, nfeat],
+        N).  nrows None: the largest window every walker of every rung of the range still has."""
+        first_rung = int(first_rung)
+        nr = self.hist_rungs - first_rung if n_rungs is None else int(n_rungs)
+        nf = self.D if nfeat is None else int(nfeat)
+        if nrows is None:
+            nrows = self._common_window(first_rung, nr)
+        if cov is None:
+            cov = nf <= 128
+        m, k = max(nr, 0), max(nf, 0)
+        o = (np.empty((m, k)), np.empty((m, k, k)) if cov else None, np.empty((m, k)))
+        count = C.c_int64(0)
+        _chk(self.L.ptm_moments_rungs(self.h, first_rung, nr, nf, int(nrows), *[None if v is None else _d(v) for v in o], C.byref(count)))
+        return o + (int(count.value),)
+
+    def adapt_proposals(self, nrows=None, scale=None, first_rung=0, n_rungs=None, factors=False):
+        """every rung's Gaussian factor replaced by scale * (the eigen factor of its own pooled covariance) -- DIAG: scale * sqrt(var) --
+        over every walker's newest `nrows` saved rows, on the device (ptm_adapt_proposals).  scale None: 2.38 / sqrt(D); nrows None: the
+        largest window every walker of every rung of the range still has.  Returns status[n_rungs] (0 installed, 1 kept: not finite, 2 kept:
+        not positive definite); factors=True: (status, factors[n_rungs, D, D] or [n_rungs, D]), what was computed, kept rungs included."""
+        first_rung = int(first_rung)
+        nr = self.hist_rungs - first_rung if n_rungs is None else int(n_rungs)
+        if nrows is None:
+            nrows = self._common_window(first_rung, nr)
+        if scale is None:
+            scale = 2.38 / np.sqrt(self.D)
+        status = np.zeros(max(nr, 0), dtype=np.int32)
+        f = None
+        if factors:
+            if self.prop_kind is None:
+                raise PtmError("adapt_proposals(factors=True): the kind of the factors is not known (call Engine.set_proposals first)")
+            f = np.empty((max(nr, 0), self.D) if self.prop_kind == PROP_DIAG else (max(nr, 0), self.D, self.D))
+        _chk(self.L.ptm_adapt_proposals(self.h, first_rung, nr, int(nrows), float(scale), status.ctypes.data_as(_i32p), None if f is None else _d(f)))
+        return (status, f) if factors else status
 
     @property
     def exchange_row_capacity(self):

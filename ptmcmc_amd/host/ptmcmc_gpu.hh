@@ -830,8 +830,11 @@ class gaussian_prop : public proposal_distribution {  // proposal_distribution.h
   int ndim;
   double oneDfrac;
 
-  // factor = V * diag(sqrt(lambda)) so that offset = factor * z as in hh:207-213 (eigenvalues ascending, hh:173-176)
-  static void eigen_factor(const std::vector<double>& A, int n, std::vector<double>& F) {
+
+ public:
+  // factor = V * diag(sqrt(lambda)) so that offset = factor * z as in hh:207-213 (eigenvalues ascending, hh:173-176); lambda_out: the
+  // eigenvalues (what ptm_eigen_factors restates on the device, and parallel_tempering_chains::adapt_gaussian_proposals' host route uses)
+  static void eigen_factor(const std::vector<double>& A, int n, std::vector<double>& F, std::vector<double>* lambda_out = nullptr) {
     std::vector<double> lam, V;
     detail::jacobi_eigen(A, n, lam, V);
     F.assign(n * n, 0.0);
@@ -839,9 +842,9 @@ class gaussian_prop : public proposal_distribution {  // proposal_distribution.h
       const double sg = std::sqrt(lam[j] > 0 ? lam[j] : 0.0);
       for (int i = 0; i < n; i++) F[i * n + j] = V[i * n + j] * sg;
     }
+    if (lambda_out) *lambda_out = lam;
   }
 
- public:
   gaussian_prop(const std::valarray<double>& sigmas, double oneDfrac = 0.0, bool scaleWithTemp = false)
       : identity_trans(true), factor(std::begin(sigmas), std::end(sigmas)), ndim(sigmas.size()), oneDfrac(oneDfrac) { check(); }
   gaussian_prop(const std::vector<double>& sigmas, double oneDfrac = 0.0, bool scaleWithTemp = false)
@@ -3772,6 +3775,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
       if (host_mode) build_engine(false);
       for (int i = 0; i < Ntemps; i++) props.push_back(proposal.clone());
       ptm_check(ptm_set_proposals(eng, kind, all.data(), odfs.data()), "set_proposals");
+      dev_prop_kind = kind;
       std::vector<double> cum, sc, od;
       proposal_distribution_set* ps = dynamic_cast<proposal_distribution_set*>(&proposal);
       // temperature-dependent shares: every rung's clone builds its thresholds from the rung's temperature as it is now (set_chain,
@@ -3888,6 +3892,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   // per-rung factors for proposals that differ by rung (what user_gaussian_prop's check_update achieves in the reference)
   void set_proposal_factors(int kind, const std::vector<double>& factors, const std::vector<double>& oneDfracs = std::vector<double>()) {
     ptm_check(ptm_set_proposals(eng, kind, factors.data(), oneDfracs.empty() ? nullptr : oneDfracs.data()), "set_proposals");
+    dev_prop_kind = kind;
   }
   void step() override { step_in_bins(1, [this](int) { step_one(); }); }
   void step_one() {
@@ -4229,6 +4234,75 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
   bool moments_dev_last = false;
   bool moments_ran_on_device() const { return moments_dev_last; }   // the last posterior_moments of this ladder ran the device's kernels
+  // ---- every recorded rung's Gaussian factor from that rung's own samples (what user_gaussian_prop::check_update / reset_dist do for
+  // one chain in the reference, proposal_distribution.cc:340-441): every replica's newest `nrows` saved rows (< 0: the largest window
+  // every replica of every recorded rung has), factor = scale * eigen_factor(pooled covariance) (DENSE) or sigma = scale * sqrt(var)
+  // (DIAG); scale <= 0: 2.38 / sqrt(dim).  A rung whose covariance is not finite or not positive definite keeps its factor.  The
+  // device does all of it in one call (ptm_adapt_proposals); with PTM_HOST_PROPOSAL_ADAPT=1 the host route runs instead --
+  // posterior_moments of every rung, gaussian_prop::eigen_factor, ptm_set_proposal_rung -- and gives the same bits.  With host-side or
+  // device user proposals, a Cholesky factor or no ring nothing is adapted (said once).  Returns the rungs that were set.
+  struct proposal_adapt_result { int rows = 0, rungs = 0, set = 0, not_finite = 0, not_positive = 0; };
+  bool proposal_adapt_on_device_possible() {
+    static const bool off = [] { const char* v = getenv("PTM_HOST_PROPOSAL_ADAPT"); return v && *v && *v != '0'; }();   // (A/B: keep the host route)
+    return !(off || host_mode || hist_rows <= 0);
+  }
+  proposal_adapt_result adapt_gaussian_proposals(int nrows = -1, double scale = -1.0) {
+    proposal_adapt_result res;
+    proposal_adapt_dev_last = false;
+    const int nr = history_rungs();
+    const char* why = host_mode ? "the proposals are drawn on the host" : user_dev ? "the proposals are a device_proposal's" : dev_prop_kind < 0 ? "no Gaussian factors are set" :
+                      dev_prop_kind == PTM_PROP_LOWER ? "the factors are Cholesky factors" : (dev_prop_kind == PTM_PROP_DENSE && dim > 128) ? "dense factors are adapted up to 128 parameters" :
+                      nr <= 0 ? "no history is kept" : nullptr;
+    if (why) {
+      if (!proposal_adapt_said) std::cout << "parallel_tempering_chains::adapt_gaussian_proposals: nothing is adapted (" << why << ")" << std::endl;
+      proposal_adapt_said = true;
+      return res;
+    }
+    if (!(scale > 0)) scale = 2.38 / std::sqrt((double)dim);
+    if (nrows < 0) {
+      std::vector<int64_t> nh((size_t)Ntemps * W);
+      ptm_check(ptm_get_array(eng, PTM_ARR_NHIST, nh.data()), "adapt_gaussian_proposals");
+      long long have = -1;
+      for (size_t c = 0; c < (size_t)nr * W; c++) {
+        const long long newest = nh[c] > 0 ? rhat_estimator::newest_row(nh[c], add_every_N) : 0;
+        if (have < 0 || newest < have) have = newest;
+      }
+      if (have > hist_rows) have = hist_rows;
+      nrows = (int)have;
+    }
+    res.rows = nrows; res.rungs = nr;
+    std::vector<int32_t> status((size_t)nr, 0);
+    if (proposal_adapt_on_device_possible()) {
+      ptm_check(ptm_adapt_proposals(eng, 0, nr, nrows, scale, status.data(), nullptr), "adapt_gaussian_proposals");
+      proposal_adapt_dev_last = true;
+    } else {
+      const bool diag = dev_prop_kind == PTM_PROP_DIAG;
+      for (int r = 0; r < nr; r++) {
+        const moments_estimator::result m = posterior_moments(r, dim, nrows);
+        const std::vector<double>& in = diag ? m.var : m.cov;
+        bool finite = true;
+        for (size_t k = 0; k < in.size(); k++) finite = finite && std::isfinite(in[k]);
+        std::vector<double> f;
+        bool positive = true;
+        if (diag) {
+          f.resize((size_t)dim);
+          for (int d = 0; d < dim; d++) { positive = positive && m.var[(size_t)d] > 0; f[(size_t)d] = scale * std::sqrt(m.var[(size_t)d]); }
+        } else {
+          std::vector<double> lam;
+          gaussian_prop::eigen_factor(m.cov, dim, f, &lam);
+          for (size_t k = 0; k < f.size(); k++) f[k] = scale * f[k];
+          positive = lam[0] > 0;
+        }
+        status[(size_t)r] = !finite ? 1 : (positive ? 0 : 2);
+        if (status[(size_t)r] == 0) ptm_check(ptm_set_proposal_rung(eng, r, f.data(), -1.0), "adapt_gaussian_proposals");
+      }
+    }
+    for (int r = 0; r < nr; r++) { res.set += status[(size_t)r] == 0; res.not_finite += status[(size_t)r] == 1; res.not_positive += status[(size_t)r] == 2; }
+    return res;
+  }
+  bool proposal_adapt_dev_last = false, proposal_adapt_said = false;
+  int dev_prop_kind = -1;   // the kind of the factors on the device (ptm_set_proposals), -1: none
+  bool proposal_adapt_ran_on_device() const { return proposal_adapt_dev_last; }   // the last adapt_gaussian_proposals ran the device's kernels
   // ---- exact pooled quantiles over the replicas of rung `rung` (quantile_estimator above): every replica's newest `nrows` saved
   // rows (< 0: all that every replica has), the first `nfeat` parameters, at the probabilities `probs`.  The device selects from its
   // own ring (ptm_quantiles: the host estimator's bits) when the ring is there; with host-side proposals (the history is the host
@@ -4710,6 +4784,8 @@ class ptmcmc_sampler : public bayes_sampler {
   double ess_stop, prop_adapt_rate, dpriormin, pt_stop_evid_err = 0, rhat_stop = -1;
   int nreplicas, replica_begin = 0, device = -1;
   std::string covariance_out, quantiles_out, corner_out;
+  int prop_cov_adapt_every = 0, prop_cov_adapt_rows = -1;   // every so many steps during burn-in, every rung's Gaussian factor from its own samples
+  double prop_cov_adapt_scale = -1;
   std::vector<double> quantile_probs;
   int corner_bins = 20;
   double corner_range = 1.0;
@@ -4741,6 +4817,9 @@ class ptmcmc_sampler : public bayes_sampler {
     ess_stop = flag<double>("chain_ess_stop");
     rhat_stop = flag<double>("chain_rhat_stop");
     covariance_out = flag<std::string>("covariance_out");
+    prop_cov_adapt_every = flag<int>("prop_cov_adapt_every");
+    prop_cov_adapt_rows = flag<int>("prop_cov_adapt_rows");
+    prop_cov_adapt_scale = flag<double>("prop_cov_adapt_scale");
     quantiles_out = flag<std::string>("quantiles_out");
     if (!quantiles_out.empty()) quantile_probs = parse_quantile_probs(flag<std::string>("quantile_probs"));
     corner_out = flag<std::string>("corner_out");
@@ -4838,6 +4917,9 @@ class ptmcmc_sampler : public bayes_sampler {
         {"replica_begin", "0", "Global index of this process's first replica (one process per GPU, disjoint ranges). [0]"},
         {"device", "-1", "GPU of this process. [-1: the current device, e.g. by HIP_VISIBLE_DEVICES]"},
         {"chain_rhat_stop", "-1.0", "Stop as soon as the split R-hat of the cold chains across the replicas, the largest over the parameters, is below this. [-1: never]"},
+        {"prop_cov_adapt_every", "0", "Every so many steps while the step is below burn_frac*nsteps, replace every recorded rung's Gaussian proposal factor by one from that rung's own sampled covariance. [0: never]"},
+        {"prop_cov_adapt_rows", "-1", "Saved rows of every replica that --prop_cov_adapt_every pools. [-1: the largest window every replica has, at most prop_cov_adapt_every/save_every]"},
+        {"prop_cov_adapt_scale", "-1.0", "Scale of the adapted factors. [-1: 2.38/sqrt(npar)]"},
         {"covariance_out", "", "At the end of the run write the cold chains' pooled posterior mean and covariance to this file (what --covariance_file reads)."},
         {"quantiles_out", "", "At the end of the run write the cold chains' pooled posterior quantiles of every parameter to this file."},
         {"quantile_probs", "0.05,0.5,0.95", "The probabilities of --quantiles_out, separated by commas (1 to 32 values in [0, 1]). [0.05,0.5,0.95]"},
@@ -5223,8 +5305,13 @@ class ptmcmc_sampler : public bayes_sampler {
       int last = istep + (every - istep % every) % every;
       if (last > chain_Nstep) last = chain_Nstep;
       if (checkp_at_step > istep && checkp_at_step <= last) last = checkp_at_step - 1;
+      if (prop_cov_adapt_every > 0) {   // ... or adapts the proposals: at multiples of prop_cov_adapt_every below the burn-in's end
+        const int next = istep + (prop_cov_adapt_every - istep % prop_cov_adapt_every) % prop_cov_adapt_every;
+        if (next < chain_nburn && next < last) last = next;
+      }
       cc->step_n(last - istep + 1);
       istep = last;
+      if (prop_cov_adapt_every > 0 && istep > 0 && 0 == istep % prop_cov_adapt_every && istep < chain_nburn) adapt_proposals();
       bool stop = false;
       if (0 == istep % every) {
         std::cout << "chain " << ic << " step " << istep << std::endl;
@@ -5284,6 +5371,20 @@ class ptmcmc_sampler : public bayes_sampler {
     if (!corner_out.empty()) write_corner(corner_out);
     std::cout << "Finished running chain " << ic << "." << std::endl;
     return 0;
+  }
+  // --prop_cov_adapt_every: every recorded rung's Gaussian factor from the rows saved since the last adaptation (or as many as
+  // --prop_cov_adapt_rows says), of every replica.  Only during burn-in: the rows the summaries keep come from fixed proposals.
+  void adapt_proposals() {
+    int rows = prop_cov_adapt_rows;
+    if (rows < 1) {
+      rows = prop_cov_adapt_every / std::max(1, save_every);
+      for (int r = 0; r < cc->history_rungs(); r++) rows = std::min(rows, cc->rhat_rows_available(r));
+    }
+    if (rows < 1 || (long long)rows * cc->replicas() < 2) return;   // (nothing saved yet to adapt to)
+    const parallel_tempering_chains::proposal_adapt_result r = cc->adapt_gaussian_proposals(rows, prop_cov_adapt_scale);
+    if (r.rungs <= 0) return;
+    std::cout << "Proposal factors from " << r.rows << " rows x " << cc->replicas() << " replicas: " << r.set << " of " << r.rungs << " rungs set, " << r.not_finite
+              << " kept (not finite), " << r.not_positive << " kept (not positive definite)" << (cc->proposal_adapt_ran_on_device() ? " (device)" : " (host)") << " at step " << istep << std::endl;
   }
   // ptmcmc_sampler::write_covariance / read_covariance (ptmcmc.cc:761-768, empty there).  The cold rung's pooled moments over the
   // newest (1 - burn_frac) share of the saved rows every replica has, in the format read_covariance reads.
