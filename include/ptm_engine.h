@@ -161,6 +161,26 @@ int ptm_target_device_rows(ptm_engine* e);
  * (ptm_set_states / ptm_init_from_prior_k), and that state x[dim]: bayes_likelihood::bestPost / bestState.  Ties go to the
  * earliest (step, local chain), a NaN never becomes the best; before any evaluation -inf and the zero state. */
 int ptm_get_best_evaluated(ptm_engine* e, double* lpost, double* x);
+/* A user PRIOR evaluated ON THE DEVICE, beside the device likelihood: what ptm_set_prior_callback is to ptm_set_target_callback.  The
+ * calling convention is ptm_loglike_device_fn's: fn is called on the HOST once per sweep (and by ptm_set_states / ptm_restore /
+ * ptm_debug_evaluate), in stream order; it enqueues its work on `stream` (a hipStream_t) and may return before that work has run.
+ * X_dev [n_rows][dim] row-major, natural dimension order, n_rows = ptm_target_device_rows.  Rows [0, *count_dev) are the VALID
+ * proposals -- those that passed stateSpace::enforce, what a host prior is shown -- in local-chain order; rows past the count hold the
+ * other chains' current states (set-up calls: copies of row 0), so a fixed-shape evaluation of all n_rows rows is safe.
+ * out_lprior_dev [n_rows]; -inf = outside the support.  The batch buffers are the engine's own, apart from the likelihood's.
+ * The step is then exchange kernel -> propose pass -> count + pack of the valid proposals -> the user's prior work -> prior gate
+ * (chain.cc:980, on the device) -> count + pack of the wanted proposals -> the user's likelihood work -> scatter (+ best) -> accept
+ * pass, all queued: ptm_step(n) returns without waiting.  The device-side prior (ptm_set_prior) is ignored for valid states while a
+ * device prior is set; ptm_set_states / ptm_restore hand it the valid states, and the kept best (ptm_get_best_evaluated) uses its values.
+ * Works with device proposals, differential evolution, mixtures, adaptive sets, evolving ladders, history, MAP and walker splits.
+ * Refused (PTM_ERR_UNSUPPORTED): without the device likelihood (at ptm_set_states, ptm_restore and every stepping call -- the setters may
+ * come in either order), beside a prior callback (the later call), with host-side proposals, on a rung shard, in partial sweeps and
+ * exchange phases, and by everything that draws from the prior (ptm_init_from_prior*, ptm_draw_prior_rows,
+ * ptm_set_proposal_prior_draw): draw the start states on the host.  fn = NULL removes it; the chains' log-priors are made anew by the
+ * next ptm_set_states / ptm_restore. */
+typedef void (*ptm_logprior_device_fn)(void* user, void* stream, int n_rows, int dim, const double* X_dev, const int32_t* count_dev,
+                                       double* out_lprior_dev);
+int ptm_set_prior_device(ptm_engine* e, ptm_logprior_device_fn fn, void* user);
 /* inverse temperatures of the GLOBAL ladder, beta[n_rungs] (chain.cc:1181-1183,1340) */
 int ptm_set_ladder(ptm_engine* e, const double* beta);
 /* parallel_tempering_chains::evolve_temps(rate, lpost_cut) (chain.hh:302-307; default-on in the sampler with rate 0.01,

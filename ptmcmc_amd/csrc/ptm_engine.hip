@@ -22,6 +22,7 @@
 #include "ptm_count_limit.hpp"
 #include "ptm_de_mfma_kernel.hpp"
 #include "ptm_devlike_kernels.hpp"
+#include "ptm_devprior_kernels.hpp"
 #include "ptm_devprop_kernels.hpp"
 #include "ptm_eigen_kernels.hpp"
 #include "ptm_ess_kernels.hpp"
@@ -155,6 +156,14 @@ struct ptm_engine {
   int *dl_rows = nullptr, *dl_chunks = nullptr;
   double *dl_xprop = nullptr, *dl_lprior_new = nullptr, *dl_llike_new = nullptr, *dl_best = nullptr;
   unsigned char* dl_gate = nullptr;
+  // device prior (ptm_set_prior_device; ptm_devprior_kernels.hpp): the user's function and this path's own batch (the likelihood's pack
+  // runs later in the same step with its own count and row -> chain index, and its batch may be the caller's memory): the packed valid
+  // proposals [Nc][D], their log-priors, the count, the row -> chain index and the pack's chunk totals
+  ptm_logprior_device_fn dprior = nullptr;
+  void* dprior_user = nullptr;
+  double *pr_x = nullptr, *pr_lp = nullptr;
+  int32_t* pr_count = nullptr;
+  int *pr_rows = nullptr, *pr_chunks = nullptr;
   // compacted sweep (partition_kernel): per-rung lists of the walkers that move, their counts; touched = an exchange phase
   // ran since the last sweep
   int *cidx = nullptr, *ccnt = nullptr;
@@ -555,7 +564,7 @@ extern "C" int ptm_engine_destroy(ptm_engine* e) {
                   e->ada_leaf, e->ada_dbl, e->ada_int, e->dl_own_x ? e->dl_x : nullptr, e->dl_own_ll ? e->dl_ll : nullptr, e->dl_count, e->dl_rows, e->dl_chunks, e->dl_xprop,
                   e->dl_lprior_new, e->dl_llike_new, e->dl_best, e->ess_ws, e->eig_ws,
                   e->dp_xcur, e->dp_xnew, e->dp_hast_k, e->dp_rung, e->dp_walker, e->dp_type_k, e->dp_valid_k, e->dp_acc_k, e->dp_count, e->dp_rows, e->dp_chunks,
-                  e->dp_xprop, e->dp_hastings, e->dp_htype, e->dp_hvalid, e->dp_acc_out};
+                  e->dp_xprop, e->dp_hastings, e->dp_htype, e->dp_hvalid, e->dp_acc_out, e->pr_x, e->pr_lp, e->pr_count, e->pr_rows, e->pr_chunks};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (e->h_sums) (void)hipHostFree(e->h_sums);
@@ -748,6 +757,7 @@ extern "C" int ptm_set_target_callback(ptm_engine* e, ptm_loglike_batch_fn fn, v
 extern "C" int ptm_set_prior_callback(ptm_engine* e, ptm_logprior_batch_fn fn, void* user) {
   SETTLE(e);
   if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  if (fn && e->dprior) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior beside a device prior is not built: remove that one first (ptm_set_prior_device)");
   if (fn && e->dfn) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior with a device likelihood is not built (ptm_set_target_device)");
   e->prior_cb = fn; e->prior_user = fn ? user : nullptr;
   e->lp_is_const = false;
@@ -764,6 +774,7 @@ extern "C" int ptm_set_proposal_callback(ptm_engine* e, ptm_propose_batch_fn pro
     return PTM_OK;
   }
   if (e->dfn) return fail(PTM_ERR_UNSUPPORTED, "host-side proposals with a device likelihood are not built (ptm_set_target_device)");
+  if (e->dprior) return fail(PTM_ERR_UNSUPPORTED, "host-side proposals with a device prior are not built (ptm_set_prior_device)");
   const size_t Nc = e->Nc, DP = e->DP;
   int rc = alloc_proposal_buffers(e);
   if (rc) return rc;
@@ -1203,6 +1214,7 @@ extern "C" int ptm_set_proposal_adaptive(ptm_engine* e, const ptm_adaptive_set* 
 // can the engine's prior be drawn from, dimension by dimension, on the device?  (what a prior member needs: ptm_set_proposal_prior_draw)
 static int prior_drawable(const ptm_engine* e) {
   if (e->prior_cb) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior (ptm_set_prior_callback) cannot be drawn from on the device: draw on the host (ptm_set_proposal_callback)");
+  if (e->dprior) return fail(PTM_ERR_UNSUPPORTED, "a user prior on the device (ptm_set_prior_device) cannot be drawn from on the device: draw in a device proposal (ptm_set_proposal_device)");
   for (int d = 0; d < e->D; ++d)
     if (e->h_ptype[d] == PTM_PRIOR_FLAT) return fail(PTM_ERR_UNSUPPORTED, "a flat prior (dimension %d) cannot be drawn from", d);
   return PTM_OK;
@@ -1504,13 +1516,8 @@ static int callback_host_part(ptm_engine* e) {
     for (size_t k = 0; k < vp.size(); ++k) {
       const size_t c = vp[k];
       const double beta = e->betaC ? hbeta[c] : e->h_beta[e->r0 + c / e->W];
-      const double bl = beta * hll[c];
-      const double cur_lpost = hlp[c] + bl;
-      const double oldlprior = cur_lpost - bl;
-      const double nl = out[k];
-      lpn[c] = nl;
-      const bool want = nl > -1e200 || nl - oldlprior > e->cfg.min_prior;
-      e->h_gate[c] = (unsigned char)(1 | (want ? 2 : 0));
+      lpn[c] = out[k];
+      e->h_gate[c] = prior_gate(out[k], hlp[c], hll[c], beta, e->cfg.min_prior);   // (ptm_devprior_kernels.hpp: the device prior's kernel applies the same function)
     }
     HIPCHK(hipMemcpyAsync(e->lprior_new, lpn.data(), Nc * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(copy_unless_shared(e->gate, e->h_gate, Nc, hipMemcpyHostToDevice, e->stream));
@@ -1609,6 +1616,112 @@ extern "C" int ptm_target_device_rows(ptm_engine* e) {
   return e->Nc;
 }
 
+// ---- device prior (ptm_set_prior_device) ----------------------------------------------------------------------------------
+extern "C" int ptm_set_prior_device(ptm_engine* e, ptm_logprior_device_fn fn, void* user) {
+  if (!e) return fail(PTM_ERR_INVALID, "null engine");
+  SETTLE(e);
+  NO_BATCH(e, "ptm_set_prior_device");
+  if (!fn) {   // back to the device-side prior of ptm_set_prior (the chains' lpriors are made anew by the next ptm_set_states / ptm_restore)
+    e->dprior = nullptr; e->dprior_user = nullptr;
+    return PTM_OK;
+  }
+  if (e->prior_cb) return fail(PTM_ERR_UNSUPPORTED, "a device prior beside a host-evaluated prior is not built: remove that one first (ptm_set_prior_callback)");
+  if (e->pcb) return fail(PTM_ERR_UNSUPPORTED, "host-side proposals with a device prior are not built (ptm_set_proposal_callback)");
+  if (e->nloc != e->Nt) return fail(PTM_ERR_UNSUPPORTED, "a device prior on a rung shard is not built: split such a population by walkers");
+  const size_t Nc = e->Nc, D = e->D;
+  int rc;
+  if (!e->pr_count &&
+      ((rc = dalloc(&e->pr_x, Nc * D)) || (rc = dalloc(&e->pr_lp, Nc)) || (rc = dalloc(&e->pr_rows, Nc)) ||
+       (rc = dalloc(&e->pr_chunks, (Nc + DL_CHUNK - 1) / DL_CHUNK)) || (rc = dalloc(&e->pr_count, 1))))
+    return rc;
+  e->dprior = fn; e->dprior_user = user;
+  e->lp_is_const = false;
+  return PTM_OK;
+}
+
+// a device prior runs between the propose pass and the device likelihood's pack: without that likelihood there is no place for it
+static int devprior_ready(const ptm_engine* e) {
+  if (e->dprior && !e->dfn) return fail(PTM_ERR_UNSUPPORTED, "a device prior needs the device likelihood (ptm_set_target_device)");
+  return PTM_OK;
+}
+
+// count + pack of the chains with (gate & 1) == 1 into the prior's batch, then the user's function on the stream.  xrest == nullptr: the
+// rows past the count become copies of row 0 (set-up: the other chains hold no state to trust)
+static int devprior_call(ptm_engine* e, const unsigned char* gate, const double* xsel, const double* xrest) {
+  const int n = e->Nc, D = e->D;
+  const int nchunk = (n + DL_CHUNK - 1) / DL_CHUNK;
+  hipLaunchKernelGGL(devlike_count_kernel, dim3(nchunk), dim3(DL_CHUNK), 0, e->stream, n, gate, 1, 1, e->pr_chunks);
+  HIPCHK(hipGetLastError());
+#define PTM_PR_PACK(N) case N: hipLaunchKernelGGL((devlike_pack_kernel<N>), dim3(nchunk), dim3(DL_CHUNK), 0, e->stream, n, D, nchunk, gate, 1, 1, \
+                                                  (const int*)e->pr_chunks, xsel, xrest, e->pr_x, e->pr_rows, e->pr_count); break;
+  switch (e->DP) {
+    PTM_PR_PACK(4) PTM_PR_PACK(8) PTM_PR_PACK(16) PTM_PR_PACK(32) PTM_PR_PACK(64) PTM_PR_PACK(128) PTM_PR_PACK(256) PTM_PR_PACK(512) PTM_PR_PACK(1024)
+    default: return fail(PTM_ERR_UNSUPPORTED, "dim > 1024 is not built");
+  }
+#undef PTM_PR_PACK
+  HIPCHK(hipGetLastError());
+  if (!xrest) {
+    const size_t tot = (size_t)n * D;
+    hipLaunchKernelGGL(devlike_fill_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, e->stream, n, D, (const int32_t*)e->pr_count, e->pr_x);
+    HIPCHK(hipGetLastError());
+  }
+  e->dprior(e->dprior_user, (void*)e->stream, n, D, e->pr_x, e->pr_count, e->pr_lp);
+  return PTM_OK;
+}
+
+// a step's prior phase, behind the propose pass: the valid proposals' log-priors from the user's function, then the prior gate on them
+// (devprior_gate_kernel): lprior_new and the gate bytes the likelihood's pack and the accept pass read.  Queued; nothing waits.
+static int devprior_stage(ptm_engine* e) {
+  const int n = e->Nc;
+  const double* xcur = xrows(e);
+  int rc = ensure_betaC(e);
+  if (rc) return rc;
+  if ((rc = devprior_call(e, e->dl_gate, e->dl_xprop, xcur))) return rc;
+  hipLaunchKernelGGL(devprior_gate_kernel, dim3((unsigned)((n + DEVPRIOR_THREADS - 1) / DEVPRIOR_THREADS)), dim3(DEVPRIOR_THREADS), 0, e->stream, n, e->W, e->r0,
+                     (const int32_t*)e->pr_count, (const int*)e->pr_rows, (const double*)e->pr_lp, (const double*)e->lp, (const double*)e->ll,
+                     (const double*)e->beta, (const double*)e->betaC, e->cfg.min_prior, e->dl_lprior_new, e->dl_gate);
+  HIPCHK(hipGetLastError());
+  return PTM_OK;
+}
+
+// set-up (ptm_set_states, ptm_restore): the user's log-priors replace what the device-side prior gave the valid states (lprior above
+// -inf), as host_prior_of_states does for a host prior; dl_gate is free between steps (the propose pass writes every chain's byte)
+static int devprior_of_states(ptm_engine* e) {
+  const int n = e->Nc;
+  const unsigned grid = (unsigned)((n + DEVPRIOR_THREADS - 1) / DEVPRIOR_THREADS);
+  const double* x = xrows(e);
+  hipLaunchKernelGGL(devprior_valid_kernel, dim3(grid), dim3(DEVPRIOR_THREADS), 0, e->stream, n, (const double*)e->lp, e->dl_gate);
+  HIPCHK(hipGetLastError());
+  int rc = devprior_call(e, e->dl_gate, x, nullptr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(devprior_states_kernel, dim3(grid), dim3(DEVPRIOR_THREADS), 0, e->stream, n, (const int32_t*)e->pr_count, (const int*)e->pr_rows,
+                     (const double*)e->pr_lp, e->lp);
+  HIPCHK(hipGetLastError());
+  return PTM_OK;
+}
+
+// the device prior of ptm_debug_evaluate's rows (natural order, enforced): those that are valid and inside the device-side prior, in
+// batches of the engine's n_rows (rows past the count: the batch's first row)
+static int devprior_debug(ptm_engine* e, const double* X, int n, const int32_t* valid, double* lprior) {
+  const size_t Nc = e->Nc, D = e->D;
+  std::vector<size_t> pick;
+  for (size_t k = 0; k < (size_t)n; ++k)
+    if (valid[k] && lprior[k] > -__builtin_inf()) pick.push_back(k);
+  std::vector<double> rows(Nc * D), out(Nc);
+  for (size_t k0 = 0; k0 < pick.size(); k0 += Nc) {
+    const size_t m = std::min(Nc, pick.size() - k0);
+    for (size_t k = 0; k < Nc; ++k) memcpy(&rows[k * D], X + pick[k0 + (k < m ? k : 0)] * D, D * 8);
+    const int32_t cnt = (int32_t)m;
+    HIPCHK(hipMemcpyAsync(e->pr_x, rows.data(), Nc * D * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pr_count, &cnt, 4, hipMemcpyHostToDevice, e->stream));
+    e->dprior(e->dprior_user, (void*)e->stream, (int)Nc, (int)D, e->pr_x, e->pr_count, e->pr_lp);
+    HIPCHK(hipMemcpyAsync(out.data(), e->pr_lp, m * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (rows, cnt and out are reused)
+    for (size_t k = 0; k < m; ++k) lprior[pick[k0 + k]] = out[k];
+  }
+  return PTM_OK;
+}
+
 extern "C" int ptm_get_best_evaluated(ptm_engine* e, double* lpost, double* x) {
   if (!e || !lpost) return fail(PTM_ERR_INVALID, "null argument");
   SETTLE(e);
@@ -1640,7 +1753,8 @@ static int devlike_debug(ptm_engine* e, const double* X, int n, double* llike) {
 }
 
 // a shard's exchange phases and partial sweeps: not with a device likelihood
-#define NO_DEVLIKE(e, name) do { if ((e) && (e)->dfn) return fail(PTM_ERR_UNSUPPORTED, name " with a device likelihood is not built (rung-sharded steps)"); } while (0)
+#define NO_DEVLIKE(e, name) do { if ((e) && (e)->dfn) return fail(PTM_ERR_UNSUPPORTED, name " with a device likelihood is not built (rung-sharded steps)"); \
+                                 if ((e) && (e)->dprior) return fail(PTM_ERR_UNSUPPORTED, name " with a device prior is not built (rung-sharded steps)"); } while (0)
 
 // box pre-pass: which local rungs it takes (ptm_sweep_plan.hpp: prefilter_flag), from the proposals' spread and the prior box.
 // pf_sigma follows every writer of prop_tiles (ptm_set_proposals, ptm_set_proposal_rung: there is no other -- mixtures, adaptive sets and
@@ -1745,6 +1859,7 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
   if (rung0 < 0 || nr < 0 || rung0 + nr > e->nloc) return fail(PTM_ERR_INVALID, "rung range out of the shard");
   p.c_begin = rung0 * e->W; p.c_end = (rung0 + nr) * e->W;
   if ((user_like(e) || user_prop(e)) && (rung0 != 0 || nr != e->nloc)) return fail(PTM_ERR_UNSUPPORTED, "partial sweeps with a user likelihood (host or device) or host-side proposals are not built");
+  { const int rc = devprior_ready(e); if (rc) return rc; }
   auto close_step = [&]() {
     e->step += 1; e->touched = false; e->step_booked = false;
     if (e->compact_step) { e->nhist_pending += 1; e->compact_step = false; }
@@ -1850,6 +1965,8 @@ static int launch_sweep(ptm_engine* e, int rung0 = 0, int nr = -1, bool last = t
     p.xprop = e->dl_xprop; p.lprior_new = e->dl_lprior_new; p.gate = e->dl_gate; p.llike_new = e->dl_llike_new;
     p.mode = 1;
     HIPCHK(launch(p));
+    // device prior: pack of the valid proposals -> the user's prior work -> prior gate, in front of the likelihood's pack
+    if (e->dprior) { const int rc = devprior_stage(e); if (rc) return rc; }
     { const int rc = devlike_eval(e, e->dl_gate, 2, 2, e->dl_xprop, xrows(e), e->dl_llike_new, nullptr, e->dl_lprior_new, true); if (rc) return rc; }
     p.mode = 2;
     HIPCHK(launch(p));
@@ -2033,6 +2150,7 @@ static int ready(ptm_engine* e) {
   if (!e->have_ladder) return fail(PTM_ERR_INVALID, "no ladder set (ptm_set_ladder)");
   if (!e->have_prop) return fail(PTM_ERR_INVALID, "no proposals set (ptm_set_proposals)");
   if (!e->have_state) return fail(PTM_ERR_INVALID, "no states set (ptm_set_states / ptm_init_from_prior)");
+  { const int rc = devprior_ready(e); if (rc) return rc; }
   if (e->prior_member >= 0) return prior_drawable(e);   // (the prior may have changed since the member was named)
   return PTM_OK;
 }
@@ -2042,7 +2160,7 @@ static int ready(ptm_engine* e) {
 // the box is never accepted) -- the exchange kernel then moves no lprior
 static int check_lp_const(ptm_engine* e) {
   e->lp_is_const = false;
-  if (!e->all_uniform || e->prior_cb) return PTM_OK;
+  if (!e->all_uniform || e->prior_cb || e->dprior) return PTM_OK;
   std::vector<double> lp((size_t)e->Nc);
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(lp.data(), e->lp, lp.size() * 8, hipMemcpyDeviceToHost));
@@ -2117,6 +2235,7 @@ extern "C" int ptm_set_states(ptm_engine* e, const double* X, const double* llik
 static int set_states(ptm_engine* e, const double* X, const double* llike, bool enforce) {
   if (!e || !X) return fail(PTM_ERR_INVALID, "null argument");
   if (!e->have_target && !llike) return fail(PTM_ERR_INVALID, "set the target first (or pass llike)");
+  { const int rc0 = devprior_ready(e); if (rc0) return rc0; }
   const size_t Nc = e->Nc, D = e->D, DP = e->DP;
   const std::vector<double> rows = pad_rows(X, Nc, D, DP);
   int rc;
@@ -2126,6 +2245,7 @@ static int set_states(ptm_engine* e, const double* X, const double* llike, bool 
   if (e->dfn) {
     // the device likelihood evaluates the (enforced) start states; the best posterior starts over with them
     if ((rc = devlike_reset_best(e))) return rc;
+    if (e->dprior && (rc = devprior_of_states(e))) return rc;   // (first: the kept best starts from lprior + llike with the user's lprior)
     if (!llike && (rc = devlike_eval(e, nullptr, 0, 0, xrows(e), xrows(e), e->ll, nullptr, e->lp, true))) return rc;
   }
   if (e->cb && !llike) {
@@ -2167,6 +2287,7 @@ extern "C" int ptm_init_from_prior_k(ptm_engine* e, int kdraw) {
   if (kdraw < 0 || kdraw > 8191) return fail(PTM_ERR_INVALID, "initial draw index out of range (0..8191)");
   if (!e->have_target) return fail(PTM_ERR_INVALID, "set the target first");
   if (e->prior_cb) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior cannot be drawn from here: draw the start states with its drawSample and pass them to ptm_set_states");
+  if (e->dprior) return fail(PTM_ERR_UNSUPPORTED, "a user prior on the device cannot be drawn from here: draw the start states with its drawSample and pass them to ptm_set_states");
   for (int d = 0; d < e->D; ++d)
     if (e->h_ptype[d] == PTM_PRIOR_FLAT)
       return fail(PTM_ERR_UNSUPPORTED, "a flat (improper) prior cannot be drawn from (dimension %d): pass start states", d);
@@ -2242,6 +2363,7 @@ extern "C" int ptm_draw_prior_rows(ptm_engine* e, int k_begin, int n, double* x_
   if (k_begin < 0 || k_begin + n - 1 > 8191) return fail(PTM_ERR_INVALID, "initial draw index out of range (0..8191)");
   if (!e->have_target) return fail(PTM_ERR_INVALID, "set the target first");
   if (e->prior_cb) return fail(PTM_ERR_UNSUPPORTED, "a host-evaluated prior cannot be drawn from here: draw with its drawSample");
+  if (e->dprior) return fail(PTM_ERR_UNSUPPORTED, "a user prior on the device cannot be drawn from here: draw with its drawSample");
   for (int d = 0; d < e->D; ++d)
     if (e->h_ptype[d] == PTM_PRIOR_FLAT)
       return fail(PTM_ERR_UNSUPPORTED, "a flat (improper) prior cannot be drawn from (dimension %d)", d);
@@ -3428,6 +3550,7 @@ extern "C" const char* ptm_sweep_kernel_name(ptm_engine* e) {
   if (de_mfma_sweep(e, e->Nc)) format_de_mfma_name(e->prop_kind == PTM_PROP_DENSE ? KIND_DENSE : KIND_LOWER, e->betaC != nullptr, b, sizeof b);
   else format_sweep_name(step_sweep_plan(e), b, sizeof b);   // (in PT steps; the plain sweeps of a big population visit every chain)
   e->kname = b;
+  if (e->dfn && e->dprior) e->kname += " + device prior";   // (pack of the valid proposals, the user's work, prior gate)
   if (e->dfn) e->kname += " + device likelihood";   // (propose pass, pack, the user's work, scatter, accept pass)
   return e->kname.c_str();
 }
@@ -4773,6 +4896,13 @@ extern "C" int ptm_debug_evaluate(ptm_engine* e, const double* X, int n, int32_t
   if (Xe) unpad_rows(rows, (size_t)n, D, DP, Xe);
   if (valid) HIPCHK(hipMemcpy(valid, dv, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (lprior) HIPCHK(hipMemcpy(lprior, dlp, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (lprior && e->dprior) {   // the device prior's log-priors of the enforced states that are valid
+    std::vector<double> xe((size_t)n * D);
+    std::vector<int32_t> hv((size_t)n);
+    unpad_rows(rows, (size_t)n, D, DP, xe.data());
+    HIPCHK(hipMemcpy(hv.data(), dv, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if ((rc = devprior_debug(e, xe.data(), n, hv.data(), lprior))) return rc;
+  }
   if (llike && e->have_target && !user_like(e)) HIPCHK(hipMemcpy(llike, dll, (size_t)n * 8, hipMemcpyDeviceToHost));
   if (llike && e->dfn) {   // the device likelihood's llikes of the enforced states
     std::vector<double> xe((size_t)n * D);

@@ -43,6 +43,7 @@ EXPORTS = [
     "ptm_get_prefilter_counts",
     "ptm_set_proposal_device",
     "ptm_nn_dist2", "ptm_nn_dist2_tile",
+    "ptm_set_prior_device",
 ]
 
 
@@ -195,6 +196,8 @@ def load():
         L.ptm_get_best_evaluated.argtypes = [C.c_void_p, _dp, _dp]
     if hasattr(L, "ptm_set_proposal_device"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
         L.ptm_set_proposal_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "ptm_set_prior_device"):   # (absent from older builds handed over through PTM_ENGINE_LIB for A/B timing)
+        L.ptm_set_prior_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "ptm_set_proposal_adaptive"):
         L.ptm_set_proposal_adaptive.argtypes = [C.c_void_p, C.POINTER(PtmAdaptiveSet), _dp, _dp, _dp, _dp, _i32p, _i32p]
         L.ptm_get_proposal_adapt_state.argtypes = [C.c_void_p, _dp, _dp, _i32p, _i32p]
@@ -814,6 +817,45 @@ class Engine:
         x = np.empty(self.D)
         _chk(self.L.ptm_get_best_evaluated(self.h, C.byref(lp), x.ctypes.data_as(_dp)))
         return lp.value, x
+
+    def set_prior_device(self, fn):
+        """user prior on the DEVICE (ptm_set_prior_device), beside set_target_device: fn(X, count, out) with torch views of the
+        engine's own buffers -- X (n_rows, D) float64, count a 1-element int32 tensor (rows [0, count) are the valid proposals, in
+        local-chain order; the rest hold in-support states), out (n_rows,) float64 to fill with log-priors (-inf outside the support).
+        It runs once per sweep with the engine's stream current, before the likelihood's function, and must only ENQUEUE its work (no
+        .item(), no copy to the host): step(n) queues n steps and returns.  Needs torch imported before the engine library (one HIP
+        runtime) and the device likelihood; start states come from set_states.  fn = None goes back to the built-in prior (set the
+        states again afterwards)."""
+        if fn is None:
+            _chk(self.L.ptm_set_prior_device(self.h, None, None))
+            return
+        import torch
+        if not TORCH_LOADED_FIRST:
+            raise PtmError("set_prior_device needs torch imported BEFORE the engine library was loaded (one HIP runtime per process: "
+                           "see ptmcmc_amd.parallel.EngineShard)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        views = {}
+
+        def view(ptr, shape, typestr):
+            key = (ptr, shape, typestr)
+            v = views.get(key)
+            if v is None:   # the engine's buffers are fixed for its lifetime: each is wrapped once
+                v = views[key] = _wrap_device(torch, ptr, shape, typestr, dev)
+            return v
+
+        def tramp(user, stream, n_rows, dim, xp, cp, op):
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                fn(view(xp, (n_rows, dim), "<f8"), view(cp, (1,), "<i4"), view(op, (n_rows,), "<f8"))
+        cb = LOGLIKE_DEVICE_FN(tramp)   # (ptm_logprior_device_fn has ptm_loglike_device_fn's shape)
+        self._keep += [cb, views]
+        _chk(self.L.ptm_set_prior_device(self.h, C.cast(cb, C.c_void_p), None))
+
+    def set_prior_device_c(self, fnptr, user=None):
+        """user prior on the device through a raw C function pointer of the ptm_logprior_device_fn shape (e.g. from a hipcc-built
+        .so: ctypes.cast(lib.my_launcher, ctypes.c_void_p)); user: the pointer it is handed"""
+        p = fnptr.value if isinstance(fnptr, C.c_void_p) else (C.cast(fnptr, C.c_void_p).value if isinstance(fnptr, C._CFuncPtr) else int(fnptr))
+        self._keep.append(fnptr)
+        _chk(self.L.ptm_set_prior_device(self.h, C.c_void_p(p), C.c_void_p(user) if user is not None else None))
 
     def set_prior_callback(self, fn, batched=False):
         """a prior evaluated on the host (ptm_set_prior_callback): the C shape of probability_function::evaluate_log

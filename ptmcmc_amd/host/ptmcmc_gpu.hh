@@ -480,6 +480,25 @@ class sampleable_probability_function : public probability_function {  // probab
   virtual bool describe(std::vector<int>& types, std::vector<double>& centers, std::vector<double>& halfwidths) const { return false; }
 };
 
+// A prior that is not a per-dimension product, evaluated ON THE DEVICE (ptm_set_prior_device) beside a device_likelihood: the engine
+// calls evaluate_log_prior_device once per sweep on its own stream with the VALID proposals in device memory (X_dev [n_rows][dim], rows
+// [0, *count_dev) to evaluate, the rest in-support states); it enqueues its work on `stream` (a hipStream_t) and returns; -inf = outside
+// the support.  The host evaluate_log and drawSample stay required: the start states are drawn on the host, and the ladder keeps the
+// host path (ptm_set_prior_callback) when the likelihood is no device_likelihood, with host-side proposals, or with PTM_DEVICE_PRIOR=0
+// in the environment.  Host and device must give the same bits for the two paths to walk the same chains.
+class device_prior : public sampleable_probability_function {
+ public:
+  device_prior(const stateSpace* space) : sampleable_probability_function(space) {}
+  virtual void evaluate_log_prior_device(void* stream, int n_rows, int dim, const double* X_dev, const int32_t* count_dev, double* out_dev) const = 0;
+  static void device_trampoline(void* self, void* stream, int n_rows, int dim, const double* X_dev, const int32_t* count_dev, double* out_dev) {
+    ((const device_prior*)self)->evaluate_log_prior_device(stream, n_rows, dim, X_dev, count_dev, out_dev);
+  }
+  static bool wanted() {
+    const char* v = getenv("PTM_DEVICE_PRIOR");
+    return !(v && *v == '0');
+  }
+};
+
 class mixed_dist_product : public sampleable_probability_function {  // probability_function.hh:141-170, .cc:219-262
  protected:
   std::valarray<int> types;
@@ -3565,6 +3584,7 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   bayes_likelihood* init_like = nullptr;
   const sampleable_probability_function* init_prior = nullptr;
   bool prior_on_host = false;   // the prior is not a per-dimension product: evaluated through ptm_set_prior_callback
+  bool prior_on_device = false; // ... or, a device_prior beside a device_likelihood, through ptm_set_prior_device (start states still drawn on the host)
   // C-ABI trampoline of a host-evaluated prior: probability_function::evaluate_log on every (valid) state of the batch
   static void prior_trampoline(void* self, const double* X, int n, int dim, double* out) {
     const sampleable_probability_function* pr = (const sampleable_probability_function*)self;
@@ -3590,6 +3610,15 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
   }
 
  private:
+  // The device route of a prior that does not describe itself: a device_prior beside a device_likelihood that takes the device, proposals
+  // not on the host, PTM_DEVICE_PRIOR not 0 in the environment.  Registers the likelihood (ptm_set_target_device) when it answers with
+  // the prior; nullptr: today's host route, nothing registered.
+  const device_prior* device_prior_route(bool host, bayes_likelihood* log_likelihood, const sampleable_probability_function* log_prior) {
+    const device_prior* dpr = dynamic_cast<const device_prior*>(log_prior);
+    if (!dpr || host || !device_prior::wanted()) return nullptr;
+    if (!dynamic_cast<device_likelihood*>(log_likelihood)) return nullptr;
+    return log_likelihood->describe_device_target(eng) ? dpr : nullptr;
+  }
   void build_engine(bool host) {
     if (eng) { engine_gone(eng); ptm_engine_destroy(eng); eng = nullptr; }
     bayes_likelihood* log_likelihood = init_like;
@@ -3637,12 +3666,17 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     }
     ptm_check(ptm_set_bounds(eng, lo.data(), hi.data(), xmin.data(), xmax.data()), "set_bounds");
     prior_on_host = !log_prior->describe(types, centers, halfwidths);
+    prior_on_device = false;
     if (!prior_on_host) {
       ptm_check(ptm_set_prior(eng, types.data(), centers.data(), halfwidths.data()), "set_prior");
       // (a device likelihood cannot serve host-side proposals, whose step waits on the host anyway: its host evaluate_log does)
       const bool skip_device = host && dynamic_cast<device_likelihood*>(log_likelihood) != nullptr;
       if (skip_device || !log_likelihood->describe_device_target(eng))
         ptm_check(ptm_set_target_callback(eng, &bayes_likelihood::batch_trampoline, log_likelihood), "set_target_callback");
+    } else if (const device_prior* dpr = device_prior_route(host, log_likelihood, log_prior)) {
+      // ... but a device_prior beside a device_likelihood that took the device: both run on the engine's stream, the step stays there
+      ptm_check(ptm_set_prior_device(eng, &device_prior::device_trampoline, (void*)dpr), "set_prior_device");
+      prior_on_device = true;
     } else {
       // a prior that is not a per-dimension product: evaluated on the host between the propose and the accept kernel, and so
       // is the likelihood then (whatever it is: its evaluate_log)
@@ -3864,7 +3898,9 @@ class parallel_tempering_chains : public chain {  // chain.hh:214-330, chain.cc:
     for (size_t d = 0; d < types.size(); d++) if (types[d] == PTM_PRIOR_FLAT) return false;
     return true;
   }
-  bool prior_evaluated_on_host() const { return prior_on_host; }   // the prior is not a per-dimension product (describe() == false)
+  bool prior_evaluated_on_host() const { return prior_on_host && !prior_on_device; }   // the prior is not a per-dimension product (describe() == false), and not a device_prior that took the device
+  bool prior_evaluated_on_device() const { return prior_on_device; }                  // a device_prior beside a device_likelihood (ptm_set_prior_device)
+  std::string step_kernel_name() const { return eng ? std::string(ptm_step_kernel_name(eng)) : std::string(); }   // the kernels a PT step of this ladder runs
   // chain::report_prop (chain.cc:2096-2109 flavour): every rung's proposal report, replica 0
   std::string report_prop(int style = 0) override {
     std::ostringstream ss;
